@@ -17,13 +17,21 @@ How the K timed steps are enqueued (--mode):
                    boundary separates two steps; every step does the full work and every per-step result equals that of
                    K separate launches (tests/test_gpu_chain.py).
   step             one t2d_step launch per step (rounds 1-2's headline).
-The line reports the other mode too (`alternates`), so both are driver-timed.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the step kernel is bound by fp64 VALU
 issue, not by HBM: the fraction of the VALU issue roof -- instructions per step from the committed rocprofv3 SQ pass of
 the same sources, checked by a source hash, over the step duration measured here with HIP events -- and the HBM figure
-beside it), `configs` (BASELINE.json's other configurations), `next_rows` (IDM, lidar, the ParkingEnv vector step),
-`gather` (N > 1) and `cpu_baseline` (the C oracle -- a port of the reference's algorithm -- on the host cores).
+beside it) and `gather` (N > 1).  A plain run does nothing else: set-up, clock ramp, warm-up, the timed steps, the line.
+
+--full adds every other measurement, each a run of its own after the timed region: the other step mode and the
+state-only outputs (`alternates`), the timed region without the clock ramp, the per-kernel HIP-event pass, power and
+clock under load and the stand-alone integrator per model (under `roofline`), `configs` (BASELINE.json's other
+configurations), `next_rows` (IDM, lidar, the ParkingEnv vector step), `closed_loop`, `strong` (N > 1: the fixed-total
+cases) and `cpu_baseline` (the C oracle -- a port of the reference's algorithm -- on the host cores).
+
+--dump-outputs DIR writes what the last timed step left for a caller -- the participants' state, the applied action, the
+event flags and the per-env result records (reward, status) -- as DIR/<name>.npy (float32 / float64), straight after the
+timed region.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -236,6 +244,37 @@ class Runner:
 
     def close(self):
         self.pool.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(pool, out_dir, outputs, prefix=""):
+    """What the pool's last step left for a caller, as out_dir/<prefix><name>.npy: per participant the state (x, y, heading,
+    speed; with --outputs all also vx / vy and the applied action) and the event flags, per env the reward and the status
+    of that step's result record (the 8 bytes a gather ships).  float32 fields as they are, integers as float64 (exact).
+    Above DUMP_LIMIT_BYTES in all, the same seeded sample of participants (and of envs) is taken from every array."""
+    from tactics2d_amd import layout as L
+    fields = [("x", L.F_X), ("y", L.F_Y), ("heading", L.F_HEADING), ("speed", L.F_SPEED)]
+    if outputs == "all":
+        fields += [("vx", L.F_VX), ("vy", L.F_VY), ("applied_accel", L.F_APPLIED0), ("applied_steer", L.F_APPLIED1)]
+    per_part = {name: pool.download(f) for name, f in fields}
+    per_part["flags"] = pool.download(L.F_FLAGS).astype(np.float64)
+    rec = pool.download(L.F_RECORD)[(pool.step_count() - 1) % L.RECORD_RING]   # [E, 2] u32: reward bits, 4 status bytes
+    per_env = dict(reward=np.ascontiguousarray(rec[:, 0]).view(np.float32),
+                   status=np.ascontiguousarray(rec[:, 1]).view(np.uint8).reshape(-1, 4).astype(np.float32))
+    total = sum(a.nbytes for a in per_part.values()) + sum(a.nbytes for a in per_env.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - (1 << 16)) / total   # (room for the .npy headers)
+        rng = np.random.default_rng(0)
+        for group in (per_part, per_env):
+            n = len(next(iter(group.values())))
+            idx = np.sort(rng.choice(n, max(1, int(n * keep)), replace=False))
+            for name in group:
+                group[name] = group[name][idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in {**per_part, **per_env}.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def integrator_per_model(variant, n_env=65536, A=64):
@@ -669,6 +708,11 @@ def main():
                     "adds the idm kernel to every step (not the metric configuration)")
     ap.add_argument("--clock-warm", type=int, default=3000, help="untimed steps of a scratch pool (same scene) before the "
                     "warm-up steps, so that the GPU has left its idle clocks when the timed region starts (0 = off)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every other measurement (alternates, "
+                    "per-kernel pass, power / clock, configs, next rows, closed loop, strong scaling, CPU baseline); "
+                    "the --no-* options above switch single ones off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (state, "
+                    "applied action, flags, per-env reward / status) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
 
     import torch
@@ -796,6 +840,8 @@ def main():
         torch.distributed.all_gather(allt, t)
         per_rank = [1e3 * float(x.item()) / args.steps for x in allt]
         elapsed = max(float(x.item()) for x in allt)
+    if args.dump_outputs:   # before anything else steps the measured pool
+        dump_outputs(run.pool, args.dump_outputs, args.outputs, "" if world == 1 else f"rank{rank}_")
 
     # ---- per-kernel pass (outside `value`): the same steps again with HIP events recorded on the launch stream around
     # every launch (the event packets cost ~2 us per launch).  At least PROF_MIN steps whatever --steps is, every
@@ -820,7 +866,7 @@ def main():
                 kern[name] = dict(avg_us=1e3 * ms / launches, launches=int(launches), steps_per_launch=steps_per_launch,
                                   avg_us_per_step=1e3 * ms / launches / steps_per_launch)
 
-    if not args.no_profile and gather is None:
+    if args.full and not args.no_profile and gather is None:
         n_prof = min(max(args.steps, PROF_MIN), 2000)
         n_prof -= n_prof % frag
         if chained_ok:
@@ -835,10 +881,10 @@ def main():
         run.pool.profile_enable(False)
 
     pclk = None
-    if world == 1 and gather is None and not args.no_profile:
+    if args.full and world == 1 and gather is None and not args.no_profile:
         pclk = power_clock_under_load(run, mode, frag)
     integ_models = None
-    if world == 1 and gather is None and not args.no_profile and args.config == "metric" and not args.no_next_rows:
+    if args.full and world == 1 and gather is None and not args.no_profile and args.config == "metric" and not args.no_next_rows:
         try:
             integ_models = integrator_per_model(args.variant)
         except Exception as exc:   # noqa: BLE001 -- a reported side measurement, never fatal for the line
@@ -846,7 +892,7 @@ def main():
 
     # ---- the other ways of running the same steps, driver-timed like `value` -----------------------------------------
     alternates = None
-    if world == 1 and gather is None and not args.no_alternates:
+    if args.full and world == 1 and gather is None and not args.no_alternates:
         alternates = {}
         other = "step" if mode == "chain" else "chain"
         if other == "step" or not args.idm:
@@ -866,7 +912,7 @@ def main():
     # ---- the same timed region once more WITHOUT the clock ramp: the GPU left idle for 0.4 s, then --warmup steps, then the
     # timed steps -- what the ramp contributes is driver-timed here, not quoted ---------------------------------------------
     no_ramp = None
-    if world == 1 and gather is None and args.clock_warm:
+    if args.full and world == 1 and gather is None and args.clock_warm:
         time.sleep(0.4)
         us, span = timed(run, mode, args.steps, args.warmup, frag, None)
         no_ramp = dict(value=N / (us * 1e-6), us_per_step=us, event_span_us_per_step=span,
@@ -881,7 +927,7 @@ def main():
 
     # ---- BASELINE.json's other configurations + the next rows, timed by the same process ------------------
     configs = nrows = None
-    if world == 1 and rank == 0 and args.config == "metric":
+    if args.full and world == 1 and rank == 0 and args.config == "metric":
         if not args.no_configs:
             configs = {}
             for name in ("cfg2", "cfg3", "cfg4", "cfg5"):
@@ -892,11 +938,11 @@ def main():
         if not args.no_next_rows:
             nrows = next_rows(dev, clock_warm, scene)
     cloop = None
-    if world == 1 and rank == 0 and not args.no_closed_loop and not args.idm:
+    if args.full and world == 1 and rank == 0 and not args.no_closed_loop and not args.idm:
         cloop = closed_loop(scene, dev, args.variant, args.steps, args.warmup, clock_warm, args.outputs)
     # ---- N > 1: the fixed-total (strong-scaling) reading of the same metric and of the sharded configs, every rank takes part --
     strong = None
-    if (world > 1 or os.environ.get("T2D_FORCE_STRONG")) and args.config == "metric" and not args.idm and not args.no_strong:
+    if args.full and (world > 1 or os.environ.get("T2D_FORCE_STRONG")) and args.config == "metric" and not args.idm and not args.no_strong:
         try:
             strong = strong_scaling(rank, world, dev, args, backend, native_gather, every, clock_warm)
             strong["note"] = ("fixed TOTAL sizes cut into contiguous env blocks over the ranks (weak `value` above: 4096 envs PER rank); the "
@@ -1032,8 +1078,9 @@ def main():
                                fragment=(min(frag, args.steps) if mode == "chain" else 1), fragment_max=frag,
                                outputs=args.outputs, host_enqueue_us_per_step=host_enqueue_us,
                                untimed_prewarm=f"{args.clock_warm} steps of a scratch pool with the same scene before every timed region (GPU clock "
-                                               f"ramp, the measured pool untouched), then {args.warmup} warm-up steps; per-kernel pass: "
-                                               f"{PREWARM} untimed steps of each kernel form, then up to {n_prof} timed ones",
+                                               f"ramp, the measured pool untouched), then {args.warmup} warm-up steps" +
+                                               (f"; per-kernel pass: {PREWARM} untimed steps of each kernel form, then up to {n_prof} "
+                                                f"timed ones" if n_prof else ""),
                                parallelism=(f"env-sharded x{world}, one async all-gather of the 8 B/env result records per {every} steps"
                                             if world > 1 else "single GPU")),
                    roofline=roof, closed_loop=cloop, value_without_clock_ramp=no_ramp, alternates=alternates, gather=gather_obj,
@@ -1042,7 +1089,7 @@ def main():
                    check=dict(state_finite=finite,
                               flag_rates=[float((flags & b).astype(bool).mean()) for b in (1, 2, 4, 8)],
                               truncated_frac=float(status[:, 3].mean())))
-        if not args.no_cpu_baseline and world == 1:   # reported at N = 1 only (the other ranks would sit in the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N = 1 only (the other ranks would sit in the barrier)
             out["cpu_baseline"] = cpu_baseline(scene)
         print(json.dumps(out))
     bad_world = (world > 1 and backend == "nccl" and not os.environ.get("T2D_GATHER_TORCH") and

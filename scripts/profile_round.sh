@@ -10,7 +10,7 @@ mkdir -p $OUT
 COMMON="--steps 1024 --warmup 128 --no-cpu-baseline --no-configs --no-next-rows --no-alternates --no-closed-loop"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU"
 for MODE in chain step; do
-  BENCH="python bench.py --mode $MODE $COMMON"
+  BENCH="python bench.py --full --mode $MODE $COMMON"   # (--full: the per-kernel pass runs the stand-alone kernels too)
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$MODE -o bench -- $BENCH > $OUT/bench_trace_$MODE.log 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$MODE -o bench -- $BENCH --no-profile > $OUT/bench_fetch_$MODE.log 2>&1
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write_$MODE -o bench -- $BENCH --no-profile > $OUT/bench_write_$MODE.log 2>&1
@@ -21,7 +21,7 @@ for MODE in chain step; do
   rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_ANY SQ_INSTS_SMEM SQ_INSTS_BRANCH --output-format csv -d $OUT/sqc2_$MODE -o bench -- $BENCH --no-profile > $OUT/bench_sqc2_$MODE.log 2>&1
 done
 # north_star's roofline kernel: an SQ pass of a run whose per-kernel pass launches the stand-alone integrator
-rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $OUT/sq_integ -o bench -- python bench.py --mode step --steps 64 --warmup 32 --clock-warm 0 --no-cpu-baseline --no-configs --no-next-rows --no-alternates --no-closed-loop > $OUT/bench_sq_integ.log 2>&1
+rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $OUT/sq_integ -o bench -- python bench.py --full --mode step --steps 64 --warmup 32 --clock-warm 0 --no-cpu-baseline --no-configs --no-next-rows --no-alternates --no-closed-loop > $OUT/bench_sq_integ.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/cal_fetch -o cal -- python scripts/calib_traffic.py > $OUT/cal_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/cal_write -o cal -- python scripts/calib_traffic.py > $OUT/cal_write.log 2>&1
 # the other BASELINE.json configurations (per-GPU shards), kernel time per config

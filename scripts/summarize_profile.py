@@ -67,7 +67,7 @@ epb = 256 >> log2A
 per_step_items = (((n_env + epb - 1) // epb + 7) & ~7) * 256    # work-items of one step in a chained launch
 
 summary = {"tag": tag, "source_sha256": B.source_hash(),
-           "commands": {m: f"python bench.py --mode {m} --steps 1024 --warmup 128 --no-cpu-baseline --no-configs --no-next-rows --no-alternates --no-closed-loop" for m in ("chain", "step")}}
+           "commands": {m: f"python bench.py --full --mode {m} --steps 1024 --warmup 128 --no-cpu-baseline --no-configs --no-next-rows --no-alternates --no-closed-loop" for m in ("chain", "step")}}
 stats_csv = []
 kt = {}
 for mode in ("chain", "step"):
