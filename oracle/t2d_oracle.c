@@ -1338,7 +1338,7 @@ int t2do_verify_state(const double* p, double lx, double ly, double lh, double l
     if (interval_ms == 0) return 1;
     const int model = (int)p[T2D_P_MODEL];
     const int flags = (int)p[T2D_P_RANGE_FLAGS];
-    if (model == T2D_MODEL_POINTMASS) { /* point_mass.py:249-259 */
+    if (model == T2D_MODEL_POINTMASS || model == T2D_MODEL_POINTMASS_EULER) { /* point_mass.py:249-259, either back-end */
         const double dt = (double)interval_ms / 1000;
         const double den = 2 / (dt * dt);
         const double ax = (x - lx - lvx * dt) * den;

@@ -855,7 +855,8 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
         int rc2 = init_iou_state(p, env_mask, hx.data(), hy.data());
         if (rc2 != T2D_OK) return rc2;
     }
-    p->types_used = types_used;
+    // (an armed auto-reset may put the snapshot's ids back into any env from the next step on)
+    p->types_used = types_used | (p->auto_reset ? p->snap_types : 0u);
     p->have_reset = true;
     return T2D_OK;
 }
@@ -1399,6 +1400,7 @@ int t2d_snapshot(t2d_pool* p) {
     T2D_HIP(p, hipMemcpy(p->d_snap_ids, p->v.ids, nb, hipMemcpyDeviceToDevice));
     T2D_HIP(p, hipMemcpy(p->d_snap_min_dist, p->d_min_dist, sizeof(double) * p->v.n_env, hipMemcpyDeviceToDevice));
     p->have_snapshot = true;
+    p->snap_types = p->types_used;   // (the ids just copied: t2d_restore and the auto-reset write them back)
     for (int k = 0; k < 6; ++k) p->v.snap[k] = p->d_snap[k];
     p->v.snap_ids = p->d_snap_ids;
     p->v.auto_reset = p->auto_reset ? 1 : 0;
@@ -1410,6 +1412,7 @@ int t2d_set_auto_reset(t2d_pool* p, int32_t on) {
     if (on && !p->have_snapshot) return fail(p, T2D_ERR_STATE, "t2d_snapshot must precede t2d_set_auto_reset");
     p->auto_reset = on != 0;
     p->v.auto_reset = p->auto_reset ? 1 : 0;
+    if (p->auto_reset) p->types_used |= p->snap_types;   // (the integrator's instantiation must carry the snapshot's models)
     return T2D_OK;
 }
 
@@ -1420,6 +1423,7 @@ int t2d_restore(t2d_pool* p, int32_t mode, void* hip_stream) {
     touch(p, (hipStream_t)hip_stream);
     if (mode == 0) p->chain_failed = false;   // (see t2d_reset)
     T2D_HIP(p, t2d::launch_restore(p->v, p->d_snap, p->d_snap_ids, mode, (hipStream_t)hip_stream));
+    p->types_used |= p->snap_types;
     return T2D_OK;
 }
 
@@ -1570,6 +1574,8 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     T2D_HIP(p, quiesce(p));
     p->have_reset = true;
     p->have_snapshot = true;
+    p->snap_types |= 1u;   // (every scene's agent is type 0: sv.ids_word, in the pool and in the snapshot)
+    p->types_used |= 1u;
     for (int k = 0; k < 6; ++k) p->v.snap[k] = p->d_snap[k];
     p->v.snap_ids = p->d_snap_ids;
     p->v.snap_omega[0] = p->v.snap_omega[1] = nullptr;

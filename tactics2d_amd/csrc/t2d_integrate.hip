@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void verify_kernel(PoolView pv, VerifyArgs 
         const double dt = (double)a.interval_ms / 1000;
         const double lx = (double)pv.x[i], ly = (double)pv.y[i];
         const double x = (double)a.x[i], y = (double)a.y[i];
-        if (model == T2D_MODEL_POINTMASS) {
+        if (model == T2D_MODEL_POINTMASS || model == T2D_MODEL_POINTMASS_EULER) {  // both back-ends: point_mass.py:234-259
             const double den = 2 / (dt * dt);
             const double ax = (x - lx - (double)pv.vx[i] * dt) * den;
             const double ay = (y - ly - (double)pv.vy[i] * dt) * den;

@@ -351,7 +351,9 @@ struct t2d_pool {
     bool ckpt_armed = false;       // every multi-step launch since the last quiesce was a CHAIN launch with a checkpoint
     uint32_t chain_sig = 0;        // shape (workgroups, split) of the last CHAIN launch whose counters d_chain holds; 0 = none
     uint32_t chain_fault = 0;      // t2d_debug_chain_fault
-    uint32_t types_used = 0;       // bit t: some active participant has type t (t2d_reset)
+    uint32_t types_used = 0;       // bit t: some active participant has type t (t2d_reset) -- or may have: every path that writes
+                                   // ids on the device ORs in what it writes (t2d_restore, an armed auto-reset, t2d_parking_scenes)
+    uint32_t snap_types = 0;       // bit t: some active participant of the snapshot has type t (t2d_snapshot, t2d_parking_scenes)
     int chain_depth = 1;           // steps per workgroup of the chained form of large pools (T2D_CHAIN_DEPTH in the environment)
     int device_cus = 0;            // compute units of the pool's device (read once)
     // result gather (the one collective of the path): RCCL communicator + a stream of its own, so that the steps that

@@ -189,7 +189,7 @@ class _BatchedModel:
         n = len(state)
         pool = self._pool(n)
         z = np.zeros(n, np.float32)
-        if self.model_id == L.MODEL_POINTMASS:
+        if self.model_id in (L.MODEL_POINTMASS, L.MODEL_POINTMASS_EULER):
             vx, vy = last_state.velocity
             pool.reset(last_state.x, last_state.y, z, z, np.zeros(n, np.uint8), vx=vx, vy=vy)
             return pool.verify_state(state.x, state.y, z, z, interval)

@@ -109,11 +109,9 @@ FORMS = [
 ]
 
 
-@pytest.mark.parametrize("name,make,chaining,split,form", FORMS, ids=[f[0] for f in FORMS])
-def test_every_form_of_step_n_against_the_oracle_chain(oracle, name, make, chaining, split, form):
-    from tactics2d_amd import layout as L, scenarios as S
+def _stressed_form_scene(make, rng):
+    from tactics2d_amd import scenarios as S
     sc = make(S)
-    rng = np.random.default_rng(31)
     if sc.A > 1:   # (stress jitter, test only: poses scattered so that collisions, off-lane and out-of-bound fire within 8 steps)
         sc.x = (sc.x + rng.normal(0, 1.5, sc.n)).astype(np.float32)
         sc.y = (sc.y + rng.normal(0, 1.0, sc.n)).astype(np.float32)
@@ -129,6 +127,14 @@ def test_every_form_of_step_n_against_the_oracle_chain(oracle, name, make, chain
     if sc.A == 1:
         still = np.arange(sc.n_env) % 4 <= 1
         r0[:, still] = 0.0
+    return sc, r0, r1
+
+
+@pytest.mark.parametrize("name,make,chaining,split,form", FORMS, ids=[f[0] for f in FORMS])
+def test_every_form_of_step_n_against_the_oracle_chain(oracle, name, make, chaining, split, form):
+    from tactics2d_amd import layout as L
+    rng = np.random.default_rng(31)
+    sc, r0, r1 = _stressed_form_scene(make, rng)
     start, got = _gpu_fragment(sc, r0, r1, chaining, split, form)
     envs = np.sort(rng.choice(sc.n_env, size=min(sc.n_env, N_SAMPLE), replace=False))
     ends = 0
@@ -151,6 +157,28 @@ def test_every_form_of_step_n_against_the_oracle_chain(oracle, name, make, chain
         st_last = steps[-1][0]
         assert np.array_equal(got[L.F_STATUS][e], st_last)
     assert ends > 0, "no sampled episode ended: the auto-reset inside the fragment was not exercised"
+
+
+@pytest.mark.parametrize("name,make,chaining,split,form", FORMS, ids=[f[0] for f in FORMS])
+def test_every_form_of_step_n_with_the_resummed_step_against_the_oracle_flags(oracle, name, make, chaining, split, form):
+    """The same fragments with integrator variant 3 (the fast variant with the resummed kinematic step forced on: what the fast
+    variant runs where the pool fills the GPU, as at bench.py's metric size).  The state is not the oracle's bit for bit
+    (tests/test_gpu_configs.py bounds it); the event flags are: at the fragment end, oracle.collide on the pool's own stored
+    poses equals the pool's flags and env flags in every env the last step did not end."""
+    from tactics2d_amd import layout as L
+    rng = np.random.default_rng(31)
+    sc, r0, r1 = _stressed_form_scene(make, rng)
+    _, got = _gpu_fragment(sc, r0, r1, chaining, split, form, variant="fast_resummed")
+    st = np.ascontiguousarray(got["record"][N_STEPS - 1, :, 1]).view(np.uint8).reshape(sc.n_env, 4)
+    live = (st[:, 2] | st[:, 3]) == 0
+    live_p = np.repeat(live, sc.A)
+    wf, we = oracle.collide(sc.rows, sc.n_env, sc.A, got[L.F_X], got[L.F_Y], got[L.F_HEADING], sc.type_id, sc.active,
+                            sc.static, sc.boundary, sc.boundary_valid, sc.lanes, 1)
+    bad = (wf != got[L.F_FLAGS]) & live_p
+    assert not bad.any(), (name, int(bad.sum()), np.nonzero(bad)[0][:8])
+    assert np.array_equal(we[live], got[L.F_ENV_FLAGS][live]), name
+    assert np.array_equal(got[L.F_STATUS], st), name
+    assert live.any() and (sc.A == 1 or (got[L.F_FLAGS][live_p] != 0).any()), name
 
 
 @pytest.mark.parametrize("tag", ["kin_100_5", "dyn_100_5", "kin_50_3", "dyn_50_3"])

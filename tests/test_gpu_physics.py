@@ -150,7 +150,8 @@ def test_pointmass_euler_mirror_and_pools_that_hold_both_backends(oracle):
     assert (gx[0::2] != gx[1::2]).any()                      # the two back-ends do differ where the speed is clipped
 
 
-@pytest.mark.parametrize("variant,only", [("fast", None), ("exact", None), ("fast", "pm"), ("exact", "pm"), ("fast", "kin"), ("exact", "kin")])
+@pytest.mark.parametrize("variant,only", [("fast", None), ("exact", None), ("fast", "pm"), ("exact", "pm"), ("fast", "kin"), ("exact", "kin"),
+                                          ("fast", "side"), ("exact", "side")])
 def test_four_per_lane_integrator_of_large_pools_equals_the_one_per_lane_step(variant, only):
     """Pools of >= 2 M participants without a dynamics row take t2d_integrate with four consecutive participants per lane
     (16-byte loads and stores: integrate_wide_kernel).  Same arithmetic per participant: every state column equals, bit for
@@ -161,6 +162,8 @@ def test_four_per_lane_integrator_of_large_pools_equals_the_one_per_lane_step(va
     rows, _ = S.full_type_table()
     # (only = "pm" / "kin": every active participant has that one model -- the instantiation that carries it alone)
     rows = rows[((rows[:, L.P_MODEL] == L.MODEL_KINEMATICS) & (only != "pm")) | ((rows[:, L.P_MODEL] == L.MODEL_POINTMASS) & (only != "kin"))]
+    if only == "side":   # + PointMass(backend="euler") and SingleTrackDrift rows: lanes of the side kernel (drift_impl), which
+        rows = np.concatenate([rows, _side_kernel_rows()])   # the wide kernel must leave exactly as drift_impl wrote them
     models = rows[:, L.P_MODEL].astype(int)
     usable = np.arange(len(rows))
     n_env, A = 32768, 64
@@ -168,7 +171,7 @@ def test_four_per_lane_integrator_of_large_pools_equals_the_one_per_lane_step(va
     rng = np.random.default_rng(12)
     tid = usable[rng.integers(0, usable.size, n)].astype(np.uint8)
     active = (rng.random(n) > 0.03).astype(np.uint8)
-    pm = models[tid] == L.MODEL_POINTMASS
+    pm = np.isin(models[tid], (L.MODEL_POINTMASS, L.MODEL_POINTMASS_EULER))
     x, y = np.float32(rng.uniform(-100, 100, n)), np.float32(rng.uniform(-100, 100, n))
     h = np.float32(rng.uniform(0, 6.28, n))
     v = np.float32(np.where(pm, rng.uniform(0.5, 1.4, n), rng.uniform(0.0, 9.0, n)))
@@ -192,6 +195,118 @@ def test_four_per_lane_integrator_of_large_pools_equals_the_one_per_lane_step(va
     off = active == 0
     assert np.array_equal(wide[0][off], x[off]) and np.array_equal(wide[3][off], v[off])
     assert (wide[0][~off] != x[~off]).mean() > 0.9
+    if only == "side":
+        side = (models[tid] >= L.MODEL_DRIFT) & ~off
+        assert side.sum() > 100000 and (wide[0][side] != x[side]).mean() > 0.9
+
+
+def _side_kernel_rows():
+    """A PointMass(backend="euler") and a SingleTrackDrift row: the models drift_impl integrates ahead of the step launch."""
+    from tactics2d_amd.physics import PointMass, SingleTrackDrift
+    euler = PointMass(speed_range=(0.0, 7.0), accel_range=(-1.5, 1.5), backend="euler")
+    drift = SingleTrackDrift(lf=1.262, lr=1.375, mass=1620.0, mass_height=0.7245, steer_range=(-0.524, 0.524),
+                             speed_range=(-16.67, 69.44), accel_range=(-11.0, 3.121))
+    return np.stack([euler.param_row(), drift.param_row()])
+
+
+def _wide_inputs(rng, rows, usable, n):
+    """Random participants of the types `usable` (rows of `rows`) for a pool of n: reset() keywords and the actions."""
+    from tactics2d_amd import layout as L
+    models = rows[:, L.P_MODEL].astype(int)
+    tid = usable[rng.integers(0, usable.size, n)].astype(np.uint8)
+    active = (rng.random(n) > 0.03).astype(np.uint8)
+    pm = models[tid] == L.MODEL_POINTMASS
+    x, y = np.float32(rng.uniform(-100, 100, n)), np.float32(rng.uniform(-100, 100, n))
+    h = np.float32(rng.uniform(0, 6.28, n))
+    v = np.float32(np.where(pm, rng.uniform(0.5, 1.4, n), rng.uniform(0.0, 9.0, n)))
+    vx, vy = np.float32(v * np.cos(h)), np.float32(v * np.sin(h))
+    a0, a1 = np.float32(rng.uniform(-2.0, 2.0, n)), np.float32(rng.uniform(-0.3, 0.3, n))
+    return dict(x=x, y=y, heading=h, speed=v, type_id=tid, active=active, vx=vx, vy=vy), (a0, a1)
+
+
+@pytest.mark.parametrize("path", ["restore", "auto_reset", "auto_reset_armed_first"])
+def test_four_per_lane_integrator_follows_the_ids_put_back_from_the_snapshot(path, oracle):
+    """t2d_integrate picks the wide kernel's instantiation from the set of types in use, and device-side writes of the ids --
+    t2d_restore, the auto-reset of a step -- put the SNAPSHOT's types back.  A pool snapshotted with kinematic bicycles and point
+    masses, then reset to point masses only, must step the bicycles it gets back as bicycles (not through the point-mass-only
+    instantiation): the wide integrate equals the one-per-lane fused step from the same state, bit for bit, and the oracle.
+    auto_reset: the unfused step (the integrator of grid-tier pools) with max_step 1, armed after the second reset or
+    before it."""
+    from tactics2d_amd import layout as L, scenarios as S
+    from tactics2d_amd.pool import ParticipantPool
+    rows, _ = S.full_type_table()
+    rows = rows[np.isin(rows[:, L.P_MODEL], (L.MODEL_KINEMATICS, L.MODEL_POINTMASS))]
+    models = rows[:, L.P_MODEL].astype(int)
+    n_env, A = 32768, 64
+    n = n_env * A
+    rng = np.random.default_rng(31)
+    first, (a0, a1) = _wide_inputs(rng, rows, np.arange(len(rows)), n)
+    second, _ = _wide_inputs(rng, rows, np.nonzero(models == L.MODEL_POINTMASS)[0], n)
+    kin = (models[first["type_id"]] == L.MODEL_KINEMATICS) & (first["active"] == 1)
+    assert kin.mean() > 0.3
+    fields = (L.F_X, L.F_Y, L.F_HEADING, L.F_SPEED, L.F_VX, L.F_VY, L.F_APPLIED0, L.F_APPLIED1)
+
+    pool = ParticipantPool(n_env, A)
+    try:
+        pool.set_param_table(rows)
+        pool.set_integrator_variant("exact")
+        pool.reset(**first)
+        ids0 = pool.download(L.F_IDS).copy()
+        pool.snapshot()
+        pool.set_actions(a0, a1)
+        if path == "auto_reset_armed_first":
+            pool.set_auto_reset(True)
+        pool.reset(**second)
+        if path == "restore":
+            pool.restore(done_only=False)
+            pool.integrate(100)
+        else:
+            pool.set_status_config(max_step=1)
+            pool.set_fused_step(False)
+            if path == "auto_reset":
+                pool.set_auto_reset(True)
+            pool.step(100)
+            pool.step(100)             # cnt_step 2 > max_step: every env ends and is put back to the snapshot
+            assert np.array_equal(pool.download(L.F_IDS), ids0)
+            assert np.array_equal(pool.download(L.F_X), first["x"])
+            pool.set_auto_reset(False)
+            pool.step(100)             # (ends every env again; without the auto-reset the step's state stays)
+        assert np.array_equal(pool.download(L.F_IDS), ids0)
+        wide = [pool.download(f).copy() for f in fields]
+    finally:
+        pool.close()
+    pool = ParticipantPool(n_env, A)
+    try:
+        pool.set_param_table(rows)
+        pool.set_integrator_variant("exact")
+        pool.reset(**first)
+        pool.set_actions(a0, a1)
+        pool.step(100)
+        narrow = [pool.download(f).copy() for f in fields]
+    finally:
+        pool.close()
+    on = first["active"] == 1
+    for f, w, nr in zip(fields, wide, narrow):
+        bad = w.view(np.uint32) != nr.view(np.uint32)
+        if f in (L.F_APPLIED0, L.F_APPLIED1):   # (an output of the stepped lanes: slots inactive now keep what earlier steps left)
+            bad &= on
+        assert not bad.any(), (path, f, int(bad.sum()), int((bad & kin).sum()))
+    # both sides could share one wrong dispatch: a sample against the oracle (deterministic trig = the exact variant)
+    k = np.sort(np.random.default_rng(5).choice(n, 20000, replace=False))
+    f = {key: val[k] for key, val in first.items()}
+    oracle.set_trig(1)
+    try:
+        o = oracle.integrate(rows, f["x"], f["y"], f["heading"], f["speed"], f["vx"], f["vy"], a0[k], a1[k], f["type_id"],
+                             f["active"], 100)
+    finally:
+        oracle.set_trig(0)
+    onk = f["active"] == 1
+    pmk = onk & (models[f["type_id"]] == L.MODEL_POINTMASS)
+    for c in range(4):
+        assert np.array_equal(np.float32(o[onk, c]), wide[c][k][onk]), (path, c)
+    for c in (4, 5):
+        assert np.array_equal(np.float32(o[pmk, c]), wide[c][k][pmk]), (path, c)
+    assert (kin[k] & onk).sum() > 5000
 
 
 @pytest.mark.parametrize("variant", ["fast", "exact"])
