@@ -38,6 +38,9 @@
  *   t2d_step              <- _ParkingScenarioManager.update + check_status  envs/parking.py:352-392
  *                            ParkingEnv.step terminated/truncated/reward    envs/parking.py:219-256,148-161
  *                            TimeExceed.update               traffic/event_detection/time_exceed.py:26-33
+ *   t2d_traj_* /          <- Trajectory.add_state / get_state / history_states  participant/trajectory/trajectory.py:115-188
+ *   t2d_verify_states        PhysicsModelBase.verify_states  physics/physics_model_base.py:53-73
+ *                            ParticipantBase._verify_trajectory  participant/element/participant_base.py:120-131
  *   t2d_step_host         <- ParkingEnv.step as its caller sees it: host action in, host 5-tuple out
  *                            envs/parking.py:219-256, _get_infos / _get_relative_pose :190-217
  *
@@ -72,7 +75,7 @@
 extern "C" {
 #endif
 
-#define T2D_ABI_VERSION 12
+#define T2D_ABI_VERSION 13
 
 /* ---- status codes --------------------------------------------------------------- */
 #define T2D_OK            0
@@ -539,6 +542,54 @@ int t2d_idm_actions(t2d_pool* pool, const int32_t* forced_leader_dev, void* hip_
  * Quirks kept: any unbounded range -> True; x / y are tested with strict inequalities against an unsorted range. */
 int t2d_verify_state(t2d_pool* pool, const float* x_dev, const float* y_dev, const float* heading_dev,
                      const float* speed_dev, int32_t interval_ms, uint8_t* valid_dev, void* hip_stream);
+
+/* Device-resident trajectories -- the reference's per-participant Trajectory (participant/trajectory/trajectory.py:12-188)
+ * for a whole pool, kept on the device, and PhysicsModelBase.verify_states (physics/physics_model_base.py:53-73; called by
+ * ParticipantBase._verify_trajectory participant_base.py:120-131) over it in one launch.
+ *
+ * A t2d_traj is bound to one pool: its N (= n_env * max_agents), its device, and -- read at t2d_verify_states time -- its
+ * participants' ids (type, model, active) and its parameter table.  It holds T2D_TRAJ_COLS fp32 columns (x, y, heading, speed,
+ * vx, vy: what the pool stores), each laid out [capacity][N]: slot s is row s of every column.  The library never grows or
+ * wraps a buffer: which frame lives in which slot, and growth (a bigger t2d_traj + t2d_traj_copy), are the caller's.
+ * Destroy a trajectory before its pool.
+ *
+ *   t2d_traj_record   slot <- the pool's current state: one stream-ordered launch, no host sync.  A record enqueued on the
+ *                     step's stream after t2d_step sees that step's state.  (The intermediate states of a t2d_step_n fragment are
+ *                     not recorded: record at fragment ends, or step one launch at a time.)
+ *   t2d_traj_write    slot <- cols_host, 6 x N fp32 (x, y, heading, speed, vx, vy), e.g. a host BatchedState; synchronous.
+ *   t2d_traj_read     cols_host (6 x N) <- slot; waits for the pool's work first (as t2d_download does).
+ *   t2d_traj_column   zero-copy device pointer of column `col` ([capacity][N] fp32), valid until t2d_traj_destroy.
+ *   t2d_traj_copy     slots [0, n_slots) of src -> dst (same N and device; capacities may differ), stream-ordered.
+ *   t2d_verify_states valid_dev[i] (uint8, N) = 1 exactly when the reference's verify_states returns True for participant i's
+ *                     trajectory of n_frames frames, frame k held in slot slot_host[k]: frame k >= 1 is checked against frame 0
+ *                     with interval interval_ms_host[k] (fp64 ms, dt = interval / 1000; entry 0 is unused).  The check is
+ *                     t2d_verify_state's, row by row (model ids 2 and 4: the point-mass acceleration test; single-track rows with
+ *                     all three range flags: the heading / speed / x / y box; True for interval 0).  Inactive participants and
+ *                     one-frame trajectories get 1.  One launch on hip_stream; the host arrays are read during the call.
+ *
+ * Reference quirks kept (the caller computes the intervals as the reference does):
+ *   - last_state is never advanced (physics_model_base.py:65-71): every frame is checked against the FIRST frame, not its
+ *     predecessor -- a trajectory the model itself stepped usually fails after frame 1, and a jump passes if it stays within
+ *     one interval's reach of frame 0;
+ *   - a stable-frequency trajectory's interval is 1000 / fps (a float: 33.333... ms at 30 fps), not the stamp difference; an
+ *     uneven one uses frame_k - frame_0;
+ *   - t2d_verify_state's own quirks: an unbounded range passes, x / y are strict inequalities against an unsorted range.
+ *
+ * Errors: T2D_ERR_INVALID for a null pointer, a slot at or past capacity, n_frames < 1, col outside [0, T2D_TRAJ_COLS),
+ * capacity < 1, or t2d_traj_copy between trajectories of another N / device or of more slots than either holds;
+ * T2D_ERR_STATE (t2d_traj_record, t2d_verify_states) for a pool without a parameter table or without a t2d_reset.  The
+ * message is the bound pool's t2d_last_error.                                                                            */
+#define T2D_TRAJ_COLS 6
+typedef struct t2d_traj t2d_traj;
+int t2d_traj_create(t2d_pool* pool, int32_t capacity, t2d_traj** out_traj);
+int t2d_traj_destroy(t2d_traj* traj);
+int t2d_traj_record(t2d_traj* traj, int32_t slot, void* hip_stream);
+int t2d_traj_write(t2d_traj* traj, int32_t slot, const float* cols_host);
+int t2d_traj_read(t2d_traj* traj, int32_t slot, float* cols_host);
+int t2d_traj_column(t2d_traj* traj, int32_t col, void** dev_ptr, size_t* nbytes);
+int t2d_traj_copy(t2d_traj* dst, const t2d_traj* src, int32_t n_slots, void* hip_stream);
+int t2d_verify_states(t2d_traj* traj, int32_t n_frames, const int32_t* slot_host, const double* interval_ms_host,
+                      uint8_t* valid_dev, void* hip_stream);
 
 /* Reset-time scene synthesis: ParkingLotGenerator.generate
  * (map/generator/generate_parking_lot.py:239-444) for n_env independent scenes, one lane per scene, on `device_id`.

@@ -2201,6 +2201,174 @@ int t2d_verify_state(t2d_pool* p, const float* x_dev, const float* y_dev, const 
     return T2D_OK;
 }
 
+// ---- device-resident trajectories (kernels: t2d_history.hip) ----------------------------------------------------------------
+struct t2d_traj {
+    t2d_pool* pool;
+    int device, N, capacity;
+    float* buf = nullptr;   // [T2D_TRAJ_COLS][capacity][N]
+    // the frame -> slot map and intervals of t2d_verify_states, staged through pinned host memory; `meta_done` follows the last
+    // launch that read them, so the next call does not overwrite them under a running kernel
+    int32_t meta_cap = 0;
+    void* meta_host = nullptr;
+    void* meta_dev = nullptr;
+    hipEvent_t meta_done = nullptr;
+    bool meta_pending = false;
+};
+
+namespace {
+size_t traj_meta_bytes(int n) { return (size_t)n * sizeof(double) + (size_t)n * sizeof(int32_t); }
+bool traj_slot_ok(const t2d_traj* t, int32_t slot) { return slot >= 0 && slot < t->capacity; }
+}  // namespace
+
+int t2d_traj_create(t2d_pool* p, int32_t capacity, t2d_traj** out) {
+    if (!p || !out) return p ? fail(p, T2D_ERR_INVALID, "t2d_traj_create: null output") : T2D_ERR_INVALID;
+    if (capacity < 1) return fail(p, T2D_ERR_INVALID, "t2d_traj_create: capacity must be >= 1");
+    T2D_HIP(p, hipSetDevice(p->device));
+    std::unique_ptr<t2d_traj> t(new (std::nothrow) t2d_traj);
+    if (!t) return fail(p, T2D_ERR_NOMEM, "t2d_traj_create: host allocation");
+    t->pool = p;
+    t->device = p->device;
+    t->N = p->v.N;
+    t->capacity = capacity;
+    const size_t bytes = (size_t)T2D_TRAJ_COLS * capacity * t->N * sizeof(float);
+    if (hipMalloc((void**)&t->buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(p, T2D_ERR_NOMEM, "t2d_traj_create: " + std::to_string(bytes) + " bytes of device memory");
+    }
+    if (hipEventCreateWithFlags(&t->meta_done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipFree(t->buf);
+        return fail(p, T2D_ERR_HIP, "t2d_traj_create: hipEventCreateWithFlags failed");
+    }
+    *out = t.release();
+    return T2D_OK;
+}
+
+int t2d_traj_destroy(t2d_traj* t) {
+    if (!t) return T2D_OK;
+    (void)hipSetDevice(t->device);
+    (void)quiesce(t->pool);   // records, copies and verify launches on the pool's streams
+    if (t->meta_pending) (void)hipEventSynchronize(t->meta_done);
+    if (t->buf) (void)hipFree(t->buf);
+    if (t->meta_dev) (void)hipFree(t->meta_dev);
+    if (t->meta_host) (void)hipHostFree(t->meta_host);
+    if (t->meta_done) (void)hipEventDestroy(t->meta_done);
+    delete t;
+    return T2D_OK;
+}
+
+int t2d_traj_record(t2d_traj* t, int32_t slot, void* hip_stream) {
+    if (!t) return T2D_ERR_INVALID;
+    t2d_pool* p = t->pool;
+    if (!traj_slot_ok(t, slot)) return fail(p, T2D_ERR_INVALID, "t2d_traj_record: slot " + std::to_string(slot) + " outside [0, " +
+                                                                   std::to_string(t->capacity) + ")");
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_traj_record");
+    T2D_HIP(p, hipSetDevice(t->device));
+    touch(p, (hipStream_t)hip_stream);
+    T2D_HIP(p, t2d::launch_traj_record(p->v, t->buf, t->capacity, slot, (hipStream_t)hip_stream));
+    return T2D_OK;
+}
+
+namespace {
+// the six rows of one slot <-> a host block of T2D_TRAJ_COLS x N floats (one 2-D copy), after the pool's work
+int traj_rows(t2d_traj* t, int32_t slot, float* host, bool to_device, const char* what) {
+    t2d_pool* p = t->pool;
+    if (!host) return fail(p, T2D_ERR_INVALID, std::string(what) + ": null host pointer");
+    if (!traj_slot_ok(t, slot)) return fail(p, T2D_ERR_INVALID, std::string(what) + ": slot " + std::to_string(slot) + " outside [0, " +
+                                                                   std::to_string(t->capacity) + ")");
+    T2D_HIP(p, hipSetDevice(t->device));
+    T2D_HIP(p, quiesce(p));
+    const size_t row = (size_t)t->N * sizeof(float), pitch = row * t->capacity;
+    float* dev = t->buf + (size_t)slot * t->N;
+    if (to_device) T2D_HIP(p, hipMemcpy2D(dev, pitch, host, row, row, T2D_TRAJ_COLS, hipMemcpyHostToDevice));
+    else T2D_HIP(p, hipMemcpy2D(host, row, dev, pitch, row, T2D_TRAJ_COLS, hipMemcpyDeviceToHost));
+    return T2D_OK;
+}
+}  // namespace
+
+int t2d_traj_write(t2d_traj* t, int32_t slot, const float* cols_host) {
+    if (!t) return T2D_ERR_INVALID;
+    return traj_rows(t, slot, const_cast<float*>(cols_host), true, "t2d_traj_write");
+}
+
+int t2d_traj_read(t2d_traj* t, int32_t slot, float* cols_host) {
+    if (!t) return T2D_ERR_INVALID;
+    return traj_rows(t, slot, cols_host, false, "t2d_traj_read");
+}
+
+int t2d_traj_column(t2d_traj* t, int32_t col, void** dev_ptr, size_t* nbytes) {
+    if (!t) return T2D_ERR_INVALID;
+    if (!dev_ptr || !nbytes) return fail(t->pool, T2D_ERR_INVALID, "t2d_traj_column: null output");
+    if (col < 0 || col >= T2D_TRAJ_COLS) return fail(t->pool, T2D_ERR_INVALID, "t2d_traj_column: column outside [0, T2D_TRAJ_COLS)");
+    const size_t n = (size_t)t->capacity * t->N;
+    *dev_ptr = t->buf + (size_t)col * n;
+    *nbytes = n * sizeof(float);
+    return T2D_OK;
+}
+
+int t2d_traj_copy(t2d_traj* dst, const t2d_traj* src, int32_t n_slots, void* hip_stream) {
+    if (!dst) return T2D_ERR_INVALID;
+    t2d_pool* p = dst->pool;
+    if (!src) return fail(p, T2D_ERR_INVALID, "t2d_traj_copy: null source");
+    if (src->N != dst->N || src->device != dst->device)
+        return fail(p, T2D_ERR_INVALID, "t2d_traj_copy: the trajectories differ in N or device");
+    if (n_slots < 0 || n_slots > src->capacity || n_slots > dst->capacity)
+        return fail(p, T2D_ERR_INVALID, "t2d_traj_copy: n_slots outside [0, min(capacities)]");
+    if (n_slots == 0 || src == dst) return T2D_OK;
+    T2D_HIP(p, hipSetDevice(dst->device));
+    touch(p, (hipStream_t)hip_stream);
+    if (src->pool != p) touch(src->pool, (hipStream_t)hip_stream);
+    const size_t row = (size_t)dst->N * sizeof(float);
+    T2D_HIP(p, hipMemcpy2DAsync(dst->buf, row * dst->capacity, src->buf, row * src->capacity, row * n_slots, T2D_TRAJ_COLS,
+                                hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    return T2D_OK;
+}
+
+int t2d_verify_states(t2d_traj* t, int32_t n_frames, const int32_t* slot_host, const double* interval_ms_host,
+                      uint8_t* valid_dev, void* hip_stream) {
+    if (!t) return T2D_ERR_INVALID;
+    t2d_pool* p = t->pool;
+    if (!slot_host || !interval_ms_host || !valid_dev) return fail(p, T2D_ERR_INVALID, "t2d_verify_states: null pointer");
+    if (n_frames < 1) return fail(p, T2D_ERR_INVALID, "t2d_verify_states: n_frames must be >= 1");
+    for (int k = 0; k < n_frames; ++k)
+        if (!traj_slot_ok(t, slot_host[k]))
+            return fail(p, T2D_ERR_INVALID, "t2d_verify_states: frame " + std::to_string(k) + " names slot " +
+                                                std::to_string(slot_host[k]) + ", outside [0, " + std::to_string(t->capacity) + ")");
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_verify_states");
+    int stable = 1;   // (bit equality: the ranges computed once are then those of every frame)
+    for (int k = 2; k < n_frames; ++k)
+        if (memcmp(&interval_ms_host[k], &interval_ms_host[1], sizeof(double)) != 0) stable = 0;
+    T2D_HIP(p, hipSetDevice(t->device));
+    if (t->meta_pending) {
+        T2D_HIP(p, hipEventSynchronize(t->meta_done));
+        t->meta_pending = false;
+    }
+    if (n_frames > t->meta_cap) {
+        int cap = std::max(64, t->meta_cap);
+        while (cap < n_frames) cap *= 2;
+        if (t->meta_dev) T2D_HIP(p, hipFree(t->meta_dev));
+        if (t->meta_host) T2D_HIP(p, hipHostFree(t->meta_host));
+        t->meta_dev = t->meta_host = nullptr;
+        t->meta_cap = 0;
+        T2D_HIP(p, hipMalloc(&t->meta_dev, traj_meta_bytes(cap)));
+        T2D_HIP(p, hipHostMalloc(&t->meta_host, traj_meta_bytes(cap), hipHostMallocDefault));
+        t->meta_cap = cap;
+    }
+    // [intervals: n doubles][slots: n int32] -- one copy
+    memcpy(t->meta_host, interval_ms_host, (size_t)n_frames * sizeof(double));
+    memcpy((char*)t->meta_host + (size_t)n_frames * sizeof(double), slot_host, (size_t)n_frames * sizeof(int32_t));
+    const hipStream_t s = (hipStream_t)hip_stream;
+    touch(p, s);
+    T2D_HIP(p, hipMemcpyAsync(t->meta_dev, t->meta_host, traj_meta_bytes(n_frames), hipMemcpyHostToDevice, s));
+    const double* iv_dev = (const double*)t->meta_dev;
+    const int32_t* slot_dev = (const int32_t*)((const char*)t->meta_dev + (size_t)n_frames * sizeof(double));
+    T2D_HIP(p, t2d::launch_verify_states(p->v, t->buf, t->capacity, slot_dev, iv_dev, n_frames, stable, valid_dev, s));
+    T2D_HIP(p, hipEventRecord(t->meta_done, s));
+    t->meta_pending = true;
+    return T2D_OK;
+}
+
 int t2d_set_outputs(t2d_pool* p, uint32_t mask) {
     if (!p) return T2D_ERR_INVALID;
     if (mask & ~T2D_OUT_ALL) return fail(p, T2D_ERR_INVALID, "unknown output bit");

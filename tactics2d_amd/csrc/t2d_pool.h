@@ -406,6 +406,11 @@ hipError_t launch_lidar(const PoolView& v, const LidarView& lv, float* out, hipS
 hipError_t launch_drift(const PoolView& v, int interval_ms, hipStream_t s);
 hipError_t launch_verify(const PoolView& v, const float* x, const float* y, const float* heading, const float* speed,
                          int interval_ms, uint8_t* valid, hipStream_t s);
+// device-resident trajectories (t2d_history.hip): slot `slot` of a [T2D_TRAJ_COLS][capacity][N] buffer <- the pool's state;
+// verify_states of the frames slot_dev[0..n_frames) against frame 0 (stable: every interval_dev[k >= 1] is the same value)
+hipError_t launch_traj_record(const PoolView& v, float* buf, int capacity, int slot, hipStream_t s);
+hipError_t launch_verify_states(const PoolView& v, const float* buf, int capacity, const int32_t* slot_dev,
+                                const double* interval_dev, int n_frames, int stable, uint8_t* valid, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

@@ -196,6 +196,29 @@ class _BatchedModel:
         pool.reset(last_state.x, last_state.y, last_state.heading, last_state.speed, np.zeros(n, np.uint8))
         return pool.verify_state(state.x, state.y, state.heading, state.speed, interval)
 
+    def verify_states(self, trajectory):
+        """Batched `verify_states(trajectory)` -> bool[n] (physics_model_base.py:53-73): every participant's history checked by
+        this model, frame k against frame 0 (the reference never advances last_state), in one launch.  trajectory: a
+        BatchedTrajectory (uploaded) or a DeviceTrajectory (copied device to device onto this model's pool)."""
+        from .history import BatchedTrajectory, DeviceTrajectory, verify_intervals
+        verify_intervals(trajectory)   # (the reference's TypeError / IndexError, before anything else)
+        if isinstance(trajectory, DeviceTrajectory):
+            n = trajectory.n
+        elif isinstance(trajectory, BatchedTrajectory):
+            n = len(trajectory.initial_state)
+        else:
+            raise ValueError("verify_states expects a BatchedTrajectory or a DeviceTrajectory")
+        pool = self._pool(n)
+        z = np.zeros(n, np.float32)
+        pool.reset(z, z, z, z, np.zeros(n, np.uint8))   # (every participant active, of this model's row)
+        if isinstance(trajectory, DeviceTrajectory) and trajectory.pool is pool:
+            return pool.verify_states(trajectory)
+        dev = trajectory.copy_to(pool) if isinstance(trajectory, DeviceTrajectory) else DeviceTrajectory.from_batched(pool, trajectory)
+        try:
+            return pool.verify_states(dev)
+        finally:
+            dev.close()
+
     def close(self):
         pool = getattr(self, "_cached_pool", None)
         if pool is not None:

@@ -103,6 +103,8 @@ class ParticipantPool:
     # ---------------------------------------------------------------- lifetime
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            for buf in list(self.__dict__.get("_traj_buffers", ())):   # (DeviceTrajectory buffers bound to this pool go first)
+                buf.close()
             self._lib.t2d_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -217,6 +219,35 @@ class ParticipantPool:
         for f, v in zip((L.F_ACT0, L.F_ACT1, L.F_APPLIED0, L.F_APPLIED1, L.F_FLAGS), saved):
             self.upload(f, v)
         return out
+
+    def verify_states(self, traj, out_ptr=None, stream=None):
+        """`ParticipantBase._verify_trajectory` (participant_base.py:120-131) for every participant at once: bool[N], participant
+        i checked under its own type row and model by `PhysicsModelBase.verify_states` (physics_model_base.py:53-73) -- every
+        frame against the FIRST one, with the reference's intervals (history.verify_intervals) -- in one launch.
+        traj: a DeviceTrajectory of this pool, or a BatchedTrajectory (uploaded into one for the call).
+        out_ptr: device memory of N bytes to write the verdicts to, asynchronously on `stream` (then returns None)."""
+        from .history import BatchedTrajectory, DeviceTrajectory, verify_intervals
+        if not isinstance(traj, BatchedTrajectory) and not (isinstance(traj, DeviceTrajectory) and traj.pool is self):
+            raise ValueError("verify_states: a DeviceTrajectory of this pool or a BatchedTrajectory")
+        intervals = verify_intervals(traj)   # (the reference's TypeError / IndexError)
+        if isinstance(traj, BatchedTrajectory):
+            dev = DeviceTrajectory.from_batched(self, traj)
+            try:
+                return self.verify_states(dev, out_ptr, stream)
+            finally:
+                dev.close()
+        slots = traj.slots()
+        iv = np.array([0.0] + [float(v) for v in intervals], np.float64)
+        buf = None
+        if out_ptr is None:
+            import torch
+            buf = torch.empty(self.n, dtype=torch.uint8, device=f"cuda:{self.device_id}")
+            out_ptr = buf.data_ptr()
+        self._ck(self._lib.t2d_verify_states(traj._buf._live(), len(slots), _p(slots), _p(iv), C.c_void_p(out_ptr), stream))
+        if buf is None:
+            return None
+        self.sync()
+        return buf.cpu().numpy().astype(bool)
 
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):
