@@ -34,6 +34,7 @@
  *   t2d_set_target_areas  <- Arrival.reset                traffic/event_detection/arrival.py:49-51
  *                            Arrival.update / NoAction.update (IoU)   arrival.py:32-47, no_action.py:32-53
  *   t2d_lidar_config/scan <- SingleLineLidar.__init__ / _scan_obstacles    sensor/lidar.py:33-57,128-221
+ *   t2d_lidar_scan_all    <- the same scan bound to every participant (bind_id)  sensor/lidar.py:29,98-221
  *   t2d_check_status      <- _ParkingScenarioManager.check_status           envs/parking.py:361-392
  *   t2d_step              <- _ParkingScenarioManager.update + check_status  envs/parking.py:352-392
  *                            ParkingEnv.step terminated/truncated/reward    envs/parking.py:219-256,148-161
@@ -491,10 +492,29 @@ int t2d_set_auto_reset(t2d_pool* pool, int32_t on);
  * the boxes of the other active participants.  beam_sin / beam_cos: host arrays [n_beams] with the sin /
  * cos of those angles (numpy), or NULL to have the library compute them with libm.
  * t2d_lidar_scan writes fp32 [n_env][n_beams] to out_dev (caller-owned device memory, e.g. the policy's
- * observation tensor) or, when NULL, to the pool's T2D_F_LIDAR buffer.  kernel_id 3 in t2d_profile_read. */
+ * observation tensor) or, when NULL, to the pool's T2D_F_LIDAR buffer.  kernel_id 3 in t2d_profile_read.
+ * The scan of every participant instead of the ego alone: t2d_lidar_scan_all below.                     */
 int t2d_lidar_config(t2d_pool* pool, int32_t n_beams, float max_range, int32_t include_participants,
                      const double* beam_sin, const double* beam_cos);
 int t2d_lidar_scan(t2d_pool* pool, float* out_dev, void* hip_stream);
+
+/* The same scan with EVERY participant of every env as the sensor, in one launch (SingleLineLidar bound to any
+ * participant: sensor/lidar.py:29 `bind_id`, :98-126 the rings in that participant's frame, :128-221 the scan).
+ * Row (e, j) is what t2d_lidar_scan gives for env e with status_config.ego_index = j, bit for bit: obstacles =
+ * the static polygons and, when include_participants, the boxes of the OTHER active participants (k != j).
+ * Rows of inactive participants and of participants whose x, y or heading is not finite are all +inf; a
+ * circle-shaped participant (pedestrian) is a sensor like any other and, as above, no obstacle.
+ * Uses the configuration of t2d_lidar_config (beams, range, include_participants, beam tables); ignores
+ * status_config.ego_index and never touches the status configuration.
+ * t2d_lidar_scan_all writes fp32 [n_env][max_agents][n_beams] to out_dev (caller-owned device memory, e.g. a
+ * multi-agent policy's observation tensor) or, when NULL, to a buffer of the pool's own, allocated on first
+ * use and again after t2d_lidar_config changed the beam count.  One launch, asynchronous on hip_stream, no
+ * host synchronisation: enqueued behind t2d_step / t2d_step_n on the same stream it sees that step's poses.
+ * T2D_ERR_STATE / T2D_ERR_GEOMETRY as t2d_lidar_scan.  kernel_id 8 in t2d_profile_read.
+ * t2d_lidar_all_buffer: pointer and size (n_env * max_agents * n_beams * 4 bytes) of the pool's own buffer;
+ * T2D_ERR_STATE before the first NULL-destination scan (and after a new beam count until the next one). */
+int t2d_lidar_scan_all(t2d_pool* pool, float* out_dev, void* hip_stream);
+int t2d_lidar_all_buffer(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
 
 /* On-device scripted agents: IDM car following (IDMController, controller/idm_controller.py:33-157).
  * ctrl_rows: host array [n_ctrl][row_stride >= T2D_IDM_COLS] of fp64 parameter sets -- the constructor
@@ -666,7 +686,8 @@ int t2d_set_integrator_variant(t2d_pool* pool, int32_t variant);
 int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel.
- * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration.                                   */
+ * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
+ * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all).                                     */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

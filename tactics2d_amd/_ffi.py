@@ -86,6 +86,8 @@ SYMBOLS = {
     "t2d_set_auto_reset": (C.c_int, [_vp, C.c_int32]),
     "t2d_lidar_config": (C.c_int, [_vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp]),
     "t2d_lidar_scan": (C.c_int, [_vp, _vp, _vp]),
+    "t2d_lidar_scan_all": (C.c_int, [_vp, _vp, _vp]),
+    "t2d_lidar_all_buffer": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "t2d_set_idm": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     "t2d_idm_actions": (C.c_int, [_vp, _vp, _vp]),
     "t2d_verify_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),

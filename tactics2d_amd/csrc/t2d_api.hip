@@ -235,6 +235,13 @@ int init_iou_state(t2d_pool* p, const uint8_t* env_mask, const float* hx, const 
     return T2D_OK;
 }
 
+// the LDS check of the lidar's edge list: what t2d_lidar_config / t2d_set_static_geometry refuse, both scans refuse too
+int lidar_fits(t2d_pool* p) {
+    if ((sizeof(double) * (p->lidar.max_slots <= 64 ? 8 : 4) + 8) * (size_t)p->lidar.max_slots + 16 * (size_t)p->lidar.n_beams + 2048 > 60 * 1024)
+        return fail(p, T2D_ERR_GEOMETRY, "too many obstacle edges per env for the lidar's LDS edge list");
+    return T2D_OK;
+}
+
 // plain per-env CSR of the static obstacle rings for the lidar kernel (from the host copy of the geometry)
 int rebuild_lidar_geo(t2d_pool* p) {
     if (!p->lidar_on) return T2D_OK;
@@ -296,9 +303,7 @@ int rebuild_lidar_geo(t2d_pool* p) {
     p->lidar.env_vert_off = p->d_lidar_env_off;
     p->lidar.xy = p->d_lidar_xy;
     p->lidar.max_slots = p->lidar.max_static_verts + (p->lidar.include_participants ? 4 * p->v.A : 0);
-    if ((sizeof(double) * (p->lidar.max_slots <= 64 ? 8 : 4) + 8) * (size_t)p->lidar.max_slots + 16 * (size_t)p->lidar.n_beams + 2048 > 60 * 1024)
-        return fail(p, T2D_ERR_GEOMETRY, "too many obstacle edges per env for the lidar's LDS edge list");
-    return T2D_OK;
+    return lidar_fits(p);
 }
 
 int record_event(t2d_pool* p, int kernel_id, hipStream_t s, bool begin) {
@@ -545,7 +550,7 @@ int t2d_destroy(t2d_pool* p) {
         if (p->field_ptr[f]) (void)hipFree(p->field_ptr[f]);
     void* bufs[] = {p->d_params, p->d_geo, p->d_boundary, p->d_boundary_valid, p->d_target_xy, p->d_target_c,
                     p->d_last_pose, p->d_max_iou, p->d_min_dist, p->d_snap_min_dist, p->d_last_valid,
-                    p->d_lidar_env_off, p->d_lidar_next, p->d_lidar_meta, p->d_lidar_xy, p->d_beam_sin, p->d_beam_cos,
+                    p->d_lidar_env_off, p->d_lidar_next, p->d_lidar_meta, p->d_lidar_xy, p->d_lidar_all, p->d_beam_sin, p->d_beam_cos,
                     p->d_snap[0], p->d_snap[1], p->d_snap[2],
                     p->d_snap[3], p->d_snap[4], p->d_snap[5], p->d_snap_ids, p->d_wgmap, p->d_idm_rows, p->d_idm_ctrl, p->d_snap_omega[0], p->d_snap_omega[1], p->d_time_penalty,
                     p->d_scene_arrays, p->d_lidar_cnt, p->d_chain, p->d_ckpt, p->d_scene_view,
@@ -2117,6 +2122,13 @@ int t2d_lidar_config(t2d_pool* p, int32_t n_beams, float max_range, int32_t incl
         T2D_HIP(p, hipMalloc(&p->field_ptr[T2D_F_LIDAR], lidar_bytes));
     }
     T2D_HIP(p, hipMemset(p->field_ptr[T2D_F_LIDAR], 0, lidar_bytes));
+    // the all-participants buffer follows the configuration: a new beam count drops it, the next NULL-destination
+    // t2d_lidar_scan_all allocates it again (a view taken with t2d_lidar_all_buffer stays valid while the size does)
+    if (p->d_lidar_all && p->lidar_all_bytes != lidar_bytes * (size_t)p->v.A) {
+        T2D_HIP(p, hipFree(p->d_lidar_all));
+        p->d_lidar_all = nullptr;
+        p->lidar_all_bytes = 0;
+    }
     p->lidar.beam_pre = p->d_beam_sin;
     p->lidar.max_range = (double)max_range;
     p->lidar.n_beams = n_beams;
@@ -2134,10 +2146,40 @@ int t2d_lidar_scan(t2d_pool* p, float* out_dev, void* hip_stream) {
     p->lidar.ego_index = p->status_cfg.ego_index;
     hipStream_t s = (hipStream_t)hip_stream;
     int rc;
+    if ((rc = lidar_fits(p))) return rc;   // (a configuration t2d_lidar_config refused: no launch)
     touch(p, s);
     if ((rc = record_event(p, 3, s, true))) return rc;
     T2D_HIP(p, t2d::launch_lidar(p->v, p->lidar, out_dev ? out_dev : (float*)p->field_ptr[T2D_F_LIDAR], s));
     return record_event(p, 3, s, false);
+}
+
+int t2d_lidar_scan_all(t2d_pool* p, float* out_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->lidar_on) return fail(p, T2D_ERR_STATE, "t2d_lidar_config must precede t2d_lidar_scan_all");
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_lidar_scan_all");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc;
+    if ((rc = lidar_fits(p))) return rc;
+    if (!out_dev && !p->d_lidar_all) {   // first use of the pool's own buffer (or the first after a new beam count)
+        const size_t bytes = (size_t)p->v.n_env * p->v.A * p->lidar.n_beams * sizeof(float);
+        T2D_HIP(p, hipSetDevice(p->device));
+        T2D_HIP(p, hipMalloc(&p->d_lidar_all, bytes));
+        p->lidar_all_bytes = bytes;
+    }
+    touch(p, s);
+    if ((rc = record_event(p, 8, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_lidar_all(p->v, p->lidar, out_dev ? out_dev : p->d_lidar_all, s));
+    return record_event(p, 8, s, false);
+}
+
+int t2d_lidar_all_buffer(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!dev_ptr || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->d_lidar_all)
+        return fail(p, T2D_ERR_STATE, "a t2d_lidar_scan_all with a NULL destination must precede t2d_lidar_all_buffer");
+    *dev_ptr = p->d_lidar_all;
+    *nbytes = p->lidar_all_bytes;
+    return T2D_OK;
 }
 
 int t2d_set_idm(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id) {

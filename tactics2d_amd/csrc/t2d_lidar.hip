@@ -17,6 +17,7 @@
 // arithmetic operation by operation (IEEE division, no contraction), so the output equals the oracle bit
 // for bit.  Output: fp32 [n_env][n_beams], +inf = no return: written once, coalesced -- the one genuinely
 // HBM-streaming product of the step (5.9 MB at 4096 envs x 360 beams).
+// The scan of EVERY participant of every env (t2d_lidar_scan_all) is lidar_all_kernel, further down in this file.
 #include "t2d_math.h"
 #include "t2d_pool.h"
 
@@ -465,7 +466,305 @@ __global__ __launch_bounds__(BLOCK, WAVES) void lidar_kernel(PoolView pv, LidarV
     T2D_LMARK(4);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The scan of EVERY participant of every env in one launch (t2d_lidar_scan_all): SingleLineLidar bound to any participant
+// (sensor/lidar.py:29, bind_id) instead of the ego alone.  Output fp32 [n_env][max_agents][n_beams].
+//
+// One workgroup per env, one sensor per wave at a time (sensor j of the env goes to wave j mod waves).
+// Phase 0, the whole workgroup: the env's obstacle list is built ONCE, in the WORLD frame, in LDS -- the static edges as they
+// lie in LidarView::xy and the four edges of every box participant (the oracle's pose_obb expressions, deterministic
+// sincos); a slot of a participant that is no obstacle (inactive, a circle, a non-finite pose) holds the far edge.
+// Per sensor, one wave: every lane takes a world edge, skips the sensor's own box and drops what lies out of reach in the
+// world frame (below); the slots of the rest are collected, and whenever 64 have come together (and at the end) each lane
+// transforms one into the sensor frame -- world vertices first, sensor transform second is the oracle's order, so the shared
+// list costs no bits -- and takes its beam span (edge_span, the ego kernel's test) on a full wave.  The
+// visible edges are compacted into a 64-slot list of the wave's own; a full list (or the end of the world list) is worked
+// off like a scatter chunk of the ego kernel: spans ORed into per-beam candidate masks, candidates queued and evaluated one
+// per lane with the same lidar_edge, minimum per beam by a 64-bit LDS atomic.  The set of evaluated (beam, edge) pairs
+// differs from the ego kernel's only by pairs neither can accept, and the minimum does not depend on the order: row
+// ego_index equals t2d_lidar_scan's output bit for bit.
+//
+// The reach test.  An edge can only produce an accepted intersection within R of the sensor (the beam's own bounds), so an
+// edge whose every point is further than R away can be dropped -- the reference's obstacle-level filter (lidar.py:118-124)
+// in a form that cannot change a result.  Tested before the transform, on the world coordinates in fp64: with M the edge's
+// mid point, h its half length and d = |M - sensor|, every point of the edge is at least d - h away, and d - h > Rm follows
+// from d^2 > 2 (Rm^2 + h^2) >= (Rm + h)^2 -- no square root, and loose by up to a factor sqrt 2, which edge_span's exact
+// point-segment test then takes care of (Rm = R * 1.0001 + 1 mm as there; rounding errors of the fp64 expressions are
+// twelve orders of magnitude below that slack for coordinates in metres).  The far edge (1e30) fails it, a NaN passes.
+constexpr int kAllMaxWaves = 4;    // waves per workgroup (launch_lidar_all takes fewer where the per-wave tables are large)
+constexpr int kAllList = 64;       // visible edges per wave and round: one bit each in a beam's candidate mask
+constexpr int kAllQueue = 256;     // (beam, edge) candidates per wave and compaction round
+constexpr size_t kAllLdsMax = 64 * 1024;
+
+T2D_DEV void lidar_wave_sync() {   // LDS traffic of one wave only: its LDS operations complete in order (see t2d_collide.hip)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// LDS of one wave: [kAllList][4] sensor-frame end points, [n_beams] minimum, [n_beams] candidate mask, [kAllList] spans, queue,
+// [128] slots of the world edges within reach
+__host__ __device__ inline size_t lidar_all_wave_bytes(int n_beams) {
+    return 32 * (size_t)kAllList + 16 * (size_t)n_beams + 4 * (size_t)kAllList + 4 * (size_t)kAllQueue + 4 * 128;
+}
+
+__global__ __launch_bounds__(64 * kAllMaxWaves, 4) void lidar_all_kernel(PoolView pv, LidarView lv, float* out) {
+    extern __shared__ __attribute__((aligned(16))) double s_all_raw[];
+    double4* const s_world = reinterpret_cast<double4*>(s_all_raw);   // [max_slots] x1, y1, x2, y2 in the world frame
+    __shared__ int s_all_qcount[kAllMaxWaves];
+    const int env = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), n_waves = (int)blockDim.x >> 6;
+    const int A = pv.A;
+    const int n_beams = lv.n_beams;
+    const size_t base = (size_t)env * A;
+    const double kFar = 1e30;
+    const bool parts = lv.include_participants != 0;
+
+    // ---- phase 0: the env's obstacle edges in the world frame ------------------------------------------------
+    int n_static = 0, v0 = 0;
+    if (lv.env_vert_cnt) {
+        v0 = env * lv.max_static_verts;
+        n_static = lv.env_vert_cnt[env];
+    } else if (lv.env_vert_off) {
+        v0 = lv.env_vert_off[env];
+        n_static = lv.env_vert_off[env + 1] - v0;
+    }
+    for (int q = tid; q < n_static; q += (int)blockDim.x) {
+        const float4 ed = reinterpret_cast<const float4*>(lv.xy)[v0 + q];
+        s_world[q] = make_double4((double)ed.x, (double)ed.y, (double)ed.z, (double)ed.w);
+    }
+    if (parts) {
+        for (int j = tid; j < A; j += (int)blockDim.x) {
+            const uint32_t ids = pv.ids[base + j];
+            const int type = (ids >> kIdsTypeShift) & 0xff;
+            const float hf = pv.heading[base + j], xf = pv.x[base + j], yf = pv.y[base + j];
+            const bool use = ((ids >> kIdsActiveShift) & 0xff) &&
+                             (int)pv.params[T2D_P_SHAPE * T2D_MAX_TYPES + type] == T2D_SHAPE_OBB &&
+                             __builtin_isfinite(hf) && __builtin_isfinite(xf) && __builtin_isfinite(yf);
+            double vx[4], vy[4];
+            if (use) {
+                const double L = pv.params[T2D_P_LENGTH * T2D_MAX_TYPES + type];
+                const double W = pv.params[T2D_P_WIDTH * T2D_MAX_TYPES + type];
+                double s2, c2;
+                sincos_det((double)hf, s2, c2);
+                const double cx = xf, cy = yf;
+                const double hl = 0.5 * L, hw = 0.5 * W;
+                const double lx[4] = {hl, hl, -hl, -hl};
+                const double ly[4] = {-hw, hw, hw, -hw};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {  // Vehicle.get_pose
+                    vx[k] = c2 * lx[k] - s2 * ly[k] + cx;
+                    vy[k] = s2 * lx[k] + c2 * ly[k] + cy;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                s_world[n_static + 4 * j + k] = use ? make_double4(vx[k], vy[k], vx[(k + 1) & 3], vy[(k + 1) & 3])
+                                                    : make_double4(kFar, kFar, kFar, kFar + 1.0);
+        }
+    }
+    const int n_slots = n_static + (parts ? 4 * A : 0);
+    __syncthreads();
+
+    // ---- the wave's own tables ---------------------------------------------------------------------------------
+    char* const w_raw = reinterpret_cast<char*>(s_all_raw) + 32 * (size_t)lv.max_slots + (size_t)wave * lidar_all_wave_bytes(n_beams);
+    double* const w_edge = reinterpret_cast<double*>(w_raw);                                        // [kAllList][4]
+    unsigned long long* const w_best = reinterpret_cast<unsigned long long*>(w_edge + 4 * kAllList);   // [n_beams]
+    unsigned long long* const w_mask = w_best + n_beams;                                            // [n_beams]
+    uint32_t* const w_span = reinterpret_cast<uint32_t*>(w_mask + n_beams);                         // [kAllList]
+    uint32_t* const queue = w_span + kAllList;                                                      // [kAllQueue]
+    uint32_t* const w_idx = queue + kAllQueue;                                                      // [2 * 64] world slots within reach
+    int* const qcount = &s_all_qcount[wave];
+    const double R = lv.max_range;
+    const double Rm = R * 1.0001 + 1e-3;
+    const double reach2 = 2.0 * (Rm * Rm);
+    const int n_iter = (n_beams + 63) >> 6;
+
+    // the queued (beam, edge) candidates, one exact solve per lane; leaves the queue empty
+    auto evaluate = [&] {
+        lidar_wave_sync();
+        const int total = *qcount;   // (may have run past the queue's end: what did not fit stayed with its lane)
+        const int n_round = total < kAllQueue ? total : kAllQueue;
+        for (int c = lane; c < n_round; c += 64) {
+            const uint32_t en = queue[c];
+            const int kb = (int)(en & 0xffffu), q = (int)(en >> 16);
+            const double2* bp = reinterpret_cast<const double2*>(lv.beam_pre + 6 * (size_t)kb);
+            const double2 ab = bp[0], bx = bp[1], by = bp[2];
+            const double* e = w_edge + 4 * q;
+            const double dd = lidar_edge(ab.x, ab.y, bx.x, bx.y, by.x, by.y, R, edge_pre(e[0], e[1], e[2], e[3]));
+            if (dd == dd) atomicMin(&w_best[kb], (unsigned long long)__double_as_longlong(dd));
+        }
+        lidar_wave_sync();
+        if (lane == 0) *qcount = 0;
+        lidar_wave_sync();
+    };
+    if (lane == 0) *qcount = 0;
+    lidar_wave_sync();
+
+    // the list of nc visible edges against the wave's beams: a scatter chunk of the ego kernel, one lane per edge
+    auto flush = [&](int nc) {
+        lidar_wave_sync();
+        {
+            constexpr int kLongSpan = 16;   // a longer span is swept by the whole wave, 64 consecutive beams per round
+            const uint32_t spw = lane < nc ? w_span[lane] : 0u;
+            const int first_k = (int)(spw & 0xfffu), len = (int)((spw >> 12) & 0x1fffu) - 1;
+            const int last = len < n_beams ? len : n_beams - 1;   // len = -1: nothing
+            const bool is_long = last >= kLongSpan;
+            if (!is_long) {
+                for (int i = 0; i <= last; ++i) {
+                    int kb = first_k + i;
+                    kb -= kb >= n_beams ? n_beams : 0;
+                    atomicOr(&w_mask[kb], 1ull << lane);
+                }
+            }
+            unsigned long long todo = __ballot(is_long);
+            while (todo) {
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const int first = __builtin_amdgcn_readlane(first_k, src), n_last = __builtin_amdgcn_readlane(last, src);
+                for (int i = lane; i <= n_last; i += 64) {
+                    int kb = first + i;
+                    kb -= kb >= n_beams ? n_beams : 0;
+                    atomicOr(&w_mask[kb], 1ull << src);
+                }
+            }
+        }
+        lidar_wave_sync();
+        // the candidates of ALL the wave's beams go through one queue: a beam's lane appends its candidates behind those of
+        // the beams before it, and the queue is evaluated when it is full and once at the end -- dense rounds of 64 exact
+        // solves, and no synchronisation per 64 beams (the ego kernel queues per 64 beams: its two waves share the masks)
+        for (int it = 0; it < n_iter; ++it) {
+            const int k = lane + (it << 6);
+            unsigned long long m = 0ull;
+            if (k < n_beams) {
+                m = w_mask[k];
+                if (m) w_mask[k] = 0ull;   // (the next list starts from empty masks)
+            }
+            for (;;) {
+                const int cnt = __popcll(m);
+                if (__ballot(cnt > 0) == 0ull) break;
+                const int off = cnt > 0 ? atomicAdd(qcount, cnt) : kAllQueue;
+                const int room = kAllQueue - off;
+                const int n_emit = room <= 0 ? 0 : (cnt < room ? cnt : room);
+                for (int e = 0; e < n_emit; ++e) {
+                    const int q = __ffsll((long long)m) - 1;
+                    m &= m - 1ull;
+                    queue[off + e] = (uint32_t)k | ((uint32_t)q << 16);
+                }
+                if (__ballot(cnt > n_emit) == 0ull) break;   // everything is queued
+                evaluate();                                  // the queue is full: work it off, then the lanes' remainders
+            }
+        }
+        evaluate();
+    };
+
+    for (int j = wave; j < A; j += n_waves) {   // (wave-uniform throughout)
+        const size_t is = base + j;
+        float* const o = out + is * (size_t)n_beams;
+        // (a sensor that is inactive or whose pose is not finite scans nothing -- every beam +inf --: the oracle's rule)
+        const float hf = pv.heading[is], xf = pv.x[is], yf = pv.y[is];
+        const bool on = ((pv.ids[is] >> kIdsActiveShift) & 0xff) != 0 && __builtin_isfinite(hf) && __builtin_isfinite(xf) &&
+                        __builtin_isfinite(yf);
+        if (!on || n_slots == 0) {
+            for (int k = lane; k < n_beams; k += 64) o[k] = __builtin_inff();
+            continue;
+        }
+        double sn, cs;
+        sincos_det((double)hf, sn, cs);
+        const double px = xf, py = yf;
+        const double x_off = -px * cs - py * sn;   // lidar.py:112-113
+        const double y_off = px * sn - py * cs;
+        for (int k = lane; k < n_beams; k += 64) {
+            w_best[k] = 0x7ff0000000000000ull;
+            w_mask[k] = 0ull;
+        }
+        const int own = parts ? n_static + 4 * j : -8;   // the sensor's own box: slots own .. own + 3
+        int nc = 0;
+        // n edges within reach (their slots in w_idx[0 .. n)), one per lane: sensor frame, beam span, the visible ones appended
+        // to the wave's list
+        auto span_pass = [&](int n) {
+            lidar_wave_sync();
+            bool vis = false;
+            double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0;
+            uint32_t spw = 0u;
+            if (lane < n) {
+                const double4 w = s_world[w_idx[lane]];
+                x1 = cs * w.x + sn * w.y + x_off;
+                y1 = -sn * w.x + cs * w.y + y_off;
+                x2 = cs * w.z + sn * w.w + x_off;
+                y2 = -sn * w.z + cs * w.w + y_off;
+                const int2 sp = edge_span(x1, y1, x2, y2, R, n_beams);
+                vis = sp.y >= 0;
+                spw = pack_span(sp);
+            }
+            const unsigned long long seen = __ballot(vis);
+            const int n_seen = __popcll(seen);
+            if (n_seen == 0) return;
+            if (nc + n_seen > kAllList) {
+                flush(nc);
+                nc = 0;
+            }
+            if (vis) {
+                const int slot = nc + __popcll(seen & ((1ull << lane) - 1ull));
+                double* e = w_edge + 4 * slot;
+                e[0] = x1; e[1] = y1; e[2] = x2; e[3] = y2;
+                w_span[slot] = spw;
+            }
+            nc += n_seen;
+        };
+        // the reach test over the whole world list, 64 edges per round; the survivors' slots are collected so that the
+        // transform + span test above runs on full waves (most of a 64-participant env is out of any one sensor's reach)
+        int np = 0;
+        for (int q0 = 0; q0 < n_slots; q0 += 64) {
+            const int q = q0 + lane;
+            bool near = false;
+            if (q < n_slots && (unsigned)(q - own) >= 4u) {
+                const double4 w = s_world[q];
+                const double mx = 0.5 * (w.x + w.z) - px, my = 0.5 * (w.y + w.w) - py;
+                const double hx = 0.5 * (w.z - w.x), hy = 0.5 * (w.w - w.y);
+                near = !(mx * mx + my * my > reach2 + 2.0 * (hx * hx + hy * hy));
+            }
+            const unsigned long long hit = __ballot(near);
+            if (hit == 0ull) continue;
+            if (near) w_idx[np + __popcll(hit & ((1ull << lane) - 1ull))] = (uint32_t)q;   // (np < 64: below 128 entries)
+            np += __popcll(hit);
+            if (np >= 64) {
+                span_pass(64);
+                np -= 64;
+                uint32_t keep = 0u;
+                if (lane < np) keep = w_idx[64 + lane];
+                lidar_wave_sync();
+                if (lane < np) w_idx[lane] = keep;
+            }
+        }
+        if (np > 0) span_pass(np);
+        if (nc > 0) flush(nc);
+        lidar_wave_sync();
+        for (int k = lane; k < n_beams; k += 64) {   // the wave writes the sensor's whole row, 256 B per instruction
+            double best = __builtin_sqrt(__longlong_as_double((long long)w_best[k]));   // min of sqrt = sqrt of min, bit for bit
+            best = best < 0.0 ? 0.0 : (best > R ? R : best);   // np.clip(0, R)
+            o[k] = best == R ? __builtin_inff() : (float)best;
+        }
+    }
+}
+
 }  // namespace
+
+// LDS of the all-participants scan with `waves` waves per workgroup: the world-frame edge list + the waves' own tables
+static size_t lidar_all_lds(const LidarView& lv, int waves) {
+    return 32 * (size_t)lv.max_slots + (size_t)waves * lidar_all_wave_bytes(lv.n_beams);
+}
+
+hipError_t launch_lidar_all(const PoolView& v, const LidarView& lv, float* out, hipStream_t s) {
+    // as many waves per workgroup (sensors scanned side by side over one shared edge list) as the LDS of a workgroup holds;
+    // one wave always fits for whatever configuration the LDS check of t2d_lidar_config lets through
+    int waves = kAllMaxWaves;
+    while (waves > 1 && (waves > v.A || lidar_all_lds(lv, waves) + 64 > kAllLdsMax)) waves >>= 1;
+    if (lidar_all_lds(lv, waves) + 64 > kAllLdsMax) return hipErrorInvalidValue;   // (never a truncated scan)
+    hipLaunchKernelGGL(lidar_all_kernel, dim3(v.n_env), dim3(64 * waves), lidar_all_lds(lv, waves), s, v, lv, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_lidar(const PoolView& v, const LidarView& lv_in, float* out, hipStream_t s) {
     LidarView lv = lv_in;

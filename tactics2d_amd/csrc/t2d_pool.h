@@ -301,6 +301,8 @@ struct t2d_pool {
     int32_t *d_lidar_env_off = nullptr, *d_lidar_next = nullptr;
     uint8_t* d_lidar_meta = nullptr;
     float* d_lidar_xy = nullptr;
+    float* d_lidar_all = nullptr;    // [n_env][max_agents][n_beams]: the pool's own destination of t2d_lidar_scan_all (first use)
+    size_t lidar_all_bytes = 0;
     double *d_beam_sin = nullptr, *d_beam_cos = nullptr;
     double* d_time_penalty = nullptr;
     bool has_drift = false;   // a T2D_MODEL_DRIFT row is in the parameter table
@@ -403,6 +405,7 @@ hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, in
 hipError_t launch_ego_step(const PoolView& v, const t2d_status_config& cfg, int interval_ms, int variant, hipStream_t s);
 hipError_t step_occupancy(const PoolView& v, int* blocks_per_cu, size_t* lds_bytes);
 hipError_t launch_lidar(const PoolView& v, const LidarView& lv, float* out, hipStream_t s);
+hipError_t launch_lidar_all(const PoolView& v, const LidarView& lv, float* out, hipStream_t s);
 hipError_t launch_drift(const PoolView& v, int interval_ms, hipStream_t s);
 hipError_t launch_verify(const PoolView& v, const float* x, const float* y, const float* heading, const float* speed,
                          int interval_ms, uint8_t* valid, hipStream_t s);

@@ -184,6 +184,27 @@ class ParticipantPool:
     def lidar_scan(self, out_ptr=None, stream=None):
         self._ck(self._lib.t2d_lidar_scan(self._h, out_ptr, stream))
 
+    def lidar_scan_all(self, out_ptr=None, stream=None):
+        """The scan of lidar_config with EVERY participant of every env as the sensor, in one launch: float32
+        [n_env, max_agents, n_beams] (+inf = no return; rows of inactive participants are all +inf) written to the device
+        memory at out_ptr, or -- out_ptr None -- to a buffer of the pool's own (lidar_all(), lidar_all_buffer()).
+        Asynchronous on `stream`; status_config.ego_index plays no part."""
+        self._ck(self._lib.t2d_lidar_scan_all(self._h, out_ptr, stream))
+
+    def lidar_all_buffer(self):
+        """(device pointer, bytes) of the pool's own all-participants scan buffer (after a lidar_scan_all() into it)."""
+        ptr, nb = C.c_void_p(), C.c_size_t()
+        self._ck(self._lib.t2d_lidar_all_buffer(self._h, C.byref(ptr), C.byref(nb)))
+        return ptr.value, nb.value
+
+    def lidar_all(self):
+        """The last lidar_scan_all() into the pool's own buffer as numpy [n_env, max_agents, n_beams], after the pool's work."""
+        import torch
+        ptr, nb = self.lidar_all_buffer()
+        view = _DevArray(ptr, (self.n_env, self.max_agents, nb // (4 * self.n)), "<f4", self)
+        self.sync()
+        return torch.as_tensor(view, device=f"cuda:{self.device_id}").cpu().numpy()
+
     def set_idm(self, ctrl_rows, ctrl_id):
         """Install IDM controllers: ctrl_rows [n_ctrl, 8] (layout.IDM_*), ctrl_id [n] uint8 (IDM_NONE =
         action supplied by the caller).  ctrl_rows=None uninstalls."""

@@ -267,5 +267,23 @@ class BatchedScenarioManager:
             cols[5] = np.where(derived, (v * np.sin(h)).astype(np.float32), cols[5])
         return np.stack(cols, 1)
 
+    def get_lidar_observation(self, out=None, stream=None):
+        """Lidar observation of EVERY participant of every scene (SingleLineLidar bound to each of them, sensor/lidar.py:29;
+        after pool.lidar_config): float32 [n_env, max_agents, n_beams], +inf = no return, one launch.
+        out: a contiguous float32 CUDA tensor of that shape -- the scan is written straight into it, asynchronously on
+        `stream` (a torch stream; default the tensor's device's current stream), and `out` is returned; None: a numpy array."""
+        pool = self.pool
+        if out is None:
+            pool.lidar_scan_all(None, None if stream is None else stream.cuda_stream)
+            return pool.lidar_all()
+        import torch
+        shape = (self.n_env, self.max_agents, pool.n_beams)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or \
+                not out.is_contiguous() or out.device.index != pool.device_id:
+            raise ValueError(f"out must be a contiguous float32 tensor {list(shape)} on cuda:{pool.device_id}")
+        st = stream if stream is not None else torch.cuda.current_stream(out.device)
+        pool.lidar_scan_all(out.data_ptr(), st.cuda_stream)
+        return out
+
     def close(self):
         self.pool.close()
