@@ -97,6 +97,10 @@ extern "C" {
                                        * T2D_MODEL_DRIFT (one launch ahead of the step launch; such pools are not chained) */
 #define T2D_MODEL_DRIFT      3   /* SingleTrackDrift (Pacejka tyres, default Tire constants); extra state
                                   * T2D_F_OMEGA_F / T2D_F_OMEGA_R; integrated by its own kernel */
+#define T2D_MODEL_REPLAY     5   /* no physics: the state at env time t is row t of a recorded trajectory (t2d_replay_bind);
+                                  * the row carries shape, length and width only (the participant takes part in events, lidar
+                                  * scans and leader searches); range, mass and sub-step columns are ignored.  Written by a
+                                  * launch of its own ahead of the step launch, like T2D_MODEL_DRIFT (such pools are not chained) */
 
 /* ---- shape kinds (column T2D_P_SHAPE) ---------------------------------------------- */
 #define T2D_SHAPE_OBB    0   /* Vehicle / Cyclist / Other: length x width box             */
@@ -610,6 +614,40 @@ int t2d_traj_column(t2d_traj* traj, int32_t col, void** dev_ptr, size_t* nbytes)
 int t2d_traj_copy(t2d_traj* dst, const t2d_traj* src, int32_t n_slots, void* hip_stream);
 int t2d_verify_states(t2d_traj* traj, int32_t n_frames, const int32_t* slot_host, const double* interval_ms_host,
                       uint8_t* valid_dev, void* hip_stream);
+
+/* Replayed participants -- ParticipantBase.is_active / get_state(frame) (participant/element/participant_base.py:166-203) and
+ * ScenarioManager.get_active_participants(frame) (traffic/scenario_manager.py:83-94) inside the device step: a participant
+ * whose parameter row has model T2D_MODEL_REPLAY takes its state from a recorded trajectory instead of a physics model.
+ *
+ * Source: a t2d_traj whose slot k holds the states of time stamp t0_ms + k * period_ms, k in [0, n_slots).  It may belong to
+ * another pool of the same max_agents and device (a library pool that is never stepped) with n_src_env envs.  Source
+ * participant j is present in slots [first_slot[j], last_slot[j]] (first > last: never).
+ * Binding: env e of `pool` shows source env src_env[e] (NULL: e itself, needs n_src_env == n_env) at stamp
+ * T2D_F_FRAME_MS[e] + offset_ms[e] (NULL: 0); agent a of the env is agent a of the source env.
+ *
+ * A step to interval i (t2d_integrate, t2d_step, every step of t2d_step_n and t2d_step_host) runs ONE launch ahead of the step
+ * launch, after the IDM controllers and the drift side kernel: for every participant whose type row has model 5, with
+ * F = frame_ms[e] + i + offset_ms[e] and k = (F - t0_ms) / period_ms: where first_slot[j] <= k <= last_slot[j] and k < n_slots
+ * the six state columns become slot k of the source, bit for bit, and the active byte of T2D_F_IDS becomes 1 (the model
+ * byte 5); elsewhere the active byte becomes 0 and the state is left as it is.  The events, the lidar and the leader
+ * search of that step see the new state.  There is no interpolation: the host refuses (T2D_ERR_INVALID, nothing stepped)
+ * an interval, an offset or a t0_ms that is not a multiple of period_ms.  t2d_collide and t2d_check_status do not advance
+ * it.  t2d_step_form reports T2D_FORM_UNFUSED for a pool with a model-5 row; a pool without one takes the launches it took.
+ *
+ *   t2d_replay_bind   all host arrays are read during the call ([n_env]: src_env, offset_ms; [n_src_env * max_agents]:
+ *                     first_slot, last_slot, NULL = 0 .. n_slots - 1).  src == NULL unbinds.  A new binding replaces the old.
+ *   t2d_replay_apply  the same write for the envs' CURRENT stamp (F = frame_ms[e] + offset_ms[e]), advancing nothing: after
+ *                     t2d_reset and before t2d_snapshot it puts the replayed participants where the recording has them at
+ *                     episode start (an auto-reset then restores that state and the ids with the snapshot).
+ *
+ * Errors: T2D_ERR_INVALID for a source of another max_agents or device, src_env outside [0, n_src_env), NULL src_env with
+ * n_src_env != n_env, n_slots outside [1, capacity], period_ms < 1, t0_ms or an offset off the grid, a window slot outside
+ * [0, n_slots) (first > last is legal), and -- at step time -- an interval off the grid; T2D_ERR_STATE for stepping (or
+ * t2d_replay_apply on) a pool whose table holds a model-5 row without a binding, and for t2d_traj_destroy of a trajectory
+ * that is still bound (unbind, or destroy the stepped pool, first).  A failed t2d_replay_bind leaves the previous binding. */
+int t2d_replay_bind(t2d_pool* pool, const t2d_traj* src, int32_t n_slots, int32_t t0_ms, int32_t period_ms,
+                    const int32_t* src_env, const int32_t* offset_ms, const int32_t* first_slot, const int32_t* last_slot);
+int t2d_replay_apply(t2d_pool* pool, void* hip_stream);
 
 /* Reset-time scene synthesis: ParkingLotGenerator.generate
  * (map/generator/generate_parking_lot.py:239-444) for n_env independent scenes, one lane per scene, on `device_id`.

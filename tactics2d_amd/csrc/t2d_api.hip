@@ -542,10 +542,13 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
     return T2D_OK;
 }
 
+static void replay_release(t2d_pool* p);   // (drops a replay binding: defined with t2d_replay_bind)
+
 int t2d_destroy(t2d_pool* p) {
     if (!p) return T2D_OK;
     (void)hipSetDevice(p->device);
     (void)quiesce(p);  // nothing of this pool may still be running (incl. a scene refill on its own stream)
+    replay_release(p);
     for (int f = 0; f < T2D_F_COUNT; ++f)
         if (p->field_ptr[f]) (void)hipFree(p->field_ptr[f]);
     void* bufs[] = {p->d_params, p->d_geo, p->d_boundary, p->d_boundary_valid, p->d_target_xy, p->d_target_c,
@@ -583,11 +586,14 @@ int t2d_set_param_table(t2d_pool* p, const double* rows, int32_t n_types, int32_
     std::vector<double> t(T2D_PARAM_COLS * T2D_MAX_TYPES, 0.0);
     double dmax = 0.0;
     bool has_drift = false;
+    uint32_t replay_types = 0u;
     for (int ty = 0; ty < n_types; ++ty) {
         const double* r = rows + (size_t)ty * row_stride;
         const int model = (int)r[T2D_P_MODEL];
-        if (model < 0 || model > T2D_MODEL_POINTMASS_EULER)
+        if (model < 0 || model > T2D_MODEL_REPLAY)
             return fail(p, T2D_ERR_INVALID, "row " + std::to_string(ty) + ": unknown model id");
+        const bool replayed = model == T2D_MODEL_REPLAY;   // (shape, length and width only: no range, mass or sub-step column is read)
+        if (replayed) replay_types |= 1u << ty;
         if (model == T2D_MODEL_POINTMASS_EULER) has_drift = true;   // (integrated by the side kernel, like the drift model)
         if (model == T2D_MODEL_DRIFT) {
             has_drift = true;
@@ -597,8 +603,8 @@ int t2d_set_param_table(t2d_pool* p, const double* rows, int32_t n_types, int32_
                                                     ": SingleTrackDrift needs mass, I_z, radius, I_yw > 0 and lf != 0");
         }
         const int dt = (int)r[T2D_P_DELTA_T_MS];
-        if (dt < 1) return fail(p, T2D_ERR_INVALID, "row " + std::to_string(ty) + ": delta_t must be >= 1 ms");
-        if (model != T2D_MODEL_POINTMASS && model != T2D_MODEL_POINTMASS_EULER && !(r[T2D_P_WB] != 0.0))
+        if (dt < 1 && !replayed) return fail(p, T2D_ERR_INVALID, "row " + std::to_string(ty) + ": delta_t must be >= 1 ms");
+        if (model != T2D_MODEL_POINTMASS && model != T2D_MODEL_POINTMASS_EULER && !replayed && !(r[T2D_P_WB] != 0.0))
             return fail(p, T2D_ERR_INVALID, "row " + std::to_string(ty) + ": zero wheel base");
         for (int c = 0; c < T2D_PARAM_COLS; ++c) {
             p->host_params[ty][c] = r[c];
@@ -607,6 +613,8 @@ int t2d_set_param_table(t2d_pool* p, const double* rows, int32_t n_types, int32_
         const double L = r[T2D_P_LENGTH], W = r[T2D_P_WIDTH];
         const double br = (int)r[T2D_P_SHAPE] == T2D_SHAPE_CIRCLE ? 0.5 * W : 0.5 * sqrt(L * L + W * W);
         t[(size_t)T2D_P_RESERVED0 * T2D_MAX_TYPES + ty] = br;  // bounding radius for the reject test
+        // (a replayed row's delta_t is never used, but the derive launch divides by every row's: keep the device's copy >= 1)
+        if (replayed && dt < 1) t[(size_t)T2D_P_DELTA_T_MS * T2D_MAX_TYPES + ty] = 1.0;
         if (model != T2D_MODEL_DRIFT) {   // the two derived columns (include/t2d.h): the sub-step in seconds now, its counts per launch interval
             t[(size_t)T2D_P_DT_S * T2D_MAX_TYPES + ty] = (double)dt / 1000;
             t[(size_t)T2D_P_SUBSTEPS * T2D_MAX_TYPES + ty] = 0.0;
@@ -615,6 +623,7 @@ int t2d_set_param_table(t2d_pool* p, const double* rows, int32_t n_types, int32_
     }
     p->v.n_types = n_types;
     p->has_drift = has_drift;
+    p->replay_types = replay_types;
     p->all_boxes = true;
     for (int ty = 0; ty < n_types; ++ty)
         if ((int)p->host_params[ty][T2D_P_SHAPE] != T2D_SHAPE_OBB) p->all_boxes = false;
@@ -989,6 +998,23 @@ static int prepare_interval(t2d_pool* p, int interval_ms, hipStream_t s) {
     return T2D_OK;
 }
 
+// Replayed participants (T2D_MODEL_REPLAY rows): pools that hold one keep helper launches around the step, as pools with a drift
+// row do -- no single-ego kernel, no chained form, controllers in a launch of their own
+static bool side_models(const t2d_pool* p) { return p->has_drift || p->replay_types != 0u; }
+
+// what must hold before a stepping call enqueues anything for a pool with replayed participants
+static int replay_check(t2d_pool* p, int interval_ms) {
+    if (!p->replay_types) return T2D_OK;
+    if (!p->replay_src)
+        return fail(p, T2D_ERR_STATE, "the parameter table holds a T2D_MODEL_REPLAY row: t2d_replay_bind must precede the step");
+    if (interval_ms % p->replay.period_ms != 0)
+        return fail(p, T2D_ERR_INVALID, "interval_ms " + std::to_string(interval_ms) + " is not a multiple of the replay source's period (" +
+                                            std::to_string(p->replay.period_ms) + " ms): there is no state between two stamps");
+    return T2D_OK;
+}
+
+static int replay_impl(t2d_pool* p, int step_ms, hipStream_t s);   // (defined with t2d_replay_bind)
+
 int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
     if (!p->have_params || !p->have_reset)
@@ -996,10 +1022,12 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if (interval_ms <= 0) return fail(p, T2D_ERR_INVALID, "interval_ms must be positive");
     hipStream_t s = (hipStream_t)hip_stream;
     int rc;
+    if ((rc = replay_check(p, interval_ms))) return rc;
     touch(p, s);
     if ((rc = prepare_interval(p, interval_ms, s))) return rc;
     if (p->idm_on && (rc = idm_impl(p, s))) return rc;
     if (p->has_drift && (rc = drift_impl(p, interval_ms, s))) return rc;
+    if (p->replay_types && (rc = replay_impl(p, interval_ms, s))) return rc;
     if ((rc = record_event(p, 0, s, true))) return rc;
     // (four participants per lane pay where the model is cheap enough for the kernel to be memory-bound: measured at 4 M
     // participants 72.4 -> 63.5 us for point masses, 74.6 -> 73.7 for the kinematic bicycle, 167.7 -> 170.3 for the dynamics
@@ -1008,8 +1036,10 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     for (int t = 0; t < p->v.n_types; ++t)   // (of the types some active participant HAS: t2d_reset keeps the set)
         wide = wide && !((p->types_used >> t & 1u) && (int)p->host_params[t][T2D_P_MODEL] == T2D_MODEL_DYNAMICS);
     int only_model = -1;   // the one model every active participant has, if there is one: an instantiation that carries it alone
+    // (replayed participants become active whenever their recording says so, not at t2d_reset: their rows always count)
+    const uint32_t used = p->types_used | p->replay_types;
     for (int t = 0; t < p->v.n_types; ++t)
-        if (p->types_used >> t & 1u) {
+        if (used >> t & 1u) {
             const int m = (int)p->host_params[t][T2D_P_MODEL];
             only_model = only_model == -1 || only_model == m ? m : -2;
         }
@@ -1025,7 +1055,7 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
 static bool idm_in_step(t2d_pool* p) {
     // (not pools with SingleTrackDrift participants: drift_kernel runs between the controllers and the step launch and reads
     // the accelerations the controllers wrote -- t2d_step's order is IDM, drift, step -- so there idm_kernel stays a launch)
-    return p->idm_on && p->chain_steps && p->fused_step && !p->grid_tier && !p->has_drift && p->v.A >= 2 && p->v.A <= 64 &&
+    return p->idm_on && p->chain_steps && p->fused_step && !p->grid_tier && !side_models(p) && p->v.A >= 2 && p->v.A <= 64 &&
            !(p->status_cfg.check_no_action || p->status_cfg.check_arrival);
 }
 static void fill_idm(t2d::PoolView& v, t2d_pool* p) {
@@ -1065,7 +1095,7 @@ static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStrea
         if (fuse_variant >= 0) return fail(p, T2D_ERR_STATE, "internal: a grid-tier pool took the fused step");
         T2D_HIP(p, t2d::launch_map_events(p->v, p->mapgrid, p->d_grid_seg, p->d_map_flags, s));
     }
-    if (fuse_variant >= 0 && p->ego_kernel && p->v.A == 1 && p->all_boxes && !p->has_drift && !p->hgeo[1].present) {
+    if (fuse_variant >= 0 && p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present) {
         t2d::PoolView v = p->v;
         // staged scene regeneration: the step's own epilogue moves finished envs into their next lot (no launch behind it)
         if (with_status && p->scene_regen && p->scene.ring > 0 && p->d_scene_view) {
@@ -1165,11 +1195,13 @@ int t2d_step(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
         return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_step");
     if (interval_ms <= 0) return fail(p, T2D_ERR_INVALID, "interval_ms must be positive");
     int rc;
+    if ((rc = replay_check(p, interval_ms))) return rc;
     if ((rc = prepare_interval(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     if ((rc = claim_record_slot(p, (hipStream_t)hip_stream))) return rc;
     // (installed IDM controllers: a launch of their own ahead of the step -- or, idm_in_step, the front of the step launch)
     if (p->idm_on && !idm_in_step(p) && (rc = idm_impl(p, (hipStream_t)hip_stream))) return rc;
     if (p->has_drift && (rc = drift_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
+    if (p->replay_types && (rc = replay_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     rc = collide_impl(p, true, interval_ms, (hipStream_t)hip_stream, p->integrator_variant);
     if (rc == T2D_OK) p->step_count++;
     if (rc == T2D_OK) rc = regenerate_done_scenes(p, (hipStream_t)hip_stream);
@@ -1191,10 +1223,10 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_step_n");
     if (interval_ms <= 0) return fail(p, T2D_ERR_INVALID, "interval_ms must be positive");
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !p->has_drift && !p->hgeo[1].present;
+    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
     const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;   // per-env history read by the epilogue
     // (the single-ego kernel has a LOOP form of its own, which reads the history with sc1 loads: IoU events are fine there)
-    const bool chain = p->chain_steps && n_steps >= 2 && p->fused_step && !p->grid_tier && (!p->idm_on || idm_in_step(p)) && !p->has_drift &&
+    const bool chain = p->chain_steps && n_steps >= 2 && p->fused_step && !p->grid_tier && (!p->idm_on || idm_in_step(p)) && !side_models(p) &&
                        !p->scene_regen && (ego ? p->chain_loop : !iou);
     const float *a0 = p->v.act0, *a1 = p->v.act1;
     int rc = T2D_OK;
@@ -1319,9 +1351,9 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
 
 int t2d_step_form(t2d_pool* p, int32_t n_steps) {
     if (!p) return -1;
-    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !p->has_drift && !p->hgeo[1].present;
+    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
     const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;
-    if (!p->fused_step || p->grid_tier || p->has_drift || p->scene_regen) return T2D_FORM_UNFUSED;
+    if (!p->fused_step || p->grid_tier || side_models(p) || p->scene_regen) return T2D_FORM_UNFUSED;
     const bool chain = p->chain_steps && n_steps >= 2 && (ego ? p->chain_loop : !iou);
     if (p->idm_on) {
         if (ego || !idm_in_step(p)) return T2D_FORM_UNFUSED;
@@ -1438,6 +1470,7 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     if (!p->have_params) return fail(p, T2D_ERR_STATE, "t2d_set_param_table must precede t2d_parking_scenes");
     if (p->v.A != 1) return fail(p, T2D_ERR_INVALID, "generated parking scenes need a pool with one participant per env");
     if (p->has_drift) return fail(p, T2D_ERR_INVALID, "SingleTrackDrift agents are not supported in generated parking scenes");
+    if (p->replay_types) return fail(p, T2D_ERR_INVALID, "replayed participants are not supported in generated parking scenes");
     if (p->hgeo[1].present) return fail(p, T2D_ERR_STATE, "lane geometry cannot be combined with generated parking scenes");
     if (env_stride < 0) return fail(p, T2D_ERR_INVALID, "env_stride must be >= 0");
     if (regenerate != 0 && regenerate != 1 && regenerate != 2)
@@ -2013,6 +2046,8 @@ int t2d_step_host(t2d_pool* p, const float* actions_host, const float* action_bo
     if (!p) return T2D_ERR_INVALID;
     if (!p->frame_sections) return fail(p, T2D_ERR_STATE, "t2d_frame_config must precede t2d_step_host");
     if (frame_index >= p->n_host_frames) return fail(p, T2D_ERR_INVALID, "frame_index out of range");
+    if (interval_ms > 0)   // (ahead of the staging: a refused step stages nothing)
+        if (int rc0 = replay_check(p, interval_ms)) return rc0;
     T2D_HIP(p, hipSetDevice(p->device));
     hipStream_t s = (hipStream_t)hip_stream;
     if (actions_host) {
@@ -2255,6 +2290,7 @@ struct t2d_traj {
     void* meta_dev = nullptr;
     hipEvent_t meta_done = nullptr;
     bool meta_pending = false;
+    int n_bound = 0;   // pools that replay this trajectory (t2d_replay_bind)
 };
 
 namespace {
@@ -2287,6 +2323,9 @@ int t2d_traj_create(t2d_pool* p, int32_t capacity, t2d_traj** out) {
 
 int t2d_traj_destroy(t2d_traj* t) {
     if (!t) return T2D_OK;
+    if (t->n_bound > 0)
+        return fail(t->pool, T2D_ERR_STATE, "t2d_traj_destroy: " + std::to_string(t->n_bound) + " pool(s) still replay this trajectory "
+                                             "(t2d_replay_bind with a null source, or t2d_destroy of the stepped pool, first)");
     (void)hipSetDevice(t->device);
     (void)quiesce(t->pool);   // records, copies and verify launches on the pool's streams
     if (t->meta_pending) (void)hipEventSynchronize(t->meta_done);
@@ -2409,6 +2448,101 @@ int t2d_verify_states(t2d_traj* t, int32_t n_frames, const int32_t* slot_host, c
     T2D_HIP(p, hipEventRecord(t->meta_done, s));
     t->meta_pending = true;
     return T2D_OK;
+}
+
+// ---- replayed participants (kernel: t2d_history.hip replay_kernel) --------------------------------------------------------
+static void replay_release(t2d_pool* p) {
+    if (p->replay_src) p->replay_src->n_bound--;
+    p->replay_src = nullptr;
+    if (p->d_replay_meta) (void)hipFree(p->d_replay_meta);
+    p->d_replay_meta = nullptr;
+    p->replay = t2d::ReplaySpec{};
+}
+
+static int replay_impl(t2d_pool* p, int step_ms, hipStream_t s) {
+    touch(p, s);
+    if (p->replay_src->pool != p) touch(p->replay_src->pool, s);   // (the source pool's set-up calls wait for readers of its buffer too)
+    t2d::ReplaySpec r = p->replay;
+    r.type_mask = p->replay_types;
+    T2D_HIP(p, t2d::launch_replay(p->v, r, step_ms, s));
+    return T2D_OK;
+}
+
+int t2d_replay_bind(t2d_pool* p, const t2d_traj* src, int32_t n_slots, int32_t t0_ms, int32_t period_ms,
+                    const int32_t* src_env, const int32_t* offset_ms, const int32_t* first_slot, const int32_t* last_slot) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (!src) {
+        T2D_HIP(p, quiesce(p));
+        replay_release(p);
+        return T2D_OK;
+    }
+    const int E = p->v.n_env, A = p->v.A;
+    if (src->device != p->device || src->pool->v.A != A)
+        return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: the source belongs to a pool of another max_agents or device");
+    const int n_src_env = src->N / A, N_src = src->N;
+    if (period_ms < 1) return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: period_ms must be >= 1");
+    if (n_slots < 1 || n_slots > src->capacity)
+        return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: n_slots " + std::to_string(n_slots) + " outside [1, " +
+                                            std::to_string(src->capacity) + "] (the source's capacity)");
+    if (t0_ms % period_ms != 0)
+        return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: t0_ms " + std::to_string(t0_ms) + " is not a multiple of period_ms " +
+                                            std::to_string(period_ms) + " (env time starts at 0: no step could land on a stamp)");
+    if (!src_env && n_src_env != E)
+        return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: a null src_env maps env e to source env e and needs as many source envs (" +
+                                            std::to_string(n_src_env) + ") as envs (" + std::to_string(E) + ")");
+    if ((first_slot == nullptr) != (last_slot == nullptr))
+        return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: pass both window arrays or neither");
+    // [src_env | offset_ms | first_slot | last_slot], each padded to a multiple of four words (16-byte loads of the windows)
+    const size_t e4 = ((size_t)E + 3) & ~(size_t)3, n4 = ((size_t)N_src + 3) & ~(size_t)3;
+    std::vector<int32_t> meta(2 * e4 + 2 * n4, 0);
+    int32_t *m_env = meta.data(), *m_off = m_env + e4, *m_first = m_off + e4, *m_last = m_first + n4;
+    for (int e = 0; e < E; ++e) {
+        m_env[e] = src_env ? src_env[e] : e;
+        m_off[e] = offset_ms ? offset_ms[e] : 0;
+        if (m_env[e] < 0 || m_env[e] >= n_src_env)
+            return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: src_env[" + std::to_string(e) + "] = " + std::to_string(m_env[e]) +
+                                                " outside [0, " + std::to_string(n_src_env) + ")");
+        if (m_off[e] % period_ms != 0)
+            return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: offset_ms[" + std::to_string(e) + "] = " + std::to_string(m_off[e]) +
+                                                " is not a multiple of period_ms " + std::to_string(period_ms));
+    }
+    for (int j = 0; j < N_src; ++j) {
+        m_first[j] = first_slot ? first_slot[j] : 0;
+        m_last[j] = last_slot ? last_slot[j] : n_slots - 1;
+        if (m_first[j] < 0 || m_first[j] >= n_slots || m_last[j] < 0 || m_last[j] >= n_slots)
+            return fail(p, T2D_ERR_INVALID, "t2d_replay_bind: the window of source participant " + std::to_string(j) + ", [" +
+                                                std::to_string(m_first[j]) + ", " + std::to_string(m_last[j]) + "], leaves [0, " +
+                                                std::to_string(n_slots) + ")");
+    }
+    int32_t* d_meta = nullptr;
+    if (hipMalloc((void**)&d_meta, meta.size() * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(p, T2D_ERR_NOMEM, "t2d_replay_bind: " + std::to_string(meta.size() * sizeof(int32_t)) + " bytes of device memory");
+    }
+    hipError_t he = quiesce(p);   // (a step that still reads the previous binding)
+    if (he == hipSuccess) he = hipMemcpy(d_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipFree(d_meta);
+        return fail(p, T2D_ERR_HIP, std::string("t2d_replay_bind: ") + hipGetErrorString(he));
+    }
+    replay_release(p);   // nothing can fail from here on: the new binding replaces the old one whole
+    p->d_replay_meta = d_meta;
+    p->replay_src = const_cast<t2d_traj*>(src);
+    p->replay_src->n_bound++;
+    p->replay = t2d::ReplaySpec{src->buf, d_meta, d_meta + e4, d_meta + 2 * e4, d_meta + 2 * e4 + n4, 0u,
+                                src->capacity, N_src, n_slots, t0_ms, period_ms};
+    return T2D_OK;
+}
+
+int t2d_replay_apply(t2d_pool* p, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_replay_apply");
+    if (!p->replay_src) return fail(p, T2D_ERR_STATE, "t2d_replay_bind must precede t2d_replay_apply");
+    if (!p->replay_types) return T2D_OK;   // (no row of the table is replayed: nothing to write)
+    T2D_HIP(p, hipSetDevice(p->device));
+    return replay_impl(p, 0, (hipStream_t)hip_stream);
 }
 
 int t2d_set_outputs(t2d_pool* p, uint32_t mask) {

@@ -80,7 +80,8 @@ __global__ __launch_bounds__(kDriftBlock) void drift_kernel(PoolView pv, int int
     if (i >= pv.N) return;
     const uint32_t ids = pv.ids[i];
     const int model = (ids >> kIdsModelShift) & 0xff;
-    if (!((ids >> kIdsActiveShift) & 0xffu) || model < T2D_MODEL_DRIFT) return;
+    // (replayed participants, T2D_MODEL_REPLAY, are written by replay_kernel: t2d_history.hip)
+    if (!((ids >> kIdsActiveShift) & 0xffu) || model < T2D_MODEL_DRIFT || model > T2D_MODEL_POINTMASS_EULER) return;
     const int type = (ids >> kIdsTypeShift) & 0xff;
     auto P = [&](int col) -> double { return pv.params[col * T2D_MAX_TYPES + type]; };
     if (model == T2D_MODEL_POINTMASS_EULER) {

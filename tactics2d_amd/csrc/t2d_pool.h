@@ -237,6 +237,18 @@ struct FrameView {
     int32_t ego_index;
 };
 
+// Replayed participants (T2D_MODEL_REPLAY; replay_kernel in t2d_history.hip): what a binding holds on the device.  The four
+// arrays share one allocation, each starting on a 16-byte boundary.
+struct ReplaySpec {
+    const float* src;            // the source trajectory's buffer, [T2D_TRAJ_COLS][capacity][N_src]
+    const int32_t* src_env;      // [n_env]
+    const int32_t* offset_ms;    // [n_env]
+    const int32_t* first_slot;   // [N_src]
+    const int32_t* last_slot;    // [N_src]
+    uint32_t type_mask;          // bit t: row t of the parameter table has model T2D_MODEL_REPLAY (set at launch time)
+    int32_t capacity, N_src, n_slots, t0_ms, period_ms;
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -306,6 +318,11 @@ struct t2d_pool {
     double *d_beam_sin = nullptr, *d_beam_cos = nullptr;
     double* d_time_penalty = nullptr;
     bool has_drift = false;   // a T2D_MODEL_DRIFT row is in the parameter table
+    // replayed participants (t2d_replay_bind): rows of model T2D_MODEL_REPLAY, the bound source and the device arrays of the binding
+    uint32_t replay_types = 0;         // bit t: row t of the parameter table has model T2D_MODEL_REPLAY
+    struct t2d_traj* replay_src = nullptr;   // null: no binding
+    t2d::ReplaySpec replay{};
+    int32_t* d_replay_meta = nullptr;
     float* d_snap_omega[2]{};
     // IDM agents (row f3)
     bool idm_on = false;
@@ -414,6 +431,8 @@ hipError_t launch_verify(const PoolView& v, const float* x, const float* y, cons
 hipError_t launch_traj_record(const PoolView& v, float* buf, int capacity, int slot, hipStream_t s);
 hipError_t launch_verify_states(const PoolView& v, const float* buf, int capacity, const int32_t* slot_dev,
                                 const double* interval_dev, int n_frames, int stable, uint8_t* valid, hipStream_t s);
+// replayed participants: state and active byte at stamp frame_ms + step_ms + offset (step_ms = 0: the envs' current stamp)
+hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

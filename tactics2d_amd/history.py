@@ -1,5 +1,5 @@
-"""Histories of a batch of participants: `BatchedTrajectory` on the host (opt-in, scope row a7) and `DeviceTrajectory`, recorded
-and kept on the device.
+"""Histories of a batch of participants: `BatchedTrajectory` on the host (opt-in, scope row a7), `DeviceTrajectory`, recorded
+and kept on the device, and `ReplaySource`: a recorded history that participants of a pool are replayed from inside the step.
 
 The device pool keeps only the CURRENT state: the reference's per-participant frame -> State dictionary
 (`tactics2d.participant.trajectory.Trajectory`, participant/trajectory/trajectory.py:12-188) grows without bound and is exactly
@@ -199,7 +199,8 @@ class _TrajBuffer:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self.pool._lib.t2d_traj_destroy(self._h)
+            # (refused -- T2DError, ERR_STATE -- while a pool still replays this buffer: pool.replay_unbind() first)
+            self.pool._ck(self.pool._lib.t2d_traj_destroy(self._h))
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -378,3 +379,210 @@ class DeviceTrajectory(_TrajectoryBase):
         b.clear()
         self._n_used = 0
         self._commit(f0, 0)
+
+
+class _ReplayedParticipant:
+    """One participant of a ReplaySource, answering as the reference's ParticipantBase does (participant_base.py:166-203)."""
+
+    def __init__(self, source, j):
+        self._src, self._j = source, int(j)
+
+    @property
+    def first_frame(self):
+        s, j = self._src, self._j
+        return None if s.first_slot[j] > s.last_slot[j] else s.t0_ms + int(s.first_slot[j]) * s.period_ms
+
+    @property
+    def last_frame(self):
+        s, j = self._src, self._j
+        return None if s.first_slot[j] > s.last_slot[j] else s.t0_ms + int(s.last_slot[j]) * s.period_ms
+
+    def is_active(self, frame):
+        # (the reference's two comparisons, :175 -- a participant without a single state raises its TypeError: `frame < None`)
+        if frame < self.first_frame or frame > self.last_frame:
+            return False
+        return True
+
+    def get_state(self, frame):
+        """BatchedState of one participant; KeyError (:201-202) for a stamp the recording does not hold: outside the window
+        or off the grid."""
+        s, j = self._src, self._j
+        k, r = divmod(frame - s.t0_ms, s.period_ms)
+        if r != 0 or not (s.first_slot[j] <= k <= s.last_slot[j]):
+            raise KeyError(f"Time stamp {frame} is not found in the trajectory {j}.")
+        c = s.slot_states(int(k))[j]
+        return BatchedState(int(frame), c[0], c[1], c[2], c[4], c[5], speed=c[3])
+
+
+class ReplaySource:
+    """A recorded history on a uniform stamp grid that participants of a pool are replayed from (pool.replay_bind; model
+    layout.MODEL_REPLAY): slot k holds the states of stamp t0_ms + k * period_ms of n_src_env x max_agents source
+    participants, participant j being present in slots [first_slot[j], last_slot[j]] (first > last: never) -- the reference's
+    `first_frame <= frame <= last_frame` (participant_base.py:166-177).  The states live in a t2d_traj on the device (a
+    DeviceTrajectory's own buffer, or one uploaded into a pool that serves as the library); a source built from host data
+    without a pool answers is_active / get_state on the host and is uploaded by `upload(pool_like)`."""
+
+    def __init__(self, n_src_env, max_agents, n_slots, t0_ms, period_ms, first_slot=None, last_slot=None, states=None, buf=None,
+                 owner=None):
+        self.n_src_env, self.max_agents, self.n_slots = int(n_src_env), int(max_agents), int(n_slots)
+        self.n = self.n_src_env * self.max_agents
+        self.t0_ms, self.period_ms = int(t0_ms), int(period_ms)
+        if self.period_ms < 1:
+            raise ValueError("ReplaySource: period_ms must be >= 1")
+        if self.n_slots < 1:
+            raise ValueError("ReplaySource: a source holds at least one slot")
+        if self.t0_ms % self.period_ms:
+            raise ValueError(f"ReplaySource: t0_ms {self.t0_ms} is not a multiple of period_ms {self.period_ms} (env time starts "
+                             "at 0: no step could land on a stamp)")
+        first = np.zeros(self.n, np.int32) if first_slot is None else np.ascontiguousarray(first_slot, np.int32).reshape(-1)
+        last = np.full(self.n, self.n_slots - 1, np.int32) if last_slot is None else \
+            np.ascontiguousarray(last_slot, np.int32).reshape(-1)
+        if first.size != self.n or last.size != self.n:
+            raise ValueError(f"ReplaySource: windows of {first.size} / {last.size} participants for a source of {self.n}")
+        if ((first < 0) | (first >= self.n_slots) | (last < 0) | (last >= self.n_slots)).any():
+            raise ValueError(f"ReplaySource: a window slot outside [0, {self.n_slots})")
+        self.first_slot, self.last_slot = first, last
+        self._states = states    # host copy [n_slots, n, 6] float32, or None (device only)
+        self._buf = buf          # _TrajBuffer, or None (host only)
+        self._owner = owner      # whatever keeps the buffer's pool / trajectory alive
+
+    # ---- constructors ------------------------------------------------------------------------------
+    @classmethod
+    def from_device(cls, traj, t0_ms, period_ms, windows=None):
+        """A DeviceTrajectory recorded with `record` replays as it is: its slots in use must hold the stamps t0_ms, t0_ms +
+        period_ms, ... in order.  windows: (first_slot, last_slot) int32 [N] or None = every slot."""
+        n_slots = traj._n_used
+        for k in range(n_slots):
+            if traj._slot_frame.get(k) != int(t0_ms) + k * int(period_ms):
+                raise ValueError(f"from_device: slot {k} holds stamp {traj._slot_frame.get(k)}, not {int(t0_ms) + k * int(period_ms)}: "
+                                 "the recording does not lie on the grid")
+        first, last = (None, None) if windows is None else windows
+        pool = traj.pool
+        return cls(pool.n_env, pool.max_agents, n_slots, t0_ms, period_ms, first, last, buf=traj._buf, owner=traj)
+
+    @classmethod
+    def from_arrays(cls, pool_like, states, first_slot=None, last_slot=None, t0_ms=0, period_ms=40):
+        """states float32 [n_slots, n_src_env, max_agents, 6] (x, y, heading, speed, vx, vy; anything where a participant is
+        outside its window).  pool_like: a pool of the same max_agents on the device the source shall live on -- it holds the
+        buffer itself when it has n_src_env envs, else a library pool of n_src_env envs (never stepped) is created beside
+        it; None: a host-only source (`upload` later)."""
+        st = np.ascontiguousarray(states, np.float32)
+        if st.ndim != 4 or st.shape[3] != L.TRAJ_COLS:
+            raise ValueError("from_arrays: states must be [n_slots, n_src_env, max_agents, 6]")
+        src = cls(st.shape[1], st.shape[2], st.shape[0], t0_ms, period_ms, first_slot, last_slot,
+                  states=st.reshape(st.shape[0], -1, L.TRAJ_COLS))
+        return src if pool_like is None else src.upload(pool_like)
+
+    @classmethod
+    def from_trajectories(cls, pool_like, trajectories, t0_ms, period_ms, n_slots=None):
+        """Pack reference-style per-participant trajectories -- objects with `frames` and `get_state(frame)` whose states
+        carry x, y, heading, speed, vx / vy (scalars or one-element columns) -- onto the grid.  trajectories:
+        [n_src_env][max_agents] (None or an empty trajectory: a participant the recording never has).  A participant's
+        window is [first frame, last frame]; every grid stamp inside it must be in the trajectory (the reference's KeyError,
+        participant_base.py:201-202, otherwise), and its first and last frame must lie on the grid (ValueError)."""
+        n_src_env, A = len(trajectories), len(trajectories[0])
+        t0_ms, period_ms = int(t0_ms), int(period_ms)
+        if period_ms < 1:
+            raise ValueError("ReplaySource: period_ms must be >= 1")
+        spans = []
+        for row in trajectories:
+            if len(row) != A:
+                raise ValueError("from_trajectories: every source env needs the same number of participants")
+            for tr in row:
+                fr = [] if tr is None else list(tr.frames)
+                if not fr:
+                    spans.append(None)
+                    continue
+                lo, hi = min(fr), max(fr)
+                if (lo - t0_ms) % period_ms or (hi - t0_ms) % period_ms or lo < t0_ms:
+                    raise ValueError(f"from_trajectories: a trajectory spans [{lo}, {hi}] ms, off the grid {t0_ms} + k * {period_ms}")
+                spans.append(((lo - t0_ms) // period_ms, (hi - t0_ms) // period_ms))
+        need = 1 + max([hi for sp in spans if sp for hi in sp[1:]], default=0)
+        n_slots = need if n_slots is None else int(n_slots)
+        if n_slots < need:
+            raise ValueError(f"from_trajectories: the trajectories need {need} slots, n_slots is {n_slots}")
+        st = np.zeros((n_slots, n_src_env * A, L.TRAJ_COLS), np.float32)
+        first, last = np.ones(n_src_env * A, np.int32), np.zeros(n_src_env * A, np.int32)   # (first > last: never present)
+        flat = [tr for row in trajectories for tr in row]
+        for j, (tr, sp) in enumerate(zip(flat, spans)):
+            if sp is None:
+                continue
+            first[j], last[j] = sp
+            have = set(tr.frames)
+            for k in range(sp[0], sp[1] + 1):
+                f = t0_ms + k * period_ms
+                if f not in have:
+                    raise KeyError(f"Time stamp {f} is not found in the trajectory {getattr(tr, 'id_', j)}.")
+                st[k, j] = _scalar_state(tr.get_state(f))
+        src = cls(n_src_env, A, n_slots, t0_ms, period_ms, first, last, states=st)
+        return src if pool_like is None else src.upload(pool_like)
+
+    # ---- device ------------------------------------------------------------------------------------
+    def upload(self, pool_like):
+        """Put a host-built source on pool_like's device (see from_arrays); returns self."""
+        if self._buf is not None:
+            return self
+        if pool_like.max_agents != self.max_agents:
+            raise ValueError(f"ReplaySource: {self.max_agents} participants per source env, the pool has {pool_like.max_agents}")
+        owner = pool_like
+        if pool_like.n_env != self.n_src_env:   # a library pool of the source's size, on the same device, never stepped
+            owner = type(pool_like)(self.n_src_env, self.max_agents, pool_like.device_id, library=pool_like._lib)
+            self._library_pool = owner
+        buf = _TrajBuffer(owner, self.n_slots)
+        for k in range(self.n_slots):
+            buf.write(k, self._states[k].T)
+        self._buf, self._owner = buf, owner
+        return self
+
+    def device_buffer(self):
+        if self._buf is None:
+            raise ValueError("the replay source lives on the host only: upload(pool_like) first")
+        return self._buf
+
+    def close(self):
+        """Free a buffer this source uploaded itself (a DeviceTrajectory's stays its own)."""
+        if self._buf is not None and not isinstance(self._owner, DeviceTrajectory):
+            self._buf.close()
+            self._buf = None
+            if getattr(self, "_library_pool", None) is not None:
+                self._library_pool.close()
+                self._library_pool = None
+
+    # ---- the reference's questions, on the host ----------------------------------------------------------
+    def slot_states(self, k):
+        """float32 [n, 6] of slot k (one read of the device buffer for a source without a host copy)"""
+        if self._states is not None:
+            return self._states[k]
+        return self._buf.read(k).T
+
+    def participant(self, j, src_env=0):
+        return _ReplayedParticipant(self, int(src_env) * self.max_agents + int(j))
+
+    def is_active(self, j, frame, src_env=0):
+        return self.participant(j, src_env).is_active(frame)
+
+    def get_state(self, j, frame, src_env=0):
+        return self.participant(j, src_env).get_state(frame)
+
+    def slot_of(self, stamp_ms):
+        """the slot holding stamp_ms (array or scalar), -1 before t0_ms -- floor on the grid, as the kernel computes it"""
+        d = np.asarray(stamp_ms, np.int64) - self.t0_ms
+        return np.where(d < 0, -1, d // self.period_ms)
+
+    def active_mask(self, stamp_ms, src_env=None):
+        """bool [n_env, max_agents]: the window rule for env e showing source env src_env[e] at stamp stamp_ms[e] (scalar: all)"""
+        se = np.arange(self.n_src_env) if src_env is None else np.asarray(src_env, np.int64)
+        k = np.broadcast_to(self.slot_of(stamp_ms), se.shape)[:, None]
+        first = self.first_slot.reshape(self.n_src_env, self.max_agents)[se]
+        last = self.last_slot.reshape(self.n_src_env, self.max_agents)[se]
+        return (k >= first) & (k <= last) & (k < self.n_slots)
+
+
+def _scalar_state(s):
+    """x, y, heading, speed, vx, vy of one participant's state (a reference State or a one-element BatchedState), as the
+    pool stores them: the velocity and speed as the state derives them"""
+    one = lambda v: 0.0 if v is None else float(np.asarray(v, np.float64).reshape(-1)[0])
+    v = getattr(s, "velocity", None)
+    vx, vy = (s.vx, s.vy) if getattr(s, "vx", None) is not None and getattr(s, "vy", None) is not None else \
+        (v if v is not None else (None, None))
+    return np.array([one(s.x), one(s.y), one(s.heading), one(s.speed), one(vx), one(vy)], np.float32)

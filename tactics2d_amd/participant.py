@@ -78,6 +78,24 @@ def pedestrian_row(name, interval=100, delta_t=None):
     return m.param_row(L.SHAPE_CIRCLE, Ln, W)
 
 
+def replayed_row(name):
+    """The parameter row of a participant of template `name` (vehicle, cyclist or pedestrian) that is REPLAYED from a
+    recorded trajectory (layout.MODEL_REPLAY; pool.replay_bind): shape, length and width of the template, no physics."""
+    if name in PEDESTRIAN_TEMPLATE:
+        shape, (Ln, W) = L.SHAPE_CIRCLE, PEDESTRIAN_TEMPLATE[name][:2]
+    else:
+        shape, (Ln, W) = L.SHAPE_OBB, (VEHICLE_TEMPLATE.get(name) or CYCLIST_TEMPLATE[name])[:2]
+    return replayed_shape_row(shape, Ln, W)
+
+
+def replayed_shape_row(shape, length, width):
+    """replayed_row for a shape that is no template's (a logged vehicle's own length and width)"""
+    row = np.zeros(L.PARAM_COLS)
+    row[L.P_MODEL], row[L.P_SHAPE], row[L.P_LENGTH], row[L.P_WIDTH] = L.MODEL_REPLAY, shape, length, width
+    row[L.P_DELTA_T_MS] = 5   # (never read: a replayed participant has no sub-steps)
+    return row
+
+
 def full_type_table(interval=100):
     """All 25 reference participant types as one table (<= 32 rows): 9 kinematic vehicles,
     9 dynamic vehicles, 3 cyclists, 4 pedestrians.  Returns (rows, names)."""

@@ -103,6 +103,9 @@ class ParticipantPool:
     # ---------------------------------------------------------------- lifetime
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            self.replay_unbind()
+            for user in list(self.__dict__.get("_replay_users", ())):   # (pools that replay a trajectory of this one let go of it)
+                user.replay_unbind()
             for buf in list(self.__dict__.get("_traj_buffers", ())):   # (DeviceTrajectory buffers bound to this pool go first)
                 buf.close()
             self._lib.t2d_destroy(self._h)
@@ -269,6 +272,38 @@ class ParticipantPool:
             return None
         self.sync()
         return buf.cpu().numpy().astype(bool)
+
+    # ---------------------------------------------------------------- replayed participants
+    def replay_bind(self, source, src_env=None, offset_ms=None):
+        """Bind a history.ReplaySource: participants whose type row has model layout.MODEL_REPLAY take their state from it
+        inside every step (t2d_replay_bind).  src_env int32[n_env]: the source env each env shows (None: its own number);
+        offset_ms int32[n_env]: env e at env time f shows stamp f + offset_ms[e] (None: 0; multiples of the period)."""
+        import weakref
+        se = _arr(src_env, np.int32, self.n_env, "src_env")
+        off = _arr(offset_ms, np.int32, self.n_env, "offset_ms")
+        buf = source.device_buffer()
+        self._ck(self._lib.t2d_replay_bind(self._h, buf._live(), source.n_slots, source.t0_ms, source.period_ms, _p(se), _p(off),
+                                           _p(source.first_slot), _p(source.last_slot)))
+        self._replay_release_user()
+        self.replay_source = source
+        self.replay_src_env = np.arange(self.n_env, dtype=np.int32) if se is None else se.copy()
+        self.replay_offset_ms = np.zeros(self.n_env, np.int32) if off is None else off.copy()
+        buf.pool.__dict__.setdefault("_replay_users", weakref.WeakSet()).add(self)
+
+    def _replay_release_user(self):
+        src = self.__dict__.pop("replay_source", None)
+        if src is not None and src._buf is not None:
+            src._buf.pool.__dict__.get("_replay_users", set()).discard(self)
+
+    def replay_unbind(self):
+        if self.__dict__.get("replay_source") is not None and self._h:
+            self._ck(self._lib.t2d_replay_bind(self._h, None, 0, 0, 0, None, None, None, None))
+            self._replay_release_user()
+
+    def replay_apply(self, stream=None):
+        """The replayed participants' state and active byte at the envs' CURRENT time, advancing nothing (t2d_replay_apply):
+        after reset() and before snapshot() it puts them where the recording has them at episode start."""
+        self._ck(self._lib.t2d_replay_apply(self._h, stream))
 
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):

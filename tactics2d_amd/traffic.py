@@ -243,9 +243,20 @@ class BatchedScenarioManager:
         raise NotImplementedError("rendering is outside the accelerated path (DESIGN.md section 9)")
 
     def get_active_participants(self, frame=None):
-        """Per scene, the indices of the active participants (scenario_manager.py:83-94)."""
-        ids = self.pool.download(L.F_IDS).reshape(self.n_env, self.max_agents)
-        act = (ids >> 16) & 0xff
+        """Per scene, the indices of the active participants (scenario_manager.py:83-94).  frame None: the participants active
+        on the device now.  With a frame (ms of env time) on a pool with a bound replay source (pool.replay_bind): replayed
+        participants answer by their recording's window at that env time -- `p.is_active(frame)`, without a device call;
+        `replayed` (bool [n_env, max_agents], default: every participant) says which participants are replayed ones, the
+        others count as active."""
+        if frame is None or getattr(self.pool, "replay_source", None) is None:
+            ids = self.pool.download(L.F_IDS).reshape(self.n_env, self.max_agents)
+            act = (ids >> 16) & 0xff
+            return [np.nonzero(a)[0].tolist() for a in act]
+        src = self.pool.replay_source
+        act = src.active_mask(np.asarray(frame) + self.pool.replay_offset_ms, self.pool.replay_src_env)
+        replayed = getattr(self, "replayed", None)
+        if replayed is not None:
+            act = act | ~np.asarray(replayed, bool).reshape(self.n_env, self.max_agents)
         return [np.nonzero(a)[0].tolist() for a in act]
 
     def get_observation(self):
