@@ -42,6 +42,8 @@
  *   t2d_traj_* /          <- Trajectory.add_state / get_state / history_states  participant/trajectory/trajectory.py:115-188
  *   t2d_verify_states        PhysicsModelBase.verify_states  physics/physics_model_base.py:53-73
  *                            ParticipantBase._verify_trajectory  participant/element/participant_base.py:120-131
+ *   t2d_set_routes* /     <- OffRoute.reset / update             traffic/event_detection/off_route.py:24-51
+ *   t2d_off_route            Trajectory.get_trace (trace routes)  participant/trajectory/trajectory.py:151-168
  *   t2d_step_host         <- ParkingEnv.step as its caller sees it: host action in, host 5-tuple out
  *                            envs/parking.py:219-256, _get_infos / _get_relative_pose :190-217
  *
@@ -649,6 +651,65 @@ int t2d_replay_bind(t2d_pool* pool, const t2d_traj* src, int32_t n_slots, int32_
                     const int32_t* src_env, const int32_t* offset_ms, const int32_t* first_slot, const int32_t* last_slot);
 int t2d_replay_apply(t2d_pool* pool, void* hip_stream);
 
+/* Off-route detection -- OffRoute.update (traffic/event_detection/off_route.py:24-34: `route.distance(location) > threshold`,
+ * location = the participant's centre point, route = a LineString) for every participant of every env in ONE launch.
+ *
+ * Per participant i with position (x, y) (the pool's fp32 columns), a route (a polyline of n >= 2 fp32 vertices, env-local
+ * coordinates) and a threshold (fp32), everything widened to fp64, one rounding per operation, per segment A -> B:
+ *   ux = Bx - Ax, uy = By - Ay, wx = Px - Ax, wy = Py - Ay, L2 = ux ux + uy uy, t = wx ux + wy uy;
+ *   t <= 0: d2 = wx wx + wy wy;  else t >= L2: vx = Px - Bx, vy = Py - By, d2 = vx vx + vy vy;  else c = wx uy - wy ux,
+ *   d2 = (c c) / L2   (a zero-length segment has t = 0 and takes the first branch);
+ * d2min = the minimum over the segments in vertex order (strict <: the first minimum wins), d = sqrt(d2min) (IEEE),
+ * off = d > (double)threshold (strict, as the reference), distance = (float)d.  A negative threshold makes every finite
+ * distance "off", a NaN threshold none (both as in the reference).
+ * BUILD-DEFINED (the reference raises, or cannot build such a LineString; a batched call cannot raise per lane): no route for
+ * the participant (route_of = -1), an inactive participant (active byte of T2D_F_IDS), a non-finite x or y, or a trace route
+ * whose window holds fewer than two slots: off = 0, distance = NaN.  A pedestrian is a point like everyone else: the centre,
+ * never the shape.  PARITY UNPINNED against the reference's engine (GEOS is not available to this build): the arithmetic is
+ * pinned against exact rational arithmetic (tests/route_ref.py).
+ *
+ * One kind of routes is installed at a time; installing one replaces the other.  All host arrays are read during the call.
+ *   t2d_set_routes          map routes, shared between envs.  A route SET is a list of polylines, CSR like
+ *                           t2d_set_static_geometry: routes of set s are [set_route_offsets[s], set_route_offsets[s + 1]),
+ *                           vertices of route r are [route_vert_offsets[r], route_vert_offsets[r + 1]) of verts_xy (interleaved
+ *                           x, y).  set_of_env[e] picks the set env e uses (NULL: set 0 for every env -- 4096 envs on one map
+ *                           hold one copy of it); route_of[i] = index of participant i's route inside its env's set, -1 = none
+ *                           (NULL: none for everybody); threshold[i] (NULL: 0 for everybody).  n_sets = 0 or NULL offsets
+ *                           clear the routes (of either kind).  A set holds at most T2D_MAX_ROUTE_SET_VERTS vertices (the
+ *                           kernel stages the env's set in LDS): T2D_ERR_GEOMETRY beyond, the message names limit and set.
+ *   t2d_set_route_assignment  route_of / threshold alone (either may be NULL = unchanged): a new episode on the same map
+ *                           re-uploads no geometry.  For trace routes route_of is the source agent index (below).
+ *   t2d_set_routes_from_traj  trace routes, straight from a recorded trajectory: the route of participant (e, a) is the
+ *                           polyline through the (x, y) of source participant (src_env[e], route_of[i]) in slots
+ *                           first_slot .. last_slot of traj (Trajectory.get_trace(frame_range),
+ *                           participant/trajectory/trajectory.py:151-168: every recorded stamp in the window, in order).
+ *                           route_of NULL: the own agent index a; -1: none.  src_env NULL: e itself (needs as many source
+ *                           envs as envs); first_slot / last_slot [N_src], NULL = 0 .. n_slots - 1, first > last is legal
+ *                           (= no route).  The source follows t2d_replay_bind's rules (same max_agents and device, possibly
+ *                           another pool).  NO VERTEX IS COPIED: the kernel reads the trajectory's own x and y columns, so
+ *                           re-recording a bound slot changes the route, and the trajectory must outlive the binding
+ *                           (t2d_traj_destroy of a bound one: T2D_ERR_STATE, as for replay; t2d_set_routes(pool, 0, ...) or
+ *                           t2d_destroy of the pool releases it).
+ *   t2d_off_route           one launch, asynchronous on hip_stream, reads the pool's current state, writes distance f32[N]
+ *                           and verdict u8[N] to caller-owned device memory; a NULL output goes to a buffer of the pool's own
+ *                           (t2d_off_route_buffers; allocated on first use).  Reads the status configuration nowhere and
+ *                           changes no pool field, flag bit, status or reward.  kernel_id 9 in t2d_profile_read.  No stepping
+ *                           call launches it.
+ * Errors, before anything is enqueued and leaving the previous routes installed: T2D_ERR_INVALID for non-monotone offsets, a
+ * route of fewer than two vertices, set_of_env / route_of / src_env out of range, n_slots outside [1, capacity], a window slot
+ * outside [0, n_slots), a source of another max_agents or device; T2D_ERR_GEOMETRY for a set beyond T2D_MAX_ROUTE_SET_VERTS;
+ * T2D_ERR_STATE for t2d_off_route without routes, without a parameter table or without a t2d_reset, for
+ * t2d_set_route_assignment without routes, and for t2d_off_route_buffers before the first use of the pool's own buffers.  */
+#define T2D_MAX_ROUTE_SET_VERTS 4096   /* vertices of one route set (64 routes x 64 vertices: 32 KiB of LDS as fp32 pairs) */
+int t2d_set_routes(t2d_pool* pool, int32_t n_sets, const int32_t* set_route_offsets, const int32_t* route_vert_offsets,
+                   const float* verts_xy, const int32_t* set_of_env, const int32_t* route_of, const float* threshold);
+int t2d_set_route_assignment(t2d_pool* pool, const int32_t* route_of, const float* threshold);
+int t2d_set_routes_from_traj(t2d_pool* pool, const t2d_traj* traj, int32_t n_slots, const int32_t* src_env,
+                             const int32_t* first_slot, const int32_t* last_slot, const int32_t* route_of,
+                             const float* threshold);
+int t2d_off_route(t2d_pool* pool, float* dist_out_dev, uint8_t* off_out_dev, void* hip_stream);
+int t2d_off_route_buffers(t2d_pool* pool, void** dist_dev, void** off_dev, size_t* n_elements);
+
 /* Reset-time scene synthesis: ParkingLotGenerator.generate
  * (map/generator/generate_parking_lot.py:239-444) for n_env independent scenes, one lane per scene, on `device_id`.
  * PARITY UNPINNED against the reference: it draws from numpy's global MT19937 stream and evaluates its predicates in
@@ -725,7 +786,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel.
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
- * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all).                                     */
+ * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route).       */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -543,12 +543,16 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
 }
 
 static void replay_release(t2d_pool* p);   // (drops a replay binding: defined with t2d_replay_bind)
+static void route_release(t2d_pool* p);    // (drops the installed routes: defined with t2d_set_routes)
 
 int t2d_destroy(t2d_pool* p) {
     if (!p) return T2D_OK;
     (void)hipSetDevice(p->device);
     (void)quiesce(p);  // nothing of this pool may still be running (incl. a scene refill on its own stream)
     replay_release(p);
+    route_release(p);
+    for (void* b : {(void*)p->d_route_of, (void*)p->d_route_thr, (void*)p->d_route_dist, (void*)p->d_route_off})
+        if (b) (void)hipFree(b);
     for (int f = 0; f < T2D_F_COUNT; ++f)
         if (p->field_ptr[f]) (void)hipFree(p->field_ptr[f]);
     void* bufs[] = {p->d_params, p->d_geo, p->d_boundary, p->d_boundary_valid, p->d_target_xy, p->d_target_c,
@@ -2325,7 +2329,8 @@ int t2d_traj_destroy(t2d_traj* t) {
     if (!t) return T2D_OK;
     if (t->n_bound > 0)
         return fail(t->pool, T2D_ERR_STATE, "t2d_traj_destroy: " + std::to_string(t->n_bound) + " pool(s) still replay this trajectory "
-                                             "(t2d_replay_bind with a null source, or t2d_destroy of the stepped pool, first)");
+                                             "or take their routes from it (t2d_replay_bind with a null source / t2d_set_routes with "
+                                             "n_sets = 0, or t2d_destroy of the stepped pool, first)");
     (void)hipSetDevice(t->device);
     (void)quiesce(t->pool);   // records, copies and verify launches on the pool's streams
     if (t->meta_pending) (void)hipEventSynchronize(t->meta_done);
@@ -2543,6 +2548,257 @@ int t2d_replay_apply(t2d_pool* p, void* hip_stream) {
     if (!p->replay_types) return T2D_OK;   // (no row of the table is replayed: nothing to write)
     T2D_HIP(p, hipSetDevice(p->device));
     return replay_impl(p, 0, (hipStream_t)hip_stream);
+}
+
+// ---- off-route detector (kernels: t2d_route.hip) ---------------------------------------------------------------------------
+static void route_release(t2d_pool* p) {
+    if (p->route_src) p->route_src->n_bound--;
+    p->route_src = nullptr;
+    if (p->d_route_geo) (void)hipFree(p->d_route_geo);
+    p->d_route_geo = nullptr;
+    p->route = t2d::RouteView{};
+    p->route_limit.clear();
+}
+
+namespace {
+// route_of (NULL: `dflt(i)`) and threshold (NULL: 0) of every participant, checked against the per-env bound `limit`
+int route_assignment(t2d_pool* p, const char* who, const int32_t* route_of, const float* threshold, const std::vector<int32_t>& limit,
+                     bool own_index_default, std::vector<int32_t>& ro, std::vector<float>& th) {
+    const int A = p->v.A, N = p->v.N;
+    ro.resize(N);
+    th.assign(N, 0.f);
+    for (int i = 0; i < N; ++i) {
+        const int e = i / A;
+        ro[i] = route_of ? route_of[i] : own_index_default ? i - e * A : -1;
+        if (ro[i] < -1 || ro[i] >= limit[e])
+            return fail(p, T2D_ERR_INVALID, std::string(who) + ": route_of[" + std::to_string(i) + "] = " + std::to_string(ro[i]) +
+                                                " outside [-1, " + std::to_string(limit[e]) + ") (env " + std::to_string(e) + ")");
+        if (threshold) th[i] = threshold[i];
+    }
+    return T2D_OK;
+}
+
+// the pool's assignment arrays (allocated once), filled after the pool's work
+int route_assignment_upload(t2d_pool* p, const std::vector<int32_t>* ro, const std::vector<float>* th) {
+    const size_t N = (size_t)p->v.N;
+    if (!p->d_route_of) T2D_HIP(p, hipMalloc((void**)&p->d_route_of, N * sizeof(int32_t)));
+    if (!p->d_route_thr) T2D_HIP(p, hipMalloc((void**)&p->d_route_thr, N * sizeof(float)));
+    if (ro) T2D_HIP(p, hipMemcpy(p->d_route_of, ro->data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (th) T2D_HIP(p, hipMemcpy(p->d_route_thr, th->data(), N * sizeof(float), hipMemcpyHostToDevice));
+    return T2D_OK;
+}
+
+// a new geometry blob of 4-byte words on the device, filled after the pool's work; the caller commits it
+int route_blob(t2d_pool* p, const char* who, const std::vector<uint32_t>& words, void** out) {
+    void* d = nullptr;
+    const size_t bytes = std::max<size_t>(words.size(), 1) * sizeof(uint32_t);
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(p, T2D_ERR_NOMEM, std::string(who) + ": " + std::to_string(bytes) + " bytes of device memory");
+    }
+    hipError_t he = quiesce(p);   // (an evaluation that still reads the previous routes)
+    if (he == hipSuccess && !words.empty()) he = hipMemcpy(d, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipFree(d);
+        return fail(p, T2D_ERR_HIP, std::string(who) + ": " + hipGetErrorString(he));
+    }
+    *out = d;
+    return T2D_OK;
+}
+}  // namespace
+
+int t2d_set_routes(t2d_pool* p, int32_t n_sets, const int32_t* set_route_offsets, const int32_t* route_vert_offsets,
+                   const float* verts_xy, const int32_t* set_of_env, const int32_t* route_of, const float* threshold) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (n_sets < 0) return fail(p, T2D_ERR_INVALID, "t2d_set_routes: n_sets must be >= 0");
+    if (n_sets == 0 || !set_route_offsets) {
+        T2D_HIP(p, quiesce(p));
+        route_release(p);
+        return T2D_OK;
+    }
+    if (!route_vert_offsets || !verts_xy) return fail(p, T2D_ERR_INVALID, "t2d_set_routes: null route_vert_offsets / verts_xy");
+    const int E = p->v.n_env;
+    if (set_route_offsets[0] != 0 || route_vert_offsets[0] != 0)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_routes: offsets must start at 0");
+    for (int s = 0; s < n_sets; ++s)
+        if (set_route_offsets[s + 1] < set_route_offsets[s])
+            return fail(p, T2D_ERR_INVALID, "t2d_set_routes: set_route_offsets decreases at set " + std::to_string(s));
+    const int n_route = set_route_offsets[n_sets];
+    for (int r = 0; r < n_route; ++r)
+        if (route_vert_offsets[r + 1] - (int64_t)route_vert_offsets[r] < 2)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_routes: route " + std::to_string(r) + " has " +
+                                                std::to_string(route_vert_offsets[r + 1] - (int64_t)route_vert_offsets[r]) +
+                                                " vertices (a route is a polyline of at least two; offsets must increase)");
+    const int n_vert = route_vert_offsets[n_route];
+    int lds_bytes = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const int nr = set_route_offsets[s + 1] - set_route_offsets[s];
+        const int nv = route_vert_offsets[set_route_offsets[s + 1]] - route_vert_offsets[set_route_offsets[s]];
+        if (nv > T2D_MAX_ROUTE_SET_VERTS)
+            return fail(p, T2D_ERR_GEOMETRY, "t2d_set_routes: route set " + std::to_string(s) + " holds " + std::to_string(nv) +
+                                                 " vertices, more than T2D_MAX_ROUTE_SET_VERTS = " +
+                                                 std::to_string(T2D_MAX_ROUTE_SET_VERTS));
+        lds_bytes = std::max(lds_bytes, nv * 8 + (nr + 1) * 4);
+    }
+    std::vector<int32_t> limit(E);
+    for (int e = 0; e < E; ++e) {
+        const int s = set_of_env ? set_of_env[e] : 0;
+        if (s < 0 || s >= n_sets)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_routes: set_of_env[" + std::to_string(e) + "] = " + std::to_string(s) +
+                                                " outside [0, " + std::to_string(n_sets) + ")");
+        limit[e] = set_route_offsets[s + 1] - set_route_offsets[s];
+    }
+    std::vector<int32_t> ro;
+    std::vector<float> th;
+    int rc;
+    if ((rc = route_assignment(p, "t2d_set_routes", route_of, threshold, limit, false, ro, th))) return rc;
+    // [verts: 2 n_vert | set_of_env: E | set_route_start: n_sets + 1 | route_vert_off: n_route + 1]
+    std::vector<uint32_t> w((size_t)2 * n_vert + E + n_sets + 1 + n_route + 1);
+    memcpy(w.data(), verts_xy, (size_t)2 * n_vert * sizeof(float));
+    int32_t* wi = reinterpret_cast<int32_t*>(w.data()) + (size_t)2 * n_vert;
+    for (int e = 0; e < E; ++e) wi[e] = set_of_env ? set_of_env[e] : 0;
+    memcpy(wi + E, set_route_offsets, (size_t)(n_sets + 1) * sizeof(int32_t));
+    memcpy(wi + E + n_sets + 1, route_vert_offsets, (size_t)(n_route + 1) * sizeof(int32_t));
+    void* d = nullptr;
+    if ((rc = route_blob(p, "t2d_set_routes", w, &d))) return rc;
+    if ((rc = route_assignment_upload(p, &ro, &th))) {
+        (void)hipFree(d);
+        return rc;
+    }
+    route_release(p);   // nothing can fail from here on: the new routes replace the old ones whole
+    p->d_route_geo = d;
+    p->route_limit = std::move(limit);
+    t2d::RouteView& rv = p->route;
+    rv.kind = 1;
+    rv.lds_bytes = lds_bytes;
+    rv.route_of = p->d_route_of;
+    rv.threshold = p->d_route_thr;
+    rv.verts = (const float*)d;
+    rv.set_of_env = (const int32_t*)d + (size_t)2 * n_vert;
+    rv.set_route_start = rv.set_of_env + E;
+    rv.route_vert_off = rv.set_route_start + n_sets + 1;
+    return T2D_OK;
+}
+
+int t2d_set_route_assignment(t2d_pool* p, const int32_t* route_of, const float* threshold) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->route.kind) return fail(p, T2D_ERR_STATE, "t2d_set_routes / t2d_set_routes_from_traj must precede t2d_set_route_assignment");
+    T2D_HIP(p, hipSetDevice(p->device));
+    std::vector<int32_t> ro;
+    std::vector<float> th;
+    int rc;
+    // (checked even when only the thresholds change: a NULL route_of stands for the one installed, which was checked then)
+    if (route_of && (rc = route_assignment(p, "t2d_set_route_assignment", route_of, nullptr, p->route_limit, false, ro, th))) return rc;
+    if (threshold) th.assign(threshold, threshold + p->v.N);
+    T2D_HIP(p, quiesce(p));
+    return route_assignment_upload(p, route_of ? &ro : nullptr, threshold ? &th : nullptr);
+}
+
+int t2d_set_routes_from_traj(t2d_pool* p, const t2d_traj* src, int32_t n_slots, const int32_t* src_env, const int32_t* first_slot,
+                             const int32_t* last_slot, const int32_t* route_of, const float* threshold) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!src) return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: null trajectory (t2d_set_routes(pool, 0, ...) clears the routes)");
+    T2D_HIP(p, hipSetDevice(p->device));
+    const int E = p->v.n_env, A = p->v.A;
+    if (src->device != p->device || src->pool->v.A != A)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: the source belongs to a pool of another max_agents or device");
+    const int n_src_env = src->N / A, N_src = src->N;
+    if (n_slots < 1 || n_slots > src->capacity)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: n_slots " + std::to_string(n_slots) + " outside [1, " +
+                                            std::to_string(src->capacity) + "] (the source's capacity)");
+    if (!src_env && n_src_env != E)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: a null src_env maps env e to source env e and needs as many source "
+                                        "envs (" + std::to_string(n_src_env) + ") as envs (" + std::to_string(E) + ")");
+    if ((first_slot == nullptr) != (last_slot == nullptr))
+        return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: pass both window arrays or neither");
+    // [src_env: E | first_slot: N_src | last_slot: N_src]
+    std::vector<uint32_t> w((size_t)E + 2 * (size_t)N_src);
+    int32_t *m_env = reinterpret_cast<int32_t*>(w.data()), *m_first = m_env + E, *m_last = m_first + N_src;
+    for (int e = 0; e < E; ++e) {
+        m_env[e] = src_env ? src_env[e] : e;
+        if (m_env[e] < 0 || m_env[e] >= n_src_env)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: src_env[" + std::to_string(e) + "] = " + std::to_string(m_env[e]) +
+                                                " outside [0, " + std::to_string(n_src_env) + ")");
+    }
+    for (int j = 0; j < N_src; ++j) {
+        m_first[j] = first_slot ? first_slot[j] : 0;
+        m_last[j] = last_slot ? last_slot[j] : n_slots - 1;
+        if (m_first[j] < 0 || m_first[j] >= n_slots || m_last[j] < 0 || m_last[j] >= n_slots)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_routes_from_traj: the window of source participant " + std::to_string(j) + ", [" +
+                                                std::to_string(m_first[j]) + ", " + std::to_string(m_last[j]) + "], leaves [0, " +
+                                                std::to_string(n_slots) + ")");
+    }
+    std::vector<int32_t> limit(E, A), ro;
+    std::vector<float> th;
+    int rc;
+    if ((rc = route_assignment(p, "t2d_set_routes_from_traj", route_of, threshold, limit, true, ro, th))) return rc;
+    void* d = nullptr;
+    if ((rc = route_blob(p, "t2d_set_routes_from_traj", w, &d))) return rc;
+    if ((rc = route_assignment_upload(p, &ro, &th))) {
+        (void)hipFree(d);
+        return rc;
+    }
+    route_release(p);   // nothing can fail from here on
+    p->d_route_geo = d;
+    p->route_limit = std::move(limit);
+    p->route_src = const_cast<t2d_traj*>(src);
+    p->route_src->n_bound++;
+    t2d::RouteView& rv = p->route;
+    rv.kind = 2;
+    rv.route_of = p->d_route_of;
+    rv.threshold = p->d_route_thr;
+    const size_t col = (size_t)src->capacity * N_src;
+    rv.tx = src->buf;             // column 0 of [T2D_TRAJ_COLS][capacity][N_src]
+    rv.ty = src->buf + col;       // column 1
+    rv.src_env = (const int32_t*)d;
+    rv.first_slot = rv.src_env + E;
+    rv.last_slot = rv.first_slot + N_src;
+    rv.N_src = N_src;
+    // lanes per participant: the smallest power of two that still puts ~128 K lanes to work, at most one per segment of the
+    // longest window and at most a wave (traj_verify_group_log2's rule)
+    int max_segs = 0;
+    for (int j = 0; j < N_src; ++j) max_segs = std::max(max_segs, m_last[j] - m_first[j]);
+    int lg = 0;
+    while (lg < 6 && ((int64_t)p->v.N << lg) < (1 << 17) && (1 << lg) < max_segs) ++lg;
+    rv.log2_group = lg;
+    return T2D_OK;
+}
+
+int t2d_off_route(t2d_pool* p, float* dist_out_dev, uint8_t* off_out_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->route.kind) return fail(p, T2D_ERR_STATE, "t2d_set_routes / t2d_set_routes_from_traj must precede t2d_off_route");
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_off_route");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if ((!dist_out_dev || !off_out_dev) && !p->d_route_dist) {   // first use of the pool's own buffers
+        T2D_HIP(p, hipMalloc((void**)&p->d_route_dist, (size_t)p->v.N * sizeof(float)));
+        if (hipMalloc((void**)&p->d_route_off, (size_t)p->v.N) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(p->d_route_dist);
+            p->d_route_dist = nullptr;
+            return fail(p, T2D_ERR_NOMEM, "t2d_off_route: the pool's own result buffers");
+        }
+    }
+    touch(p, s);
+    if (p->route_src && p->route_src->pool != p) touch(p->route_src->pool, s);   // (the source pool's set-up calls wait for readers of its buffer)
+    int rc;
+    if ((rc = record_event(p, 9, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_off_route(p->v, p->route, dist_out_dev ? dist_out_dev : p->d_route_dist,
+                                     off_out_dev ? off_out_dev : p->d_route_off, s));
+    return record_event(p, 9, s, false);
+}
+
+int t2d_off_route_buffers(t2d_pool* p, void** dist_dev, void** off_dev, size_t* n_elements) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!dist_dev || !off_dev || !n_elements) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->d_route_dist)
+        return fail(p, T2D_ERR_STATE, "a t2d_off_route with a NULL destination must precede t2d_off_route_buffers");
+    *dist_dev = p->d_route_dist;
+    *off_dev = p->d_route_off;
+    *n_elements = (size_t)p->v.N;
+    return T2D_OK;
 }
 
 int t2d_set_outputs(t2d_pool* p, uint32_t mask) {

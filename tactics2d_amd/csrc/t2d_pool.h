@@ -249,6 +249,23 @@ struct ReplaySpec {
     int32_t capacity, N_src, n_slots, t0_ms, period_ms;
 };
 
+// Off-route detector (t2d_route.hip): what an installed kind of routes holds on the device.  kind 1 = route sets (polylines
+// in CSR form, shared between envs), kind 2 = trace routes read out of a recorded trajectory's own x / y columns.
+struct RouteView {
+    int32_t kind;                    // 0 none, 1 sets, 2 traces
+    int32_t lds_bytes;               // sets: dynamic LDS of the launch (the largest set's vertices + route offsets)
+    const int32_t* route_of;         // [N] sets: route inside the env's set; traces: agent index of the source participant; -1 none
+    const float* threshold;          // [N]
+    const int32_t* set_of_env;       // [E] sets
+    const int32_t* set_route_start;  // [n_sets + 1] first route of each set
+    const int32_t* route_vert_off;   // [n_route + 1] first vertex of each route
+    const float* verts;              // [n_vert][2]
+    const float *tx, *ty;            // traces: the source trajectory's x and y columns, [capacity][N_src]
+    const int32_t *src_env, *first_slot, *last_slot;   // traces: [E], [N_src], [N_src]
+    int32_t N_src;
+    int32_t log2_group;              // traces: 1 << log2_group lanes per participant (0: one lane each)
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -323,6 +340,16 @@ struct t2d_pool {
     struct t2d_traj* replay_src = nullptr;   // null: no binding
     t2d::ReplaySpec replay{};
     int32_t* d_replay_meta = nullptr;
+    // off-route detector (t2d_set_routes / t2d_set_routes_from_traj): the installed routes, the assignment arrays and the pool's
+    // own result buffers (first NULL-destination t2d_off_route)
+    t2d::RouteView route{};
+    struct t2d_traj* route_src = nullptr;   // trace routes: the bound trajectory
+    void* d_route_geo = nullptr;            // sets: verts | set_of_env | set_route_start | route_vert_off; traces: src_env | first | last
+    int32_t* d_route_of = nullptr;
+    float* d_route_thr = nullptr;
+    float* d_route_dist = nullptr;
+    uint8_t* d_route_off = nullptr;
+    std::vector<int32_t> route_limit;       // [E] exclusive upper bound of route_of in env e (routes of its set / max_agents)
     float* d_snap_omega[2]{};
     // IDM agents (row f3)
     bool idm_on = false;
@@ -433,6 +460,8 @@ hipError_t launch_verify_states(const PoolView& v, const float* buf, int capacit
                                 const double* interval_dev, int n_frames, int stable, uint8_t* valid, hipStream_t s);
 // replayed participants: state and active byte at stamp frame_ms + step_ms + offset (step_ms = 0: the envs' current stamp)
 hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hipStream_t s);
+// off-route detector (t2d_route.hip): distance (f32) and verdict (u8) of every participant against its route
+hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

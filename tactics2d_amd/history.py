@@ -315,6 +315,16 @@ class DeviceTrajectory(_TrajectoryBase):
         ptr, _ = self._buf.column_ptr(col)
         return _DevArray(ptr, (self._n_used, self.n), self._buf)
 
+    def traces(self):
+        """host copy of the recorded (x, y) of every participant: float32 [slots in use, N, 2], row k = slot k (tests; the
+        device-side counterpart is set_routes_from)"""
+        return np.stack([self._buf.rows(L.TRAJ_X, self._n_used), self._buf.rows(L.TRAJ_Y, self._n_used)], -1)
+
+    def set_routes_from(self, pool, route_of=None, threshold=0.0, src_env=None, windows=None):
+        """Make this recording the routes of `pool`'s off-route detector without touching the host: participant (e, a) follows
+        the recorded trace of participant (src_env[e], route_of) -- its own by default (pool.set_routes_from)."""
+        pool.set_routes_from(self, src_env, windows, route_of, threshold)
+
     def slots(self):
         """int32[len(frames)]: the slot of each stamp (duplicates resolve to the overwritten state, as the reference's dict)"""
         return np.array([self._book.by_frame[f] for f in self._book.stamps], np.int32)
@@ -554,6 +564,17 @@ class ReplaySource:
         if self._states is not None:
             return self._states[k]
         return self._buf.read(k).T
+
+    def traces(self):
+        """host copies of every source participant's trace -- `get_trace` over its window: a list of N float32 (k, 2) arrays,
+        the (x, y) of slots first_slot[j] .. last_slot[j] in order (k = 0 where first > last)"""
+        xy = np.stack([self.slot_states(k)[:, :2] for k in range(self.n_slots)])   # [n_slots, N, 2]
+        return [np.ascontiguousarray(xy[self.first_slot[j]:self.last_slot[j] + 1, j], np.float32) for j in range(self.n)]
+
+    def set_routes_from(self, pool, route_of=None, threshold=0.0, src_env=None, windows=None):
+        """Make the source's traces the routes of `pool`'s off-route detector, read on the device (pool.set_routes_from: the
+        source's windows, and the src_env of the pool's replay binding of this source, unless given)."""
+        pool.set_routes_from(self, src_env, windows, route_of, threshold)
 
     def participant(self, j, src_env=0):
         return _ReplayedParticipant(self, int(src_env) * self.max_agents + int(j))

@@ -40,6 +40,8 @@ OUT_VELOCITY, OUT_APPLIED, OUT_ALL = 1, 2, 3
 SAFE_RECTS = 4
 MAX_POLY_VERTS = 8
 MAX_AGENTS = 256
+MAX_ROUTE_SET_VERTS = 4096   # T2D_MAX_ROUTE_SET_VERTS: vertices of one route set (t2d_set_routes)
+PROFILE_OFF_ROUTE = 9        # kernel id of t2d_off_route in t2d_profile_read
 # IDM controller parameter sets (t2d_set_idm)
 IDM_DESIRED_SPEED, IDM_TIME_HEADWAY, IDM_MIN_SPACING, IDM_MAX_ACCEL, IDM_COMF_DECEL, IDM_DELTA = range(6)
 IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7

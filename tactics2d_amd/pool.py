@@ -104,8 +104,11 @@ class ParticipantPool:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self.replay_unbind()
+            self.clear_routes()
             for user in list(self.__dict__.get("_replay_users", ())):   # (pools that replay a trajectory of this one let go of it)
                 user.replay_unbind()
+            for user in list(self.__dict__.get("_route_users", ())):    # (... or take their routes from one)
+                user.clear_routes()
             for buf in list(self.__dict__.get("_traj_buffers", ())):   # (DeviceTrajectory buffers bound to this pool go first)
                 buf.close()
             self._lib.t2d_destroy(self._h)
@@ -304,6 +307,104 @@ class ParticipantPool:
         """The replayed participants' state and active byte at the envs' CURRENT time, advancing nothing (t2d_replay_apply):
         after reset() and before snapshot() it puts them where the recording has them at episode start."""
         self._ck(self._lib.t2d_replay_apply(self._h, stream))
+
+    # ---------------------------------------------------------------- off-route detection
+    def _route_assignment(self, route_of, threshold):
+        """int32[n] / float32[n] (None stays None); scalars and [n_env, max_agents] arrays are accepted"""
+        def flat(v, dtype, name):
+            if v is None:
+                return None
+            a = np.asarray(v, dtype)
+            return _arr(np.broadcast_to(a.reshape(-1) if a.ndim else a, (self.n,)), dtype, self.n, name)
+        return flat(route_of, np.int32, "route_of"), flat(threshold, np.float32, "threshold")
+
+    def set_routes(self, route_sets, set_of_env=None, route_of=None, threshold=0.0):
+        """Install map routes for the off-route detector (t2d_set_routes).  route_sets: [[polyline (n, 2), ...] per set] (or
+        the CSR triple of traffic.routes_to_csr); set_of_env int32[n_env]: the set each env uses (None: set 0 serves every
+        env -- one copy of the map); route_of int32[n]: the route of each participant inside its env's set, -1 = none (a
+        scalar broadcasts; None: route 0 for everybody); threshold float32[n] (a scalar broadcasts)."""
+        from .traffic import routes_to_csr
+        so, vo, xy = route_sets if isinstance(route_sets, tuple) else routes_to_csr(route_sets)
+        so, vo = _arr(so, np.int32, None, "set offsets"), _arr(vo, np.int32, None, "route offsets")
+        xy = _arr(xy, np.float32, None, "verts_xy")
+        if so.size < 2 or vo.size != so[-1] + 1 or xy.size != 2 * vo[-1]:
+            raise ValueError("route sets: need n_sets + 1 set offsets (n_sets >= 1), n_route + 1 route offsets and 2 * n_vert coordinates")
+        se = _arr(set_of_env, np.int32, self.n_env, "set_of_env")
+        ro, th = self._route_assignment(0 if route_of is None else route_of, threshold)
+        self._ck(self._lib.t2d_set_routes(self._h, so.size - 1, _p(so), _p(vo), _p(xy), _p(se), _p(ro), _p(th)))
+        self._route_release_user()
+        self.route_kind = "sets"
+
+    def set_route_assignment(self, route_of=None, threshold=None):
+        """route_of / threshold of the installed routes alone (t2d_set_route_assignment; None = unchanged): a new episode on the
+        same map uploads no geometry.  For trace routes route_of is the source agent index."""
+        ro, th = self._route_assignment(route_of, threshold)
+        self._ck(self._lib.t2d_set_route_assignment(self._h, _p(ro), _p(th)))
+
+    def set_routes_from(self, source, src_env=None, windows=None, route_of=None, threshold=0.0):
+        """Trace routes straight from a recording (t2d_set_routes_from_traj): the route of participant (e, a) is the polyline
+        through the recorded (x, y) of source participant (src_env[e], route_of[i]) -- `get_trace` -- read by the kernel out of
+        the trajectory's own columns; nothing is copied or brought to the host.  source: a history.DeviceTrajectory (every slot
+        in use) or a history.ReplaySource (its windows; src_env defaults to the current replay binding's when this pool replays
+        that source).  windows: (first_slot, last_slot) int32[N_src]; route_of None: the own agent index, -1 = none."""
+        import weakref
+        from .history import DeviceTrajectory
+        if isinstance(source, DeviceTrajectory):
+            buf, n_slots = source._buf, source._n_used
+        else:
+            buf, n_slots = source.device_buffer(), source.n_slots
+            if windows is None:
+                windows = (source.first_slot, source.last_slot)
+            if src_env is None and self.__dict__.get("replay_source") is source:
+                src_env = self.replay_src_env
+        first, last = (None, None) if windows is None else windows
+        first, last = _arr(first, np.int32, buf.n, "first_slot"), _arr(last, np.int32, buf.n, "last_slot")
+        se = _arr(src_env, np.int32, self.n_env, "src_env")
+        ro, th = self._route_assignment(route_of, threshold)
+        self._ck(self._lib.t2d_set_routes_from_traj(self._h, buf._live(), int(n_slots), _p(se), _p(first), _p(last), _p(ro), _p(th)))
+        self._route_release_user()
+        self.route_kind = "traces"
+        self._route_buf = buf
+        buf.pool.__dict__.setdefault("_route_users", weakref.WeakSet()).add(self)
+
+    def _route_release_user(self):
+        buf = self.__dict__.pop("_route_buf", None)
+        if buf is not None:
+            buf.pool.__dict__.get("_route_users", set()).discard(self)
+        self.route_kind = None
+
+    def clear_routes(self):
+        if self.__dict__.get("route_kind") is not None and self._h:
+            self._ck(self._lib.t2d_set_routes(self._h, 0, None, None, None, None, None, None))
+            self._route_release_user()
+
+    def off_route(self, dist_ptr=None, off_ptr=None, stream=None):
+        """OffRoute.update for every participant in one launch (t2d_off_route): distance float32[n] and verdict uint8[n] written
+        to the device memory at dist_ptr / off_ptr, or -- None -- to buffers of the pool's own (off_route_buffers(),
+        off_route_all()).  Asynchronous on `stream`; reads the pool's current state, changes nothing in it."""
+        self._ck(self._lib.t2d_off_route(self._h, dist_ptr, off_ptr, stream))
+
+    def off_route_buffers(self):
+        """(distance pointer, verdict pointer, elements) of the pool's own result buffers (after an off_route() into them)."""
+        d, o, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._ck(self._lib.t2d_off_route_buffers(self._h, C.byref(d), C.byref(o), C.byref(n)))
+        return d.value, o.value, n.value
+
+    def off_route_all(self):
+        """The last off_route() into the pool's own buffers as numpy (distance float32, off bool), each [n_env, max_agents],
+        after the pool's work."""
+        import torch
+        d, o, n = self.off_route_buffers()
+        shape = (self.n_env, self.max_agents)
+        self.sync()
+        dev = f"cuda:{self.device_id}"
+        return (torch.as_tensor(_DevArray(d, shape, "<f4", self), device=dev).cpu().numpy(),
+                torch.as_tensor(_DevArray(o, shape, "|u1", self), device=dev).cpu().numpy().astype(bool))
+
+    def off_route_host(self, stream=None):
+        """off_route() into the pool's own buffers + off_route_all()."""
+        self.off_route(None, None, stream)
+        return self.off_route_all()
 
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):

@@ -6,6 +6,7 @@ Mirrors (tactics2d v0.1.9rc3):
     StaticCollision / DynamicCollision      traffic/event_detection/collision.py:12-46
     OutBound                                traffic/event_detection/out_bound.py:12-65
     OffLane                                 traffic/event_detection/off_lane.py:10-20
+    OffRoute                                traffic/event_detection/off_route.py:12-51
     TimeExceed                              traffic/event_detection/time_exceed.py:10-36
     ScenarioManager                         traffic/scenario_manager.py:13-98
     _ParkingScenarioManager.update/check_status/reset   envs/parking.py:352-441
@@ -57,6 +58,32 @@ def polygons_to_csr(per_env_polygons):
         eo.append(eo[-1] + len(polys))
     xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.float32)
     return np.array(eo, np.int32), np.array(vo, np.int32), xy
+
+
+def as_polyline(route):
+    """OffRoute.reset's acceptance rule (off_route.py:45-49): a LineString (anything with `.coords`) or what LineString(...)
+    accepts -- a sequence of at least two points of two (or three: z is dropped) numbers each -- as float32 (n, 2); TypeError
+    otherwise, as the reference raises for whatever LineString refuses."""
+    try:
+        pts = np.asarray(list(route.coords) if hasattr(route, "coords") else route, np.float64)
+        if pts.ndim != 2 or pts.shape[0] < 2 or pts.shape[1] not in (2, 3):
+            raise ValueError(pts.shape)
+    except Exception:
+        raise TypeError("The route should be a LineString or a list of points.") from None
+    return np.ascontiguousarray(pts[:, :2], np.float32)
+
+
+def routes_to_csr(route_sets):
+    """[[polyline, ...] per route set] -> (set_route_offsets, route_vert_offsets, verts_xy) for t2d_set_routes; every polyline
+    goes through as_polyline (TypeError for what cannot become a polyline of >= 2 points)."""
+    so, vo, xy = [0], [0], []
+    for routes in route_sets:
+        for r in routes:
+            q = as_polyline(r)
+            xy.append(q); vo.append(vo[-1] + len(q))
+        so.append(so[-1] + len(routes))
+    xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.float32)
+    return np.array(so, np.int32), np.array(vo, np.int32), xy
 
 
 class _FlagDetector:
@@ -131,6 +158,73 @@ class OffLane(_FlagDetector):
             self._m.pool.set_lane_geometry(self._m._lanes)
 
 
+class OffRoute:
+    """OffRoute (off_route.py:12-51) for every participant of every scene: `route.distance(centre) > threshold`, evaluated by
+    one launch of its own (t2d_off_route) -- no flag bit, status or reward is involved.
+
+    reset(route): the reference's form -- ONE polyline (a LineString, or a list of >= 2 points; TypeError otherwise) that
+    every participant of every scene follows.  The batched forms, by keyword:
+        reset(route_sets=[[polyline, ...] per set], set_of_env=int[n_env] | None, route_of=int[n_env, max_agents] | int)
+            per-scene sets of routes (None: set 0 serves every scene), per-participant route inside the scene's set (-1: none)
+        reset(source=DeviceTrajectory | ReplaySource, route_of=None, src_env=None, windows=None)
+            the recorded trace of a participant as its route (route_of None: its own), read on the device
+    threshold: a scalar or float[n_env, max_agents].  Participants without a route, inactive ones and non-finite positions
+    give False / NaN (build-defined, DESIGN.md)."""
+
+    def __init__(self, threshold, manager=None):
+        self.threshold = threshold
+        self.route = None
+        self._m = None
+        if manager is not None:
+            self.bind(manager)
+
+    def bind(self, manager):
+        self._m = manager
+        manager.off_route = self
+
+    @property
+    def installed(self):
+        return self.route is not None
+
+    def reset(self, route=None, *, route_sets=None, set_of_env=None, route_of=None, source=None, src_env=None, windows=None):
+        if sum(v is not None for v in (route, route_sets, source)) != 1:
+            raise TypeError("The route should be a LineString or a list of points.")
+        if route is not None:
+            route_sets, set_of_env, route_of = [[as_polyline(route)]], None, 0
+        if route_sets is not None:
+            csr = route_sets if isinstance(route_sets, tuple) else routes_to_csr(route_sets)
+            if self._m is not None:
+                self._m.pool.set_routes(csr, set_of_env, 0 if route_of is None else route_of, self.threshold)
+            self.route = csr
+        else:
+            if self._m is None:
+                raise ValueError("trace routes live on a pool's device: bind the detector to a manager first")
+            self._m.pool.set_routes_from(source, src_env, windows, route_of, self.threshold)
+            self.route = source
+        if self._m is not None:
+            self._m._off_route_fresh = False
+
+    def _result(self):
+        if self.route is None:
+            raise ValueError("The route should be set before the event detection.")
+        m = self._m
+        if not m._off_route_fresh:   # (step() / check_status() launch it behind the step; otherwise: now)
+            m.pool.off_route()
+            m._off_route_fresh = True
+        return m.pool.off_route_all()
+
+    def update(self, ego_only=True):
+        """Reference: update(location) -> bool.  Batched: bool[n_env] for the ego of every scene (ego_only) or
+        bool[n_env, max_agents]; ValueError before reset."""
+        off = self._result()[1]
+        return off[:, self._m.ego_index] if ego_only else off
+
+    def distance(self, ego_only=True):
+        """float32 distance to the route behind the last verdict (NaN: not evaluated)."""
+        d = self._result()[0]
+        return d[:, self._m.ego_index] if ego_only else d
+
+
 class TimeExceed:
     """time_exceed.py:10-36; the counter lives in the pool (cnt_step per scene)."""
 
@@ -170,6 +264,16 @@ class BatchedScenarioManager:
             "off_lane": OffLane(self),
         }
         self._flags_cache = None
+        self.off_route = None          # an OffRoute detector bound to this manager (OffRoute(threshold, manager)), optional
+        self._off_route_fresh = False  # the pool's off-route buffers hold the verdict of the current state
+
+    def _after_step(self, stream):
+        """behind a step: the flags are new, and -- only when a route is installed -- one t2d_off_route launch on the same stream"""
+        self._flags_cache = None
+        self._off_route_fresh = False
+        if self.off_route is not None and self.off_route.installed:
+            self.pool.off_route(None, None, stream)
+            self._off_route_fresh = True
 
     # -- state views ----------------------------------------------------------------------------
     @property
@@ -204,6 +308,7 @@ class BatchedScenarioManager:
         self.pool.reset(x, y, heading, speed, type_id, active, env_mask=env_mask)
         self.pool.snapshot()
         self._flags_cache = None
+        self._off_route_fresh = False
         self._ego_velocity_derived = None   # (an env's ego model is fixed until the next reset: see get_observation)
 
     def update(self, act0, act1, stream=None):
@@ -211,11 +316,12 @@ class BatchedScenarioManager:
         self.pool.set_actions(act0, act1)
         self.pool.integrate(self.step_size, stream)
         self._flags_cache = None
+        self._off_route_fresh = False
 
     def check_status(self, stream=None):
         """Ordered event checks (parking.py:361-392) -> (scenario_status[E], traffic_status[E])."""
         self.pool.check_status(self.step_size, stream)
-        self._flags_cache = None
+        self._after_step(stream)
         st = self.pool.download(L.F_STATUS)
         return st[:, 0], st[:, 1]
 
@@ -224,7 +330,7 @@ class BatchedScenarioManager:
         if act0 is not None:
             self.pool.set_actions(act0, act1)
         self.pool.step(self.step_size, stream)
-        self._flags_cache = None
+        self._after_step(stream)
 
     def step_host(self, actions, lidar=False, fresh=True):
         """update + check_status for every scene, host to host, in ONE library call (t2d_step_host): `actions` float32
@@ -237,6 +343,7 @@ class BatchedScenarioManager:
             self._frame_cfg = want
         a = np.ascontiguousarray(actions, np.float32).reshape(self.n_env * self.max_agents, 2)
         self._flags_cache = None
+        self._off_route_fresh = False
         return self.pool.step_host(a, self.step_size, fresh=fresh)
 
     def render(self):
