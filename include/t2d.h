@@ -44,6 +44,8 @@
  *                            ParticipantBase._verify_trajectory  participant/element/participant_base.py:120-131
  *   t2d_set_routes* /     <- OffRoute.reset / update             traffic/event_detection/off_route.py:24-51
  *   t2d_off_route            Trajectory.get_trace (trace routes)  participant/trajectory/trajectory.py:151-168
+ *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
+ *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_step_host         <- ParkingEnv.step as its caller sees it: host action in, host 5-tuple out
  *                            envs/parking.py:219-256, _get_infos / _get_relative_pose :190-217
  *
@@ -710,6 +712,80 @@ int t2d_set_routes_from_traj(t2d_pool* pool, const t2d_traj* traj, int32_t n_slo
 int t2d_off_route(t2d_pool* pool, float* dist_out_dev, uint8_t* off_out_dev, void* hip_stream);
 int t2d_off_route_buffers(t2d_pool* pool, void** dist_dev, void** off_dev, size_t* n_elements);
 
+/* Racing tile progress -- _RacingScenarioManager._locate_agent (envs/racing.py:261-301), check_status (:339-369) and
+ * RacingEnv._get_rewards (:121-139) for every env in ONE launch behind the step launch.
+ *
+ * A TRACK is a ring of n_tile lane tiles, tile i's successor is (i + 1) % n_tile (what RacingTrackGenerator._get_tiles builds,
+ * map/generator/generate_racing_track.py:160-198), each tile four fp32 vertices in the order of Lane.geometry
+ * (map/element/lane.py:125-128: the left side, then the right side reversed).  Lane.geometry is a LinearRing, so the
+ * reference's `tile_shape.intersects(pose) or tile_shape.contains(pose)` is true exactly when one of the tile's four EDGES
+ * meets the closed box of the car: a car wholly inside a tile touches nothing.  The predicate is stated in
+ * tactics2d_amd/csrc/t2d_track_dev.h (fp64 from the fp32 inputs, one rounding per operation, the box = Vehicle.get_pose with
+ * the event kernels' expressions) and again in tests/track_ref.py; like every geometric predicate here it is pinned against
+ * exact rational arithmetic, not against GEOS.  It needs no convexity of the tile.  An ego that is inactive, not box-shaped
+ * or whose pose is not finite touches nothing (build-defined).
+ *
+ * The march (racing.py:271-288): starting at tile_visiting it walks the successors once round the ring, collects the FIRST
+ * contiguous run of touched tiles and stops at the first untouched tile after the run has begun.  With offsets counted from
+ * tile_visiting the run is [j0, j1).  If it is not empty, tile_visiting becomes its last tile, the run is marked visited,
+ * and so is the GAP in front of it, under one of two rules:
+ *   T2D_TRACK_RULE_REFERENCE  the reference exactly (racing.py:292-301): the gap loop starts at the successor of tile_visiting
+ *                             and stops at the first member of the run, i.e. offsets [1, j0) -- and when the run is
+ *                             [tile_visiting] alone it never meets a member until it has gone all the way round: EVERY tile is
+ *                             marked and the lap is complete (the reference's degenerate case, kept bit for bit; so does a car
+ *                             that touches only the tile behind it).  max_advance is ignored.
+ *   T2D_TRACK_RULE_FORWARD    BUILD-DEFINED: the same predicate and the same march, but (a) only tile_visiting and its first
+ *                             max_advance successors are looked at (0 = the whole ring), and (b) the gap is the tiles strictly
+ *                             between tile_visiting and the run's first tile -- empty when the run starts at tile_visiting or at
+ *                             its successor.  Nothing else differs.  With it a lap completes when the car has driven it.
+ *
+ * Status and reward, per env, from what the step launch left in T2D_F_STATUS / T2D_F_FLAGS / T2D_F_CNT_STEP (nothing is
+ * recomputed; the order of the first three checks is ParkingEnv's, so the pool's bytes already decide them; configure the pool
+ * with check_no_action = 1, no_action_max_step = 100 and no arrival for the reference's racing checklist), first match wins:
+ *   pool scenario TIME_EXCEEDED            -> scenario TIME_EXCEEDED (3), reward -1
+ *   pool traffic  T2D_TRAFFIC_NO_ACTION_QUIRK -> traffic 5 (racing.py:351 stores ScenarioStatus.NO_ACTION in traffic_status, so
+ *                                             _get_rewards gives this step the RUNNING reward, not -1), truncated
+ *   pool scenario OUT_BOUND                -> traffic 4 (racing.py:356 stores ScenarioStatus.OUT_BOUND there), reward -5
+ *   check_off_road and T2D_FLAG_OFF_LANE of the ego -> traffic T2D_TRAFFIC_OFF_LANE (6), reward -5.  BUILD-DEFINED: the
+ *                                             reference's OffLane.update is a stub and TrafficStatus.OFF_ROAD does not exist
+ *   every tile visited                     -> scenario COMPLETED, reward (n_tile - 0.1 cnt_step) / n_tile * 100, terminated
+ *   otherwise                              running reward -0.1 cnt_step + 0.1 num_visited
+ * in fp64 in the reference's order, stored as fp32; truncated = not terminated and (scenario != NORMAL or traffic != NORMAL).
+ *
+ *   t2d_set_tracks       n_sets tracks shared between envs, CSR like t2d_set_routes: tiles of track s are
+ *                        [set_tile_offsets[s], set_tile_offsets[s + 1]) of tiles_xy ([n_tile][4][2] fp32, host memory);
+ *                        3 <= n_tile <= T2D_MAX_TRACK_TILES (beyond: T2D_ERR_GEOMETRY; the visited mask is
+ *                        T2D_MAX_TRACK_TILES / 32 words per env); set_of_env[e] picks env e's track (NULL: track 0); ego_index =
+ *                        the agent that drives; rule, max_advance, check_off_road as above.  Every env starts as after
+ *                        t2d_track_reset.  n_sets = 0 or NULL offsets remove the tracks.
+ *   t2d_track_reset      envs with env_mask[e] != 0 (NULL: all): only tile 0 visited, tile_visiting = 0 (_reset_map,
+ *                        racing.py:303-312), status NORMAL.
+ *   t2d_track_upload     the same from the caller's values (an episode resumed in the middle of a lap): tile_visiting i32[E],
+ *                        mask u32[E][T2D_MAX_TRACK_TILES / 32] (bit t % 32 of word t / 32 = tile t); entries of unselected envs
+ *                        are ignored.  A tile_visiting outside the env's ring or mask bits beyond n_tile: T2D_ERR_INVALID.
+ *   t2d_track_progress   one launch, asynchronous on hip_stream.  Results go to buffers of the track's own
+ *                        (t2d_track_buffers: tile_visiting i32[E], num_visited i32[E], mask, status u8[E][4] in the layout of
+ *                        T2D_F_STATUS, reward f32[E]); write_status != 0 also stores status and reward into T2D_F_STATUS /
+ *                        T2D_F_REWARD, so that t2d_restore(pool, 1, stream) puts finished racing episodes back.  An env whose
+ *                        OWN status buffer says terminated or truncated from the previous launch starts this launch from the
+ *                        progress state t2d_track_reset / t2d_track_upload last gave it (the library keeps that copy as
+ *                        t2d_snapshot keeps the pool's), whatever write_status was.  kernel_id 10 in t2d_profile_read.  No
+ *                        stepping call launches it, it changes no other pool field, and t2d_set_auto_reset is not involved.
+ * Errors: T2D_ERR_INVALID for a null pool / array, n_tile < 3, non-monotone offsets, set_of_env / ego_index / rule out of
+ * range, max_advance < 0; T2D_ERR_GEOMETRY for a track beyond T2D_MAX_TRACK_TILES or a non-finite vertex; T2D_ERR_STATE for
+ * t2d_track_reset / _upload / _progress / _buffers without tracks and for t2d_track_progress without a parameter table or
+ * a t2d_reset.  A failing call leaves the installed tracks and their state as they were.                                   */
+#define T2D_MAX_TRACK_TILES 2048      /* tiles of one track: four times the largest ring the reference's generator was seen to make */
+#define T2D_TRACK_RULE_REFERENCE 0
+#define T2D_TRACK_RULE_FORWARD 1
+int t2d_set_tracks(t2d_pool* pool, int32_t n_sets, const int32_t* set_tile_offsets, const float* tiles_xy,
+                   const int32_t* set_of_env, int32_t ego_index, int32_t rule, int32_t max_advance, int32_t check_off_road);
+int t2d_track_reset(t2d_pool* pool, const uint8_t* env_mask);
+int t2d_track_upload(t2d_pool* pool, const uint8_t* env_mask, const int32_t* tile_visiting, const uint32_t* mask);
+int t2d_track_progress(t2d_pool* pool, int32_t write_status, void* hip_stream);
+int t2d_track_buffers(t2d_pool* pool, void** tile_visiting_dev, void** num_visited_dev, void** mask_dev, void** status_dev,
+                      void** reward_dev, size_t* n_env);
+
 /* Reset-time scene synthesis: ParkingLotGenerator.generate
  * (map/generator/generate_parking_lot.py:239-444) for n_env independent scenes, one lane per scene, on `device_id`.
  * PARITY UNPINNED against the reference: it draws from numpy's global MT19937 stream and evaluates its predicates in
@@ -786,7 +862,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel.
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
- * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route).       */
+ * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
+ * 10 = racing tile progress (t2d_track_progress).                                                                            */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -106,6 +106,11 @@ SYMBOLS = {
     "t2d_set_routes_from_traj": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "t2d_off_route": (C.c_int, [_vp, _vp, _vp, _vp]),
     "t2d_off_route_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "t2d_set_tracks": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "t2d_track_reset": (C.c_int, [_vp, _vp]),
+    "t2d_track_upload": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "t2d_track_progress": (C.c_int, [_vp, C.c_int32, _vp]),
+    "t2d_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 5 + [C.POINTER(C.c_size_t)]),
     "t2d_generate_parking": (C.c_int, [C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double]
                              + [_vp] * 8),
     "t2d_parking_scenes": (C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32]),

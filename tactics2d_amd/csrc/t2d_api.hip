@@ -544,6 +544,7 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
 
 static void replay_release(t2d_pool* p);   // (drops a replay binding: defined with t2d_replay_bind)
 static void route_release(t2d_pool* p);    // (drops the installed routes: defined with t2d_set_routes)
+static void track_release(t2d_pool* p);    // (drops the installed tracks: defined with t2d_set_tracks)
 
 int t2d_destroy(t2d_pool* p) {
     if (!p) return T2D_OK;
@@ -551,6 +552,7 @@ int t2d_destroy(t2d_pool* p) {
     (void)quiesce(p);  // nothing of this pool may still be running (incl. a scene refill on its own stream)
     replay_release(p);
     route_release(p);
+    track_release(p);
     for (void* b : {(void*)p->d_route_of, (void*)p->d_route_thr, (void*)p->d_route_dist, (void*)p->d_route_off})
         if (b) (void)hipFree(b);
     for (int f = 0; f < T2D_F_COUNT; ++f)
@@ -2798,6 +2800,197 @@ int t2d_off_route_buffers(t2d_pool* p, void** dist_dev, void** off_dev, size_t* 
     *dist_dev = p->d_route_dist;
     *off_dev = p->d_route_off;
     *n_elements = (size_t)p->v.N;
+    return T2D_OK;
+}
+
+// ---- racing tile progress (kernel: t2d_track.hip) ----------------------------------------------------------------------------
+static void track_release(t2d_pool* p) {
+    if (p->d_track) (void)hipFree(p->d_track);
+    p->d_track = nullptr;
+    p->track = t2d::TrackView{};
+    p->track_n_tile.clear();
+}
+
+namespace {
+constexpr int kTrackWords = T2D_MAX_TRACK_TILES / 32;
+// byte offsets of the sections of the one allocation behind a TrackView, each on a 256-byte boundary.  The per-env state
+// (visiting .. start_mask) is contiguous: t2d_track_reset / t2d_track_upload move it in one copy each way.
+struct TrackLayout {
+    size_t tiles, set_start, set_of_env, visiting, num_visited, mask, status, reward, start_visiting, start_mask, bytes;
+    TrackLayout(size_t n_tile, size_t n_sets, size_t E) {
+        size_t o = 0;
+        auto take = [&](size_t b) { const size_t at = o; o += (b + 255) & ~(size_t)255; return at; };
+        tiles = take(n_tile * 32); set_start = take((n_sets + 1) * 4); set_of_env = take(E * 4);
+        visiting = take(E * 4); num_visited = take(E * 4); mask = take(E * kTrackWords * 4); status = take(E * 4);
+        reward = take(E * 4); start_visiting = take(E * 4); start_mask = take(E * kTrackWords * 4);
+        bytes = o;
+    }
+};
+
+// the progress state of the selected envs <- (tile_visiting, mask) (null: tile 0, only tile 0 visited), in `buf` (a host image
+// of the allocation); their status goes back to NORMAL, their reward to 0, and the start copy follows
+void track_assign_host(char* buf, const TrackLayout& lay, int E, const uint8_t* env_mask, const int32_t* visiting, const uint32_t* mask) {
+    int32_t *v = (int32_t*)(buf + lay.visiting), *nv = (int32_t*)(buf + lay.num_visited), *sv = (int32_t*)(buf + lay.start_visiting);
+    uint32_t *m = (uint32_t*)(buf + lay.mask), *sm = (uint32_t*)(buf + lay.start_mask);
+    uint8_t* st = (uint8_t*)(buf + lay.status);
+    float* rw = (float*)(buf + lay.reward);
+    for (int e = 0; e < E; ++e) {
+        if (env_mask && !env_mask[e]) continue;
+        uint32_t* me = m + (size_t)e * kTrackWords;
+        int count = 0;
+        for (int w = 0; w < kTrackWords; ++w) {
+            me[w] = mask ? mask[(size_t)e * kTrackWords + w] : (w == 0 ? 1u : 0u);
+            count += __builtin_popcount(me[w]);
+        }
+        v[e] = visiting ? visiting[e] : 0;
+        nv[e] = count;
+        sv[e] = v[e];
+        memcpy(sm + (size_t)e * kTrackWords, me, kTrackWords * sizeof(uint32_t));
+        st[4 * e] = T2D_SCENARIO_NORMAL; st[4 * e + 1] = T2D_TRAFFIC_NORMAL; st[4 * e + 2] = 0; st[4 * e + 3] = 0;
+        rw[e] = 0.f;
+    }
+}
+
+int track_assign(t2d_pool* p, const char* who, const uint8_t* env_mask, const int32_t* visiting, const uint32_t* mask) {
+    if (!p->track.installed) return fail(p, T2D_ERR_STATE, std::string("t2d_set_tracks must precede ") + who);
+    const int E = p->v.n_env;
+    for (int e = 0; e < E; ++e) {
+        if (env_mask && !env_mask[e]) continue;
+        const int n = p->track_n_tile[e];
+        if (visiting && (visiting[e] < 0 || visiting[e] >= n))
+            return fail(p, T2D_ERR_INVALID, std::string(who) + ": tile_visiting[" + std::to_string(e) + "] = " + std::to_string(visiting[e]) +
+                                                " outside the env's ring [0, " + std::to_string(n) + ")");
+        if (mask)
+            for (int w = n / 32; w < kTrackWords; ++w) {
+                const uint32_t beyond = w == n / 32 ? ~((1u << (n & 31)) - 1u) : 0xffffffffu;
+                if (mask[(size_t)e * kTrackWords + w] & beyond)
+                    return fail(p, T2D_ERR_INVALID, std::string(who) + ": the mask of env " + std::to_string(e) + " has bits beyond its " +
+                                                        std::to_string(n) + " tiles");
+            }
+    }
+    T2D_HIP(p, hipSetDevice(p->device));
+    const TrackLayout lay(0, 0, (size_t)E);   // (only differences of the state sections' offsets are used)
+    const size_t bytes = lay.bytes - lay.visiting;
+    std::vector<char> img(lay.bytes);
+    char* dev = (char*)p->track.visiting;
+    T2D_HIP(p, quiesce(p));
+    T2D_HIP(p, hipMemcpy(img.data() + lay.visiting, dev, bytes, hipMemcpyDeviceToHost));
+    track_assign_host(img.data(), lay, E, env_mask, visiting, mask);
+    T2D_HIP(p, hipMemcpy(dev, img.data() + lay.visiting, bytes, hipMemcpyHostToDevice));
+    return T2D_OK;
+}
+}  // namespace
+
+int t2d_set_tracks(t2d_pool* p, int32_t n_sets, const int32_t* set_tile_offsets, const float* tiles_xy, const int32_t* set_of_env,
+                   int32_t ego_index, int32_t rule, int32_t max_advance, int32_t check_off_road) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (n_sets < 0) return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: n_sets must be >= 0");
+    if (n_sets == 0 || !set_tile_offsets) {
+        T2D_HIP(p, quiesce(p));
+        track_release(p);
+        return T2D_OK;
+    }
+    if (!tiles_xy) return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: null tiles_xy");
+    const int E = p->v.n_env;
+    if (ego_index < 0 || ego_index >= p->v.A)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: ego_index " + std::to_string(ego_index) + " outside [0, max_agents)");
+    if (rule != T2D_TRACK_RULE_REFERENCE && rule != T2D_TRACK_RULE_FORWARD)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: unknown rule " + std::to_string(rule));
+    if (max_advance < 0) return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: max_advance must be >= 0 (0 = the whole ring)");
+    if (set_tile_offsets[0] != 0) return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: offsets must start at 0");
+    for (int s = 0; s < n_sets; ++s) {
+        const int64_t n = (int64_t)set_tile_offsets[s + 1] - set_tile_offsets[s];
+        if (n < 3)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: track " + std::to_string(s) + " has " + std::to_string(n) +
+                                                " tiles (a ring needs at least three; offsets must increase)");
+        if (n > T2D_MAX_TRACK_TILES)
+            return fail(p, T2D_ERR_GEOMETRY, "t2d_set_tracks: track " + std::to_string(s) + " has " + std::to_string(n) +
+                                                 " tiles, more than T2D_MAX_TRACK_TILES = " + std::to_string(T2D_MAX_TRACK_TILES));
+    }
+    const int n_tile = set_tile_offsets[n_sets];
+    for (size_t k = 0; k < (size_t)n_tile * 8; ++k)
+        if (!__builtin_isfinite(tiles_xy[k])) return fail(p, T2D_ERR_GEOMETRY, "t2d_set_tracks: non-finite vertex in tile " + std::to_string(k / 8));
+    std::vector<int32_t> n_of_env(E);
+    for (int e = 0; e < E; ++e) {
+        const int s = set_of_env ? set_of_env[e] : 0;
+        if (s < 0 || s >= n_sets)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_tracks: set_of_env[" + std::to_string(e) + "] = " + std::to_string(s) +
+                                                " outside [0, " + std::to_string(n_sets) + ")");
+        n_of_env[e] = set_tile_offsets[s + 1] - set_tile_offsets[s];
+    }
+    const TrackLayout lay((size_t)n_tile, (size_t)n_sets, (size_t)E);
+    std::vector<char> img(lay.bytes);
+    memcpy(img.data() + lay.tiles, tiles_xy, (size_t)n_tile * 32);
+    memcpy(img.data() + lay.set_start, set_tile_offsets, (size_t)(n_sets + 1) * sizeof(int32_t));
+    for (int e = 0; e < E; ++e) ((int32_t*)(img.data() + lay.set_of_env))[e] = set_of_env ? set_of_env[e] : 0;
+    track_assign_host(img.data(), lay, E, nullptr, nullptr, nullptr);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, lay.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(p, T2D_ERR_NOMEM, "t2d_set_tracks: " + std::to_string(lay.bytes) + " bytes of device memory");
+    }
+    hipError_t he = quiesce(p);   // (a progress launch that still reads the previous tracks)
+    if (he == hipSuccess) he = hipMemcpy(d, img.data(), lay.bytes, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipFree(d);
+        return fail(p, T2D_ERR_HIP, std::string("t2d_set_tracks: ") + hipGetErrorString(he));
+    }
+    track_release(p);   // nothing can fail from here on
+    p->d_track = d;
+    p->track_n_tile = std::move(n_of_env);
+    t2d::TrackView& tv = p->track;
+    tv.installed = 1; tv.ego_index = ego_index; tv.rule = rule; tv.max_advance = max_advance; tv.check_off_road = check_off_road != 0;
+    tv.tiles = (const float*)(d + lay.tiles);
+    tv.set_start = (const int32_t*)(d + lay.set_start);
+    tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
+    tv.visiting = (int32_t*)(d + lay.visiting);
+    tv.num_visited = (int32_t*)(d + lay.num_visited);
+    tv.mask = (uint32_t*)(d + lay.mask);
+    tv.status = (uint8_t*)(d + lay.status);
+    tv.reward = (float*)(d + lay.reward);
+    tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
+    tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+    return T2D_OK;
+}
+
+int t2d_track_reset(t2d_pool* p, const uint8_t* env_mask) {
+    if (!p) return T2D_ERR_INVALID;
+    return track_assign(p, "t2d_track_reset", env_mask, nullptr, nullptr);
+}
+
+int t2d_track_upload(t2d_pool* p, const uint8_t* env_mask, const int32_t* tile_visiting, const uint32_t* mask) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!tile_visiting || !mask) return fail(p, T2D_ERR_INVALID, "t2d_track_upload: null tile_visiting / mask");
+    return track_assign(p, "t2d_track_upload", env_mask, tile_visiting, mask);
+}
+
+int t2d_track_progress(t2d_pool* p, int32_t write_status, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->track.installed) return fail(p, T2D_ERR_STATE, "t2d_set_tracks must precede t2d_track_progress");
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_track_progress");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, 10, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_track_progress(p->v, p->track, write_status != 0, s));
+    return record_event(p, 10, s, false);
+}
+
+int t2d_track_buffers(t2d_pool* p, void** tile_visiting_dev, void** num_visited_dev, void** mask_dev, void** status_dev,
+                      void** reward_dev, size_t* n_env) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!tile_visiting_dev || !num_visited_dev || !mask_dev || !status_dev || !reward_dev || !n_env)
+        return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->track.installed) return fail(p, T2D_ERR_STATE, "t2d_set_tracks must precede t2d_track_buffers");
+    *tile_visiting_dev = p->track.visiting;
+    *num_visited_dev = p->track.num_visited;
+    *mask_dev = p->track.mask;
+    *status_dev = p->track.status;
+    *reward_dev = p->track.reward;
+    *n_env = (size_t)p->v.n_env;
     return T2D_OK;
 }
 

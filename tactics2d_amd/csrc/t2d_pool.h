@@ -266,6 +266,21 @@ struct RouteView {
     int32_t log2_group;              // traces: 1 << log2_group lanes per participant (0: one lane each)
 };
 
+// Racing tile progress (t2d_track.hip): the installed track sets, the per-env progress state and the copy of it that
+// t2d_track_reset / t2d_track_upload last gave each env (where an env whose episode ended starts again).
+struct TrackView {
+    int32_t installed, ego_index, rule, max_advance, check_off_road, pad;
+    const float* tiles;            // [n_tile of all sets][4][2] ring vertices, 32-byte records
+    const int32_t* set_start;      // [n_sets + 1] first tile of each set
+    const int32_t* set_of_env;     // [E]
+    int32_t *visiting, *num_visited;   // [E]
+    uint32_t* mask;                // [E][T2D_MAX_TRACK_TILES / 32] bit t of an env: tile t visited
+    uint8_t* status;               // [E][4] in the layout of T2D_F_STATUS
+    float* reward;                 // [E]
+    const int32_t* start_visiting; // [E]
+    const uint32_t* start_mask;    // [E][T2D_MAX_TRACK_TILES / 32]
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -350,6 +365,10 @@ struct t2d_pool {
     float* d_route_dist = nullptr;
     uint8_t* d_route_off = nullptr;
     std::vector<int32_t> route_limit;       // [E] exclusive upper bound of route_of in env e (routes of its set / max_agents)
+    // racing tile progress (t2d_set_tracks): one allocation behind every pointer of the view; n_tile of each env's track
+    t2d::TrackView track{};
+    void* d_track = nullptr;
+    std::vector<int32_t> track_n_tile;      // [E]
     float* d_snap_omega[2]{};
     // IDM agents (row f3)
     bool idm_on = false;
@@ -462,6 +481,8 @@ hipError_t launch_verify_states(const PoolView& v, const float* buf, int capacit
 hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hipStream_t s);
 // off-route detector (t2d_route.hip): distance (f32) and verdict (u8) of every participant against its route
 hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s);
+// racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
+hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

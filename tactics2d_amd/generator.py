@@ -103,3 +103,191 @@ class ParkingLotGenerator:
             self.vehicle_size[1], ptr(out.quads), ptr(out.quad_id), ptr(out.n_quads), ptr(out.start), ptr(out.target),
             ptr(out.target_heading), ptr(out.boundary), ptr(out.info)))
         return out
+
+
+# ------------------------------------------------------------------------------------------------------- racing tracks
+@dataclass
+class RacingTrack:
+    """One generated track.  tiles float64 [n_tile, 4, 2]: tile i's ring in the order of Lane.geometry (left side, then the
+    right side reversed: left[i], left[i + 1], right[i + 1], right[i]); tile i's successor is (i + 1) % n_tile.
+    start_line float64 [2, 2] = tile 0's ends, end_line = its starts, center_line float64 [m, 2]; start_point the
+    customs["start_state"] location; n_checkpoint the number of turns."""
+    tiles: np.ndarray
+    start_line: np.ndarray
+    end_line: np.ndarray
+    center_line: np.ndarray
+    start_point: np.ndarray
+    n_checkpoint: int
+
+    @property
+    def n_tile(self):
+        return len(self.tiles)
+
+    def start_pose(self, length=VEHICLE_TEMPLATE["medium_car"][0]):
+        """_reset_agent (envs/racing.py:314-326): (x, y, heading) of the car, its nose on the start line"""
+        vec = self.start_line[1] - self.start_line[0]
+        heading = np.arctan2(vec[0], -vec[1])
+        loc = np.mean(self.start_line, axis=0)
+        loc -= length / 2 / np.linalg.norm(vec) * np.array([-vec[1], vec[0]])
+        return float(loc[0]), float(loc[1]), float(heading)
+
+
+def _circle_radius(p1, p2, p3):
+    """radius of the circle through three points, by the perpendicular bisectors (geometry/cpp_geometry/src/circle.cpp:3-33)"""
+    a = p1[0] - p2[0]; b = p1[1] - p2[1]; c = p1[0] - p3[0]; d = p1[1] - p3[1]
+    e = (p1[0] * p1[0] - p2[0] * p2[0] + p1[1] * p1[1] - p2[1] * p2[1]) / 2.0
+    f = (p1[0] * p1[0] - p3[0] * p3[0] + p1[1] * p1[1] - p3[1] * p3[1]) / 2.0
+    denom = a * d - b * c
+    if abs(denom) < 1e-10:
+        raise RuntimeError("Cannot define a unique circle: points are collinear")
+    cx = (e * d - b * f) / denom
+    cy = (a * f - e * c) / denom
+    dx = p1[0] - cx; dy = p1[1] - cy
+    return np.sqrt(dx * dx + dy * dy)
+
+
+def _bezier2(p0, p1, p2, n):
+    """n points of the order-2 Bezier curve, Bernstein form, accumulated control point by control point
+    (interpolator/cpp_interpolator/src/bezier.cpp): float64 [n, 2]"""
+    t = np.arange(n) * (1.0 / (n - 1))
+    u = 1.0 - t
+    w0 = 1.0 * (u * u) * 1.0
+    w1 = 2.0 * u * t
+    w2 = 1.0 * 1.0 * (t * t)
+    out = np.zeros((n, 2))
+    for w, p in ((w0, p0), (w1, p1), (w2, p2)):
+        out[:, 0] += w * p[0]
+        out[:, 1] += w * p[1]
+    return out
+
+
+class _Polyline:
+    """LineString.length / interpolate of the reference's shapely calls: segment lengths sqrt(dx dx + dy dy) summed in order;
+    the point at distance d lies on the first segment whose end is beyond d, at p0 + frac (p1 - p0) with
+    frac = (d - length before) / segment length; d <= 0 gives the first point, d beyond the end the last."""
+
+    def __init__(self, pts):
+        self.p = np.asarray(pts, np.float64)
+        d = np.diff(self.p, axis=0)
+        self.seg = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+        total, before = 0.0, []
+        for s in self.seg.tolist():          # (a running sum in segment order, not a pairwise one)
+            before.append(total)
+            total += s
+        self.before, self.length = before, total
+        self._k = 0
+
+    def interpolate(self, dist):
+        if dist <= 0.0:
+            return self.p[0].copy()
+        k = self._k if self.before[self._k] <= dist else 0      # (distances are asked for in increasing order)
+        while k < len(self.seg):
+            if self.before[k] + self.seg[k] > dist:
+                self._k = k
+                frac = (dist - self.before[k]) / self.seg[k]
+                p0, p1 = self.p[k], self.p[k + 1]
+                return np.array([p0[0] + frac * (p1[0] - p0[0]), p0[1] + frac * (p1[1] - p0[1])])
+            k += 1
+        return self.p[-1].copy()
+
+
+class RacingTrackGenerator:
+    """Host-side restatement of `tactics2d.map.generator.RacingTrackGenerator` (map/generator/generate_racing_track.py):
+    checkpoints on a circle of radius 800 m with their rejection loop, the three-point circle, order-2 Bezier turns of 50
+    points, the start point, the centre line and the tiles of `_get_tiles`.  It consumes numpy's GLOBAL random stream draw
+    for draw, as the reference does: `np.random.seed(s)` before `generate()` gives the track the reference generates after the
+    same seed (tests/golden/racing_tracks.npz).  Set-up code: there is no kernel here."""
+
+    _n_checkpoint = (10, 20)
+    _track_width = 5
+    _track_rad = 800
+    _curve_rad = (50, 150)
+    _tile_length = 10
+
+    def __init__(self, bezier_order=2, bezier_interpolation=50, max_tiles=L.MAX_TRACK_TILES):
+        if bezier_order != 2:
+            raise NotImplementedError("only the order-2 curves RacingEnv uses are restated")
+        self._bezier_interpolation = int(bezier_interpolation)
+        self.max_tiles = int(max_tiles)
+
+    def _get_checkpoints(self):
+        rnd = np.random
+        n = rnd.randint(*self._n_checkpoint)
+        noise = rnd.uniform(0, 2 * np.pi / n, n)
+        alpha = 2 * np.pi * np.arange(n) / n + noise
+        rad = rnd.uniform(self._track_rad / 5, self._track_rad, n)
+        cp = np.array([rad * np.cos(alpha), rad * np.sin(alpha)])
+        control, success = [], False
+        for _ in range(100):
+            control, glued = [], 0
+            for i in range(n):
+                nxt = 0 if i + 1 == n else i + 1
+                pt1, pt2, pt3 = cp[:, i - 1], cp[:, i], cp[:, nxt]
+                t1 = rnd.uniform(low=1 / 4, high=1 / 2)
+                t2 = rnd.uniform(low=1 / 4, high=1 / 2)
+                a = (1 - t1) * pt2 + t1 * pt1
+                b = (1 - t2) * pt2 + t2 * pt3
+                radius = _circle_radius(a, pt2, b)
+                if radius < self._curve_rad[0] or radius > self._curve_rad[1]:
+                    # too sharp: push the next checkpoint away from this one's radius and on; too wide: the other way
+                    sign = 1.0 if radius < self._curve_rad[0] else -1.0
+                    step = rnd.uniform(0.0, 10.0)
+                    rad[nxt] += sign * step if rad[i] > rad[nxt] else -sign * step
+                    alpha[nxt] += sign * rnd.uniform(0.0, 0.05)
+                    cp[:, nxt] = [rad[nxt] * np.cos(alpha[nxt]), rad[nxt] * np.sin(alpha[nxt])]
+                else:
+                    glued += 1
+                    control.append([a, b])
+            if glued == n:
+                success = True
+                break
+        success = success and all(alpha == sorted(alpha))
+        return cp, control, success
+
+    def _get_start_point(self, n, control):
+        # (the reference measures each straight by np.linalg.norm of the 2 x 2 array of its two end points -- the Frobenius
+        # norm of their coordinates, not their distance; kept, since the choice of the start straight follows from it)
+        lens = [np.linalg.norm([control[i][0], control[i - 1][1]]) for i in range(n)]
+        order = sorted(range(n), key=lambda i: lens[i], reverse=True)
+        start_id = None
+        for i in range(3):
+            start_id = order[i]
+            if lens[start_id] < 200:
+                break
+        line = _Polyline([control[start_id][0], control[start_id - 1][1]])
+        return line.interpolate(lens[start_id] / 3), start_id
+
+    def _get_center_line(self, start_point, start_id, cp, control):
+        pts = [start_point[None]]
+        for i in range(cp.shape[1]):
+            k = start_id - i - 1
+            pts.append(_bezier2(control[k][1], cp[:, k], control[k][0], self._bezier_interpolation))
+        pts.append(start_point[None])
+        return np.concatenate(pts)
+
+    def _get_tiles(self, n_tile, line):
+        c = np.array([line.interpolate(self._tile_length * i) for i in range(n_tile)])
+        prev = np.roll(c, 1, axis=0)
+        xd, yd = c[:, 0] - prev[:, 0], c[:, 1] - prev[:, 1]
+        k = np.array([self._track_width / 2 / np.linalg.norm([a, b]) for a, b in zip(xd.tolist(), yd.tolist())])
+        left = np.stack([c[:, 0] - k * yd, c[:, 1] + k * xd], 1)
+        right = np.stack([c[:, 0] + k * yd, c[:, 1] - k * xd], 1)
+        ln, rn = np.roll(left, -1, axis=0), np.roll(right, -1, axis=0)
+        return np.stack([left, ln, rn, right], 1)
+
+    def generate(self):
+        """One track from numpy's global random stream -> RacingTrack (fp64, the reference's coordinates)."""
+        success = False
+        while not success:
+            cp, control, success = self._get_checkpoints()
+        n = cp.shape[1]
+        start_point, start_id = self._get_start_point(n, control)
+        center = self._get_center_line(start_point, start_id, cp, control)
+        line = _Polyline(center)
+        n_tile = int(np.ceil(line.length / self._tile_length))
+        if n_tile > self.max_tiles:
+            raise ValueError(f"the generated track has {n_tile} tiles, more than the {self.max_tiles} a track may hold "
+                             "(T2D_MAX_TRACK_TILES)")
+        tiles = self._get_tiles(n_tile, line)
+        return RacingTrack(tiles, np.array([tiles[0, 1], tiles[0, 2]]), np.array([tiles[0, 0], tiles[0, 3]]), center,
+                           start_point, n)

@@ -42,6 +42,10 @@ MAX_POLY_VERTS = 8
 MAX_AGENTS = 256
 MAX_ROUTE_SET_VERTS = 4096   # T2D_MAX_ROUTE_SET_VERTS: vertices of one route set (t2d_set_routes)
 PROFILE_OFF_ROUTE = 9        # kernel id of t2d_off_route in t2d_profile_read
+MAX_TRACK_TILES = 2048       # T2D_MAX_TRACK_TILES: tiles of one racing track (t2d_set_tracks); the visited mask is 64 words per env
+TRACK_MASK_WORDS = MAX_TRACK_TILES // 32
+TRACK_RULE_REFERENCE, TRACK_RULE_FORWARD = 0, 1   # T2D_TRACK_RULE_*
+PROFILE_TRACK_PROGRESS = 10  # kernel id of t2d_track_progress in t2d_profile_read
 # IDM controller parameter sets (t2d_set_idm)
 IDM_DESIRED_SPEED, IDM_TIME_HEADWAY, IDM_MIN_SPACING, IDM_MAX_ACCEL, IDM_COMF_DECEL, IDM_DELTA = range(6)
 IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7

@@ -24,6 +24,22 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def pack_track_mask(visited):
+    """bool [n_env, <= MAX_TRACK_TILES] -> uint32 [n_env, TRACK_MASK_WORDS]: bit t % 32 of word t // 32 = tile t"""
+    v = np.asarray(visited, bool)
+    if v.ndim != 2 or v.shape[1] > L.MAX_TRACK_TILES:
+        raise ValueError(f"visited: bool [n_env, <= {L.MAX_TRACK_TILES}]")
+    full = np.zeros((v.shape[0], L.MAX_TRACK_TILES), bool)
+    full[:, :v.shape[1]] = v
+    return np.ascontiguousarray(np.packbits(full, axis=1, bitorder="little")).view("<u4")
+
+
+def unpack_track_mask(mask, n_tile=None):
+    """uint32 [n_env, TRACK_MASK_WORDS] -> bool [n_env, n_tile or MAX_TRACK_TILES]"""
+    m = np.ascontiguousarray(mask, "<u4")
+    return np.unpackbits(m.view(np.uint8), axis=1, bitorder="little")[:, :n_tile].astype(bool)
+
+
 class _DevArray:
     """Zero-copy view of a pool field for `torch.as_tensor(..., device='cuda')`."""
 
@@ -405,6 +421,81 @@ class ParticipantPool:
         """off_route() into the pool's own buffers + off_route_all()."""
         self.off_route(None, None, stream)
         return self.off_route_all()
+
+    # ---------------------------------------------------------------- racing tile progress
+    def set_tracks(self, tracks, set_of_env=None, ego_index=0, rule="forward", max_advance=8, check_off_road=False):
+        """Install racing tracks (t2d_set_tracks).  tracks: a list of float32 [n_tile, 4, 2] arrays -- the tiles of each track
+        in ring order, tile i's successor is (i + 1) % n_tile, vertices in the order of Lane.geometry -- shared between envs;
+        set_of_env int32[n_env]: the track each env drives on (None: track 0); ego_index: the agent that drives;
+        rule: "reference" (the reference's march and gap filling, degenerate case included) or "forward" (build-defined: only
+        max_advance successors of tile_visiting are looked at, 0 = the whole ring, and only the tiles strictly between
+        tile_visiting and the touched run are filled); check_off_road: the ego's off-lane flag ends the episode (traffic
+        status 6, reward -5; build-defined).  Every env starts as after track_reset().  None removes the tracks."""
+        if tracks is None:
+            self._ck(self._lib.t2d_set_tracks(self._h, 0, None, None, None, 0, 0, 0, 0))
+            self.track_n_tile = None
+            return
+        rules = {"reference": L.TRACK_RULE_REFERENCE, "forward": L.TRACK_RULE_FORWARD}
+        if rule not in rules:
+            raise ValueError(f"unknown progress rule {rule!r}")
+        tiles = [np.ascontiguousarray(t, np.float32).reshape(-1, 4, 2) for t in tracks]
+        off = np.concatenate([[0], np.cumsum([len(t) for t in tiles])]).astype(np.int32)
+        xy = np.ascontiguousarray(np.concatenate(tiles) if tiles else np.zeros((0, 4, 2), np.float32))
+        se = _arr(set_of_env, np.int32, self.n_env, "set_of_env")
+        self._ck(self._lib.t2d_set_tracks(self._h, len(tiles), _p(off), _p(xy), _p(se), int(ego_index), rules[rule],
+                                          int(max_advance), int(bool(check_off_road))))
+        n = np.diff(off)
+        self.track_n_tile = (n[se] if se is not None else np.full(self.n_env, n[0])).astype(np.int32)
+
+    def _track_env_mask(self, env_mask):
+        return None if env_mask is None else _arr(np.asarray(env_mask, bool), np.uint8, self.n_env, "env_mask")
+
+    def track_reset(self, env_mask=None):
+        """_reset_map (envs/racing.py:303-312) for the selected envs (None: all): only tile 0 visited, tile_visiting = 0."""
+        self._ck(self._lib.t2d_track_reset(self._h, _p(self._track_env_mask(env_mask))))
+
+    def set_track_state(self, tile_visiting, visited, env_mask=None):
+        """The progress state of the selected envs from the caller's values (t2d_track_upload): tile_visiting int32[n_env];
+        visited bool [n_env, <= MAX_TRACK_TILES] (tile t of env e) or the packed uint32 [n_env, TRACK_MASK_WORDS] mask."""
+        tv = _arr(tile_visiting, np.int32, self.n_env, "tile_visiting")
+        v = np.asarray(visited)
+        if v.dtype != np.uint32:
+            v = pack_track_mask(v)
+        m = _arr(v, np.uint32, self.n_env * L.TRACK_MASK_WORDS, "visited mask")
+        self._ck(self._lib.t2d_track_upload(self._h, _p(self._track_env_mask(env_mask)), _p(tv), _p(m)))
+
+    def track_progress(self, write_status=False, stream=None):
+        """_locate_agent + check_status + _get_rewards of the racing env for every env in one launch (t2d_track_progress),
+        asynchronous on `stream`, from the state and the status bytes the last step left.  write_status: status and reward also
+        go to the pool's own fields (restore(1) then puts finished episodes back)."""
+        self._ck(self._lib.t2d_track_progress(self._h, int(bool(write_status)), stream))
+
+    def track_buffers(self):
+        """Device pointers of the progress results: dict(tile_visiting, num_visited, mask, status, reward)."""
+        ptrs = [C.c_void_p() for _ in range(5)]
+        n = C.c_size_t()
+        self._ck(self._lib.t2d_track_buffers(self._h, *[C.byref(q) for q in ptrs], C.byref(n)))
+        return dict(zip(("tile_visiting", "num_visited", "mask", "status", "reward"), (q.value for q in ptrs)))
+
+    def track_views(self):
+        """Zero-copy torch views of track_buffers() (valid until set_tracks / close)."""
+        import torch
+        b, E, dev = self.track_buffers(), self.n_env, f"cuda:{self.device_id}"
+        shapes = dict(tile_visiting=((E,), "<i4"), num_visited=((E,), "<i4"), mask=((E, L.TRACK_MASK_WORDS), "<u4"),
+                      status=((E, 4), "|u1"), reward=((E,), "<f4"))
+        # (torch has no uint32 everywhere: the mask is viewed as int32, same bits)
+        out = {}
+        for k, (shape, ts) in shapes.items():
+            out[k] = torch.as_tensor(_DevArray(b[k], shape, "<i4" if ts == "<u4" else ts, self), device=dev)
+        return out
+
+    def track_state(self):
+        """The progress results as numpy, after the pool's work: dict(tile_visiting int32[n_env], num_visited int32[n_env],
+        mask uint32[n_env, TRACK_MASK_WORDS], status uint8[n_env, 4], reward float32[n_env])."""
+        self.sync()
+        out = {k: v.cpu().numpy() for k, v in self.track_views().items()}
+        out["mask"] = out["mask"].view(np.uint32)
+        return out
 
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):
