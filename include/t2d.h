@@ -786,6 +786,79 @@ int t2d_track_progress(t2d_pool* pool, int32_t write_status, void* hip_stream);
 int t2d_track_buffers(t2d_pool* pool, void** tile_visiting_dev, void** num_visited_dev, void** mask_dev, void** status_dev,
                       void** reward_dev, size_t* n_env);
 
+/* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
+ * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
+ *
+ * What the reference defines, and this follows (sensor/camera.py, renderer/matplotlib_renderer.py, matplotlib_config.py):
+ *   view window   _calculate_bounds: x in [sx - left, sx + right], y in [sy - back, sy + front] around the sensor ("front" is
+ *                 +y of the view); auto_scale then widens the short side, about the centre, to the image's aspect ratio
+ *                 height / width.
+ *   transform     _transform_to_camera_view: v = R(+camera_yaw) (p - sensor) + sensor.  heading_up != 0 takes camera_yaw =
+ *                 pi / 2 - heading of the bound participant (it points to the front); heading_up = 0 is north-up, camera_yaw = 0.
+ *   style         _resolve_style gives every class its colour and z-order; elements of equal z are drawn in the order
+ *                 BEVCamera lists them: areas (the parking target, then the obstacles), lanes, then the participants by slot,
+ *                 each body followed by its heading triangle (midpoints of edges 0-1, 1-2 and 3-0 of the body ring).  A
+ *                 pedestrian (T2D_SHAPE_CIRCLE) is a disc of radius width / 2 and has no triangle.  Inactive participants are
+ *                 not listed.  The defaults below are the reference's resolved values for its envs' objects: a `medium_car`
+ *                 Vehicle and an `adult_male` Pedestrian resolve to z-order 1 (their type names are not in DEFAULT_ORDER), so a
+ *                 car's body is drawn UNDER the lane it drives on and only its heading triangle (z 7) shows there.
+ *   culling       _in_perception_range (distance <= 1.5 x the largest range) never changes a pixel: the farthest corner of
+ *                 the window is at most sqrt(2) x the largest range from the sensor.  Not implemented.
+ * BUILD-DEFINED, the raster: the image is exactly the view window; pixel (row r, col c) of the height x width image is the
+ * class of the topmost element that contains the CENTRE of the pixel; row 0 is at the front edge.  Containment is even-odd
+ * crossing on the caller's undivided ring (racing tiles may be non-convex), dx^2 + dy^2 <= r^2 for discs.  No anti-aliasing,
+ * no outline strokes; road lines (whose widths are in points) are not drawn.  fp32 throughout: a pixel whose centre is
+ * within about 1e-4 m of an edge may fall on either side.  A bound participant whose pose is not finite gives an all-
+ * background image.
+ *
+ *   t2d_camera_config      width x height pixels (each 1 .. T2D_CAMERA_MAX_SIDE), the perception range (left, right, front,
+ *                          back; metres, finite, left + right > 0, front + back > 0), bind_slot = the participant slot the
+ *                          camera follows, heading_up, layers = T2D_CAMERA_LAYER_* bits, format = T2D_CAMERA_FORMAT_CLASS,
+ *                          _RGB or both (| T2D_CAMERA_FORMAT_NAIVE: the measurement yardstick in which every pixel tests
+ *                          every element; same image).  Allocates the library's own images.  width = 0 removes the camera.
+ *   t2d_camera_set_palette rgb u8[n_class][3], n_class <= T2D_CAMERA_N_CLASS: the colour of classes 0 .. n_class - 1.
+ *   t2d_camera_set_style   class_of_type u8[T2D_MAX_TYPES] (NULL: T2D_SHAPE_OBB rows are vehicles, T2D_SHAPE_CIRCLE rows
+ *                          pedestrians; T2D_CAMERA_CLASS_BACKGROUND = participants of that row are not drawn, what the
+ *                          reference does with an `Obstacle` participant) and z_of_class u8[T2D_CAMERA_N_CLASS] (NULL: the
+ *                          defaults), 1 .. 255.
+ *   t2d_camera_render      one launch, asynchronous on hip_stream, of the pool's current state.  out_class_dev / out_rgb_dev:
+ *                          device memory u8[n_env][height][width] / u8[n_env][height][width][3], 4-byte aligned; with both
+ *                          NULL the configured formats go to the library's own images.  kernel_id 11 in t2d_profile_read.  No
+ *                          stepping call launches it and it changes no pool field.
+ *   t2d_camera_buffers     the library's own images (NULL for a format that was not configured) and their sizes in bytes.
+ * Errors: T2D_ERR_INVALID for a null pool, a size / range / slot / layer / format / class out of range; T2D_ERR_STATE for
+ * t2d_camera_set_palette / _set_style / _render / _buffers without a configured camera, for t2d_camera_render without a
+ * parameter table or a t2d_reset, and for a rendered layer whose geometry was never set (T2D_CAMERA_LAYER_STATIC without
+ * static geometry or generated scenes, _LANES without lane geometry, _TRACKS without t2d_set_tracks, _TARGET without target
+ * areas); T2D_ERR_NOMEM when the images cannot be allocated.                                                                 */
+#define T2D_CAMERA_MAX_SIDE 4096
+#define T2D_CAMERA_LAYER_STATIC 1
+#define T2D_CAMERA_LAYER_LANES 2
+#define T2D_CAMERA_LAYER_TRACKS 4
+#define T2D_CAMERA_LAYER_TARGET 8
+#define T2D_CAMERA_LAYER_PARTICIPANTS 16
+#define T2D_CAMERA_LAYER_ARROWS 32      /* the heading triangles (needs T2D_CAMERA_LAYER_PARTICIPANTS) */
+#define T2D_CAMERA_LAYER_ALL 63
+#define T2D_CAMERA_FORMAT_CLASS 1
+#define T2D_CAMERA_FORMAT_RGB 2
+#define T2D_CAMERA_FORMAT_NAIVE 4
+#define T2D_CAMERA_CLASS_BACKGROUND 0   /* the figure's white (255, 255, 255) */
+#define T2D_CAMERA_CLASS_LANE 1         /* z 3, (47, 53, 66) */
+#define T2D_CAMERA_CLASS_OBSTACLE 2     /* z 5, (178, 190, 195) */
+#define T2D_CAMERA_CLASS_TARGET 3       /* z 1, (238, 118, 110) */
+#define T2D_CAMERA_CLASS_VEHICLE 4      /* z 1, (43, 203, 186) */
+#define T2D_CAMERA_CLASS_CYCLIST 5      /* z 6, (253, 150, 68) */
+#define T2D_CAMERA_CLASS_PEDESTRIAN 6   /* z 1, (69, 170, 242) */
+#define T2D_CAMERA_CLASS_HEADING_ARROW 7 /* z 7, (47, 53, 66) */
+#define T2D_CAMERA_N_CLASS 8
+#define T2D_PROFILE_CAMERA 11
+int t2d_camera_config(t2d_pool* pool, int32_t width, int32_t height, float left, float right, float front, float back,
+                      int32_t bind_slot, int32_t heading_up, uint32_t layers, uint32_t format);
+int t2d_camera_set_palette(t2d_pool* pool, const uint8_t* rgb, int32_t n_class);
+int t2d_camera_set_style(t2d_pool* pool, const uint8_t* class_of_type, const uint8_t* z_of_class);
+int t2d_camera_render(t2d_pool* pool, void* out_class_dev, void* out_rgb_dev, void* hip_stream);
+int t2d_camera_buffers(t2d_pool* pool, void** class_dev, void** rgb_dev, size_t* class_bytes, size_t* rgb_bytes);
+
 /* Reset-time scene synthesis: ParkingLotGenerator.generate
  * (map/generator/generate_parking_lot.py:239-444) for n_env independent scenes, one lane per scene, on `device_id`.
  * PARITY UNPINNED against the reference: it draws from numpy's global MT19937 stream and evaluates its predicates in
@@ -863,7 +936,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel.
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
- * 10 = racing tile progress (t2d_track_progress).                                                                            */
+ * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render).                                       */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

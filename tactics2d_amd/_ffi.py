@@ -111,6 +111,12 @@ SYMBOLS = {
     "t2d_track_upload": (C.c_int, [_vp, _vp, _vp, _vp]),
     "t2d_track_progress": (C.c_int, [_vp, C.c_int32, _vp]),
     "t2d_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 5 + [C.POINTER(C.c_size_t)]),
+    "t2d_camera_config": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                    C.c_uint32, C.c_uint32]),
+    "t2d_camera_set_palette": (C.c_int, [_vp, _vp, C.c_int32]),
+    "t2d_camera_set_style": (C.c_int, [_vp, _vp, _vp]),
+    "t2d_camera_render": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "t2d_camera_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "t2d_generate_parking": (C.c_int, [C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double]
                              + [_vp] * 8),
     "t2d_parking_scenes": (C.c_int, [_vp, C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32]),

@@ -545,6 +545,7 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
 static void replay_release(t2d_pool* p);   // (drops a replay binding: defined with t2d_replay_bind)
 static void route_release(t2d_pool* p);    // (drops the installed routes: defined with t2d_set_routes)
 static void track_release(t2d_pool* p);    // (drops the installed tracks: defined with t2d_set_tracks)
+static void camera_release(t2d_pool* p);   // (drops the camera: defined with t2d_camera_config)
 
 int t2d_destroy(t2d_pool* p) {
     if (!p) return T2D_OK;
@@ -553,6 +554,7 @@ int t2d_destroy(t2d_pool* p) {
     replay_release(p);
     route_release(p);
     track_release(p);
+    camera_release(p);
     for (void* b : {(void*)p->d_route_of, (void*)p->d_route_thr, (void*)p->d_route_dist, (void*)p->d_route_off})
         if (b) (void)hipFree(b);
     for (int f = 0; f < T2D_F_COUNT; ++f)
@@ -656,6 +658,7 @@ int t2d_set_static_geometry(t2d_pool* p, const int32_t* env_poly_offsets,
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
+    ++p->geo_gen;
     const int E = p->v.n_env;
     int rc;
     if (p->scene_mode) {  // host-described geometry replaces the generated scenes
@@ -690,6 +693,7 @@ int t2d_set_lane_geometry(t2d_pool* p, const int32_t* env_lane_offsets,
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
+    ++p->geo_gen;
     const int E = p->v.n_env;
     int rc;
     if (p->scene_mode) return fail(p, T2D_ERR_STATE, "lane geometry cannot be combined with generated parking scenes");
@@ -1489,6 +1493,7 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     if (type_proportion > 1.0) type_proportion = 1.0;
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
+    ++p->geo_gen;
     const int E = p->v.n_env;
     constexpr int K = T2D_GEN_MAX_QUADS;
     int rc;
@@ -2991,6 +2996,218 @@ int t2d_track_buffers(t2d_pool* p, void** tile_visiting_dev, void** num_visited_
     *status_dev = p->track.status;
     *reward_dev = p->track.reward;
     *n_env = (size_t)p->v.n_env;
+    return T2D_OK;
+}
+
+// ---- BEV camera (kernel: t2d_camera.hip) ---------------------------------------------------------------------------------------
+static void camera_release(t2d_pool* p) {
+    for (void* b : {(void*)p->d_cam_class, (void*)p->d_cam_rgb, p->d_cam_geo})
+        if (b) (void)hipFree(b);
+    p->d_cam_class = p->d_cam_rgb = nullptr;
+    p->d_cam_geo = nullptr;
+    p->camera = t2d::CameraView{};
+    p->cam_geo_gen = -1;
+    p->cam_type_default = true;
+}
+
+namespace {
+// the reference's resolved style of the classes (renderer/matplotlib_config.py through _resolve_style; pinned by
+// tests/golden/camera_style.json)
+constexpr uint8_t kCamRgb[T2D_CAMERA_N_CLASS][3] = {{255, 255, 255}, {47, 53, 66}, {178, 190, 195}, {238, 118, 110},
+                                                    {43, 203, 186}, {253, 150, 68}, {69, 170, 242}, {47, 53, 66}};
+constexpr uint8_t kCamZ[T2D_CAMERA_N_CLASS] = {0, 3, 5, 1, 1, 6, 1, 7};
+
+// the camera's device copy of the caller's rings, from the host copies the lidar's edge list is made of as well: per kind
+// env_poly_off [E + 1] | poly_vert_off [P + 1] | xy [V][2], one allocation, remade when the geometry has changed
+int camera_refresh_geo(t2d_pool* p) {
+    if (p->cam_geo_gen == p->geo_gen) return T2D_OK;
+    const int E = p->v.n_env;
+    size_t off[2][3], total = 0;
+    bool have[2];
+    auto take = [&](size_t b) { const size_t at = total; total += (b + 255) & ~(size_t)255; return at; };
+    for (int k = 0; k < 2; ++k) {
+        const auto& g = p->hgeo[k];
+        have[k] = g.present && !p->scene_mode && (int)g.ring_env_off.size() == E + 1;
+        if (!have[k]) continue;
+        off[k][0] = take(g.ring_env_off.size() * 4);
+        off[k][1] = take(g.ring_vert_off.size() * 4);
+        off[k][2] = take(g.ring_xy.size() * 4 + 4);
+    }
+    char* d = nullptr;
+    if (total) {
+        std::vector<char> img(total);
+        for (int k = 0; k < 2; ++k) {
+            if (!have[k]) continue;
+            const auto& g = p->hgeo[k];
+            memcpy(img.data() + off[k][0], g.ring_env_off.data(), g.ring_env_off.size() * 4);
+            memcpy(img.data() + off[k][1], g.ring_vert_off.data(), g.ring_vert_off.size() * 4);
+            if (!g.ring_xy.empty()) memcpy(img.data() + off[k][2], g.ring_xy.data(), g.ring_xy.size() * 4);
+        }
+        if (hipMalloc((void**)&d, total) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(p, T2D_ERR_NOMEM, "t2d_camera_render: " + std::to_string(total) + " bytes of device memory for the rings");
+        }
+        hipError_t he = quiesce(p);   // (a render that still reads the previous copy)
+        if (he == hipSuccess) he = hipMemcpy(d, img.data(), total, hipMemcpyHostToDevice);
+        if (he != hipSuccess) {
+            (void)hipFree(d);
+            return fail(p, T2D_ERR_HIP, std::string("t2d_camera_render: ") + hipGetErrorString(he));
+        }
+    } else {
+        T2D_HIP(p, quiesce(p));
+    }
+    if (p->d_cam_geo) (void)hipFree(p->d_cam_geo);
+    p->d_cam_geo = d;
+    for (int k = 0; k < 2; ++k) {
+        p->camera.env_poly_off[k] = have[k] ? (const int32_t*)(d + off[k][0]) : nullptr;
+        p->camera.poly_vert_off[k] = have[k] ? (const int32_t*)(d + off[k][1]) : nullptr;
+        p->camera.poly_xy[k] = have[k] ? (const float*)(d + off[k][2]) : nullptr;
+    }
+    p->cam_geo_gen = p->geo_gen;
+    return T2D_OK;
+}
+}  // namespace
+
+int t2d_camera_config(t2d_pool* p, int32_t width, int32_t height, float left, float right, float front, float back,
+                      int32_t bind_slot, int32_t heading_up, uint32_t layers, uint32_t format) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (width == 0) {
+        T2D_HIP(p, quiesce(p));
+        camera_release(p);
+        return T2D_OK;
+    }
+    if (width < 1 || width > T2D_CAMERA_MAX_SIDE || height < 1 || height > T2D_CAMERA_MAX_SIDE)
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_config: width and height must be in 1 .. " + std::to_string(T2D_CAMERA_MAX_SIDE));
+    if (!__builtin_isfinite(left) || !__builtin_isfinite(right) || !__builtin_isfinite(front) || !__builtin_isfinite(back) ||
+        !(left + right > 0.f) || !(front + back > 0.f))
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_config: the perception range must be finite with left + right > 0 and front + back > 0");
+    if (bind_slot < 0 || bind_slot >= p->v.A)
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_config: bind_slot " + std::to_string(bind_slot) + " outside [0, max_agents)");
+    if (layers == 0 || (layers & ~(uint32_t)T2D_CAMERA_LAYER_ALL)) return fail(p, T2D_ERR_INVALID, "t2d_camera_config: unknown layer bit, or no layer");
+    const uint32_t fmt = format & ~(uint32_t)T2D_CAMERA_FORMAT_NAIVE;
+    if (fmt == 0 || (fmt & ~(uint32_t)(T2D_CAMERA_FORMAT_CLASS | T2D_CAMERA_FORMAT_RGB)))
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_config: format must be T2D_CAMERA_FORMAT_CLASS, _RGB or both");
+    const size_t px = (size_t)width * height, blocks = (size_t)((width + 63) / 64) * ((height + 15) / 16);
+    if (px * p->v.n_env * 3 > ((size_t)1 << 36) || blocks * p->v.n_env > 0x7fffffffull)
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_config: images too large for this pool");
+    uint8_t *dc = nullptr, *dr = nullptr;
+    if (fmt & T2D_CAMERA_FORMAT_CLASS)
+        if (hipMalloc((void**)&dc, px * p->v.n_env) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(px * p->v.n_env) + " bytes of device memory");
+        }
+    if (fmt & T2D_CAMERA_FORMAT_RGB)
+        if (hipMalloc((void**)&dr, 3 * px * p->v.n_env) != hipSuccess) {
+            (void)hipGetLastError();
+            if (dc) (void)hipFree(dc);
+            return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(3 * px * p->v.n_env) + " bytes of device memory");
+        }
+    const hipError_t he = quiesce(p);   // (a render into the previous images)
+    if (he != hipSuccess) {
+        if (dc) (void)hipFree(dc);
+        if (dr) (void)hipFree(dr);
+        return fail(p, T2D_ERR_HIP, std::string("t2d_camera_config: ") + hipGetErrorString(he));
+    }
+    t2d::CameraView& cv = p->camera;
+    const bool fresh = !cv.configured;
+    if (p->d_cam_class) (void)hipFree(p->d_cam_class);
+    if (p->d_cam_rgb) (void)hipFree(p->d_cam_rgb);
+    p->d_cam_class = dc;
+    p->d_cam_rgb = dr;
+    // the window: _calculate_bounds, then auto_scale widens the short side about the centre (matplotlib_renderer.py:137-232),
+    // here as offsets from the sensor
+    double x0 = -(double)left, x1 = (double)right, y0 = -(double)back, y1 = (double)front;
+    const double ww = x1 - x0, wh = y1 - y0, cx = (x0 + x1) / 2, cy = (y0 + y1) / 2;
+    const double res_aspect = (double)height / (double)width;
+    double nw, nh;
+    if (wh / ww > res_aspect) { nw = wh / res_aspect; nh = wh; }
+    else { nw = ww; nh = ww * res_aspect; }
+    x0 = cx - nw / 2; y1 = cy + nh / 2;
+    cv.configured = 1; cv.width = width; cv.height = height; cv.bind_slot = bind_slot; cv.heading_up = heading_up != 0;
+    cv.layers = layers; cv.format = format;
+    cv.ux0 = (float)x0; cv.uy1 = (float)y1; cv.px_w = (float)(nw / width); cv.px_h = (float)(nh / height);
+    if (fresh) {   // (a camera that is configured again keeps its palette and style)
+        for (int c = 0; c < T2D_CAMERA_N_CLASS; ++c) {
+            cv.palette[c] = (uint32_t)kCamRgb[c][0] | (uint32_t)kCamRgb[c][1] << 8 | (uint32_t)kCamRgb[c][2] << 16;
+            cv.z_of_class[c] = kCamZ[c];
+        }
+        p->cam_type_default = true;
+    }
+    return T2D_OK;
+}
+
+int t2d_camera_set_palette(t2d_pool* p, const uint8_t* rgb, int32_t n_class) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->camera.configured) return fail(p, T2D_ERR_STATE, "t2d_camera_config must precede t2d_camera_set_palette");
+    if (!rgb || n_class < 1 || n_class > T2D_CAMERA_N_CLASS)
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_set_palette: null rgb, or n_class outside 1 .. T2D_CAMERA_N_CLASS");
+    for (int c = 0; c < n_class; ++c)
+        p->camera.palette[c] = (uint32_t)rgb[3 * c] | (uint32_t)rgb[3 * c + 1] << 8 | (uint32_t)rgb[3 * c + 2] << 16;
+    return T2D_OK;
+}
+
+int t2d_camera_set_style(t2d_pool* p, const uint8_t* class_of_type, const uint8_t* z_of_class) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->camera.configured) return fail(p, T2D_ERR_STATE, "t2d_camera_config must precede t2d_camera_set_style");
+    if (class_of_type)
+        for (int t = 0; t < T2D_MAX_TYPES; ++t)
+            if (class_of_type[t] != T2D_CAMERA_CLASS_BACKGROUND && (class_of_type[t] < T2D_CAMERA_CLASS_VEHICLE || class_of_type[t] > T2D_CAMERA_CLASS_PEDESTRIAN))
+                return fail(p, T2D_ERR_INVALID, "t2d_camera_set_style: class_of_type[" + std::to_string(t) + "] is not a participant class");
+    if (z_of_class)
+        for (int c = 1; c < T2D_CAMERA_N_CLASS; ++c)
+            if (z_of_class[c] == 0) return fail(p, T2D_ERR_INVALID, "t2d_camera_set_style: z-orders must be in 1 .. 255");
+    if (class_of_type) memcpy(p->camera.class_of_type, class_of_type, T2D_MAX_TYPES);
+    p->cam_type_default = class_of_type == nullptr;
+    for (int c = 1; c < T2D_CAMERA_N_CLASS; ++c) p->camera.z_of_class[c] = z_of_class ? z_of_class[c] : kCamZ[c];
+    return T2D_OK;
+}
+
+int t2d_camera_render(t2d_pool* p, void* out_class_dev, void* out_rgb_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    t2d::CameraView& cv = p->camera;
+    if (!cv.configured) return fail(p, T2D_ERR_STATE, "t2d_camera_config must precede t2d_camera_render");
+    if (!p->have_params || !p->have_reset)
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_camera_render");
+    if (((uintptr_t)out_class_dev | (uintptr_t)out_rgb_dev) & 3)
+        return fail(p, T2D_ERR_INVALID, "t2d_camera_render: the images must be 4-byte aligned");
+    if ((cv.layers & T2D_CAMERA_LAYER_STATIC) && !p->scene_mode && !p->hgeo[0].present)
+        return fail(p, T2D_ERR_STATE, "t2d_camera_render: T2D_CAMERA_LAYER_STATIC without static geometry or generated scenes");
+    if ((cv.layers & T2D_CAMERA_LAYER_LANES) && !p->hgeo[1].present)
+        return fail(p, T2D_ERR_STATE, "t2d_camera_render: T2D_CAMERA_LAYER_LANES without lane geometry");
+    if ((cv.layers & T2D_CAMERA_LAYER_TRACKS) && !p->track.installed)
+        return fail(p, T2D_ERR_STATE, "t2d_camera_render: T2D_CAMERA_LAYER_TRACKS without t2d_set_tracks");
+    if ((cv.layers & T2D_CAMERA_LAYER_TARGET) && !p->have_target)
+        return fail(p, T2D_ERR_STATE, "t2d_camera_render: T2D_CAMERA_LAYER_TARGET without target areas");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    int rc;
+    if ((rc = camera_refresh_geo(p))) return rc;
+    if (p->scene_mode) {
+        cv.scene_quads = p->scene.live.quads; cv.scene_quad_id = p->scene.live.quad_id; cv.scene_n_quads = p->scene.live.n_quads;
+    } else {
+        cv.scene_quads = nullptr; cv.scene_quad_id = nullptr; cv.scene_n_quads = nullptr;
+    }
+    if (p->cam_type_default)
+        for (int t = 0; t < T2D_MAX_TYPES; ++t)
+            cv.class_of_type[t] = (int)p->host_params[t][T2D_P_SHAPE] == T2D_SHAPE_CIRCLE ? T2D_CAMERA_CLASS_PEDESTRIAN : T2D_CAMERA_CLASS_VEHICLE;
+    uint8_t *oc = (uint8_t*)out_class_dev, *orgb = (uint8_t*)out_rgb_dev;
+    if (!oc && !orgb) { oc = p->d_cam_class; orgb = p->d_cam_rgb; }
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_CAMERA, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_camera(p->v, cv, p->track, oc, orgb, (cv.format & T2D_CAMERA_FORMAT_NAIVE) != 0, s));
+    return record_event(p, T2D_PROFILE_CAMERA, s, false);
+}
+
+int t2d_camera_buffers(t2d_pool* p, void** class_dev, void** rgb_dev, size_t* class_bytes, size_t* rgb_bytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!class_dev || !rgb_dev || !class_bytes || !rgb_bytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->camera.configured) return fail(p, T2D_ERR_STATE, "t2d_camera_config must precede t2d_camera_buffers");
+    const size_t px = (size_t)p->camera.width * p->camera.height * p->v.n_env;
+    *class_dev = p->d_cam_class;
+    *rgb_dev = p->d_cam_rgb;
+    *class_bytes = p->d_cam_class ? px : 0;
+    *rgb_bytes = p->d_cam_rgb ? 3 * px : 0;
     return T2D_OK;
 }
 

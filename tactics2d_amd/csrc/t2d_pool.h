@@ -281,6 +281,22 @@ struct TrackView {
     const uint32_t* start_mask;    // [E][T2D_MAX_TRACK_TILES / 32]
 };
 
+// BEV camera (t2d_camera.hip): the window, the style tables and the camera's own device copy of the caller's static and lane
+// rings (kind 0 / 1; undivided, as the lidar scans them) -- or, in scene mode, the generated scenes' live quads.
+struct CameraView {
+    int32_t configured, width, height, bind_slot, heading_up;
+    uint32_t layers, format;
+    float ux0, uy1, px_w, px_h;          // camera frame, offsets from the sensor: left edge, front edge; pixel size (m)
+    const int32_t* env_poly_off[2];      // [E + 1] or null
+    const int32_t* poly_vert_off[2];     // [P + 1]
+    const float* poly_xy[2];             // [V][2]
+    const float* scene_quads;            // scene mode: [E][T2D_GEN_MAX_QUADS][4][2], else null
+    const int32_t *scene_quad_id, *scene_n_quads;
+    uint32_t palette[T2D_CAMERA_N_CLASS];   // r | g << 8 | b << 16
+    uint8_t z_of_class[T2D_CAMERA_N_CLASS];
+    uint8_t class_of_type[T2D_MAX_TYPES];
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -369,6 +385,13 @@ struct t2d_pool {
     t2d::TrackView track{};
     void* d_track = nullptr;
     std::vector<int32_t> track_n_tile;      // [E]
+    // BEV camera (t2d_camera_config): the view, the library's own images, the device copy of the rings (one allocation) and
+    // the geometry generation it was made of (geo_gen counts every change of the host rings / the scene mode)
+    t2d::CameraView camera{};
+    uint8_t *d_cam_class = nullptr, *d_cam_rgb = nullptr;
+    void* d_cam_geo = nullptr;
+    long long geo_gen = 0, cam_geo_gen = -1;
+    bool cam_type_default = true;   // class_of_type follows the parameter table's shapes
     float* d_snap_omega[2]{};
     // IDM agents (row f3)
     bool idm_on = false;
@@ -483,6 +506,9 @@ hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hi
 hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s);
 // racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
 hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
+// BEV camera (t2d_camera.hip): the class and / or RGB image of every env (null: not written); naive = every pixel tests every element
+hipError_t launch_camera(const PoolView& v, const CameraView& cv, const TrackView& tv, uint8_t* out_class, uint8_t* out_rgb, int naive,
+                         hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

@@ -7,8 +7,10 @@ the accelerated path: `step()` = physics update of the ego (`_ParkingScenarioMan
 :148-166).  `Arrival` (IoU >= 0.95 with the target bay -> COMPLETED, +5, terminated), `NoAction` (IoU with the
 previous pose > 0.999 on more than 100 checks, including the reference's quirk of reporting it in
 `traffic_status`) and the IoU / distance reward shaping are evaluated in the same launch.  `info["lidar"]` is the 360-beam / 20 m
-SingleLineLidar scan of the same poses (t2d_lidar_scan).  The rendered camera image is not on the
-accelerated path: the observation returned here is the ego state vector.
+SingleLineLidar scan of the same poses (t2d_lidar_scan).  observation="state" (the default) returns the ego state vector;
+observation="camera" returns the reference's declared observation, the (200, 200, 3) uint8 top-down image of the camera
+bound to the agent (tactics2d_amd.sensor.BEVCamera, one launch behind the step).  Windows, matplotlib and
+the WebGL viewer (`render()`) stay outside the accelerated path.
 
 gymnasium is not a dependency: `Box` below is the minimal stand-in for `spaces.Box`.
 """
@@ -46,6 +48,19 @@ class Box:
         return rng.uniform(self.low, self.high, size).astype(self.dtype)
 
 
+CAMERA_WINDOW = (200, 200)   # Box(0, 255, (200, 200, 3), uint8): envs/racing.py:102, envs/parking.py:130
+
+
+def _camera_space():
+    return Box(np.zeros(CAMERA_WINDOW[::-1] + (3,)), np.full(CAMERA_WINDOW[::-1] + (3,), 255), np.uint8)
+
+
+def _check_observation(observation):
+    if observation not in ("state", "camera"):
+        raise ValueError(f"unknown observation {observation!r}")
+    return observation
+
+
 class VecParkingEnv:
     """n_envs independent ParkingEnv scenes stepped by one t2d_step per call.
 
@@ -57,7 +72,8 @@ class VecParkingEnv:
     _discrete_actions = {1: (0, 0), 2: (-0.5, 0), 3: (0.5, 0), 4: (0, 1), 5: (0, -1)}  # parking.py:95
 
     def __init__(self, n_envs, max_step=int(2e4), continuous=True, auto_reset=False, seed=0, device_id=0,
-                 scene_source="layout", type_proportion=0.5, info_lidar=True, copy=True, zero_copy=None, lidar_beams=360):
+                 scene_source="layout", type_proportion=0.5, info_lidar=True, copy=True, zero_copy=None, lidar_beams=360,
+                 observation="state"):
         """scene_source: "generator" = the device-side ParkingLotGenerator (tactics2d_amd.generator; bay and
         parallel scenes with the reference's rejection sampler, `type_proportion` as in envs/parking.py:331-333),
         "layout" = the fixed bay layout of scenarios.parking (BASELINE config 2).
@@ -72,7 +88,11 @@ class VecParkingEnv:
         (envs/parking.py:303-304): the scan is then exactly `full_scan[:, ::360 // lidar_beams]` -- the tutorial policy keeps
         every third beam (docs/tutorial/train_parking_demo.ipynb), i.e. lidar_beams=120 moves a third of the bytes.  zero_copy: the kernels read the actions from / write
         the frame to mapped host memory instead of copy commands (None = for pools of at most 16384 envs; beyond, the
-        8 B per env of the actions would cross PCIe inside the step kernel)."""
+        8 B per env of the actions would cross PCIe inside the step kernel).
+        observation: "state" = the ego's 6-vector; "camera" = the reference's observation, the uint8 [200, 200, 3] image of a
+        BEVCamera with perception_range (20, 20, 20, 20) bound to the agent (envs/parking.py:130, :306-308): reset() and step()
+        return [n_envs, 200, 200, 3] arrays (downloaded: 120 KB per env), step_torch() adds `image` / `image_class`."""
+        self.observation = _check_observation(observation)
         if scene_source not in ("layout", "generator"):
             raise ValueError(f"unknown scene_source {scene_source!r}")
         self.scene_source = scene_source
@@ -91,7 +111,8 @@ class VecParkingEnv:
         if self.lidar_beams < 1 or 360 % self.lidar_beams:
             raise ValueError("lidar_beams must divide 360 (a regular subset of the reference's scan)")
         self.zero_copy = self.n_envs <= 16384 if zero_copy is None else bool(zero_copy)
-        self.observation_space = Box(np.full(6, -np.inf), np.full(6, np.inf))
+        self.observation_space = _camera_space() if self.observation == "camera" else Box(np.full(6, -np.inf), np.full(6, np.inf))
+        self.camera = None
         self.action_space = Box([-self._max_steer, -self._max_accel], [self._max_steer, self._max_accel])
         lo, hi = self.action_space.low, self.action_space.high
         self._action_box = np.float32([lo[0], hi[0], lo[1], hi[1]]) if continuous else None
@@ -143,6 +164,11 @@ class VecParkingEnv:
         self._target_area, self._target_heading = self._scene.target, self._scene.target_heading
         fr = m.pool.frame_fetch(fresh=self.copy)
         fr = self._last = fr.copy() if self.copy_always else fr
+        if self.observation == "camera":
+            from .sensor import BEVCamera
+            # BEVCamera(perception_range=(20, 20, 20, 20)) bound to the agent  envs/parking.py:306-308
+            self.camera = BEVCamera(m.pool, (20, 20, 20, 20), CAMERA_WINDOW, 0, True, ("static", "target", "participants", "arrows"))
+            return self.camera.render_numpy()["image"], self._infos(fr)
         return fr.obs, self._infos(fr)
 
     @property
@@ -180,7 +206,8 @@ class VecParkingEnv:
                 raise InvalidAction(f"Action {actions} is not in the action space.") from None
             raise
         self.scenario_manager._flags_cache = None
-        return fr.obs, fr.reward, fr.terminated, fr.truncated, self._infos(fr)
+        obs = self.camera.render_numpy()["image"] if self.observation == "camera" else fr.obs
+        return obs, fr.reward, fr.terminated, fr.truncated, self._infos(fr)
 
     def step_torch(self, actions, stream=None):
         """The device-resident step: `actions` is a float32 CUDA tensor [n_envs, 2] in the reference's layout (steering,
@@ -188,8 +215,9 @@ class VecParkingEnv:
         ZERO-COPY VIEWS of the pool (valid until the next step): state [6 x n_envs] columns (vx, vy as written by the ego's
         SingleTrackKinematics -- a dynamics / drift ego leaves those two fields alone, include/t2d.h), reward, status (u8 [n, 4]:
         scenario, traffic, terminated, truncated), iou, and `lidar` [n_envs, lidar_beams] written by the scan kernel straight
-        into a tensor owned by this env -- the observation buffer handed back to the policy.  Out-of-range actions are
-        the caller's responsibility here (the numpy `step` raises InvalidAction like the reference)."""
+        into a tensor owned by this env -- the observation buffer handed back to the policy.  With observation="camera":
+        `image` u8 [n, 200, 200, 3] and `image_class` u8 [n, 200, 200], rendered on the same stream behind the step.
+        Out-of-range actions are the caller's responsibility here (the numpy `step` raises InvalidAction like the reference)."""
         import torch
         if self._scene is None:
             raise RuntimeError("call reset() first")
@@ -215,8 +243,10 @@ class VecParkingEnv:
                                      vx=view(L.F_VX), vy=view(L.F_VY), reward=view(L.F_REWARD), status=view(L.F_STATUS),
                                      iou=view(L.F_IOU))
             pool.lidar_scan(self._t_lidar.data_ptr(), st.cuda_stream)
+            cam = self.camera.render(st.cuda_stream) if self.observation == "camera" else {}
         out = dict(self._t_views)
         out["lidar"] = self._t_lidar
+        out.update(cam)   # image, image_class: the poses (and, with regenerated scenes, the lots) the returned state shows
         return out
 
     def _infos(self, fr):
@@ -251,8 +281,11 @@ class VecRacingEnv:
 
     step(actions[n_envs, 2]) -> (obs[n_envs, 6], reward[n_envs], terminated[n_envs], truncated[n_envs], infos); the action
     layout is the reference's: (steering in +-0.5, accel in -4 .. 2), or an index into its 11 x 13 discrete table
-    (racing.py:111-115).  The observation is the ego state vector, as in VecParkingEnv (the camera image is not on the
-    accelerated path).  infos carries tile_visiting, num_visited_tile and num_tile beside the state and the two statuses.
+    (racing.py:111-115).  observation="state" (the default): the ego state vector, as in VecParkingEnv; observation="camera":
+    the reference's observation, the uint8 [200, 200, 3] image of a BEVCamera with perception_range (30, 30, 50, 10) bound to
+    the agent (racing.py:102, :234-236) -- obs is then [n_envs, 200, 200, 3] (downloaded by reset() / step(); step_torch() hands
+    out `image` / `image_class` as views, rendered behind the progress / restore launches, so after an auto-reset the image
+    shows the start pose the returned state shows).  infos carries tile_visiting, num_visited_tile and num_tile beside the state and the two statuses.
 
     n_tracks distinct tracks are generated per reset() (tactics2d_amd.generator.RacingTrackGenerator, numpy's global random
     stream as in the reference; seeded with `seed` at the first reset and whenever reset(seed=...) names one); env e drives
@@ -272,7 +305,9 @@ class VecRacingEnv:
     _max_steer, _max_accel, _min_accel = 0.5, 2.0, -4.0   # envs/racing.py:24-26
 
     def __init__(self, n_envs, max_step=int(1e5), continuous=True, auto_reset=False, seed=0, n_tracks=1,
-                 progress_rule="forward", max_advance=8, check_off_road=False, device_id=0):
+                 progress_rule="forward", max_advance=8, check_off_road=False, device_id=0, observation="state"):
+        self.observation = _check_observation(observation)
+        self.camera = None
         if progress_rule not in ("forward", "reference"):
             raise ValueError(f"unknown progress_rule {progress_rule!r}")
         if not 1 <= int(n_tracks) <= int(n_envs):
@@ -281,7 +316,7 @@ class VecRacingEnv:
         self.n_tracks, self.progress_rule, self.max_advance = int(n_tracks), progress_rule, int(max_advance)
         self.check_off_road = bool(check_off_road)
         self.device_id = device_id
-        self.observation_space = Box(np.full(6, -np.inf), np.full(6, np.inf))
+        self.observation_space = _camera_space() if self.observation == "camera" else Box(np.full(6, -np.inf), np.full(6, np.inf))
         self.action_space = Box([-self._max_steer, self._min_accel], [self._max_steer, self._max_accel])
         xx, yy = np.meshgrid(np.linspace(-self._max_steer, self._max_steer, 11), np.linspace(self._min_accel, self._max_accel, 13))
         self._discrete_action = np.vstack([xx.ravel(), yy.ravel()]).T     # racing.py:111-115
@@ -348,7 +383,13 @@ class VecRacingEnv:
         self.num_tile = m.pool.track_n_tile
         obs = m.get_observation()
         st = np.tile(np.uint8([1, 1, 0, 0]), (E, 1))
-        return obs, self._infos(obs, st, np.zeros(E, np.int32), np.ones(E, np.int32))
+        infos = self._infos(obs, st, np.zeros(E, np.int32), np.ones(E, np.int32))
+        if self.observation == "camera":
+            from .sensor import BEVCamera
+            # BEVCamera(perception_range=(30, 30, 50, 10)) bound to the agent  envs/racing.py:234-236
+            self.camera = BEVCamera(m.pool, (30, 30, 50, 10), CAMERA_WINDOW, 0, True, ("tracks", "participants", "arrows"))
+            obs = self.camera.render_numpy()["image"]
+        return obs, infos
 
     def _infos(self, obs, st, visiting, n_visited):
         return dict(state=dict(x=obs[:, 0], y=obs[:, 1], heading=obs[:, 2], speed=obs[:, 3], vx=obs[:, 4], vy=obs[:, 5]),
@@ -392,15 +433,17 @@ class VecRacingEnv:
         ts = m.pool.track_state()
         obs = m.get_observation()
         st = ts["status"]
-        return obs, ts["reward"], st[:, 2].astype(bool), st[:, 3].astype(bool), \
-            self._infos(obs, st, ts["tile_visiting"], ts["num_visited"])
+        infos = self._infos(obs, st, ts["tile_visiting"], ts["num_visited"])
+        if self.observation == "camera":
+            obs = self.camera.render_numpy()["image"]
+        return obs, ts["reward"], st[:, 2].astype(bool), st[:, 3].astype(bool), infos
 
     def step_torch(self, actions, stream=None):
         """The device-resident step: `actions` is a float32 CUDA tensor [n_envs, 2] (steering, accel), read in place; step
         launch -> progress launch (-> t2d_restore of finished episodes with auto_reset), nothing is copied to the host and
         nothing synchronises.  Returns a dict of torch tensors that are ZERO-COPY VIEWS (valid until the next step / reset):
         x, y, heading, speed, vx, vy, reward, status (u8 [n, 4]: scenario, traffic, terminated, truncated), tile_visiting,
-        num_visited.  Out-of-range actions are the caller's responsibility here."""
+        num_visited -- and with observation="camera" image (u8 [n, 200, 200, 3]) and image_class (u8 [n, 200, 200]).  Out-of-range actions are the caller's responsibility here."""
         import torch
         if self.tracks is None:
             raise RuntimeError("call reset() first")
@@ -426,8 +469,11 @@ class VecRacingEnv:
                 self._t_views = dict(x=view(L.F_X), y=view(L.F_Y), heading=view(L.F_HEADING), speed=view(L.F_SPEED),
                                      vx=view(L.F_VX), vy=view(L.F_VY), reward=tv["reward"], status=tv["status"],
                                      tile_visiting=tv["tile_visiting"], num_visited=tv["num_visited"])
+            cam = self.camera.render(st.cuda_stream) if self.observation == "camera" else {}
         self.scenario_manager._flags_cache = None
-        return dict(self._t_views)
+        out = dict(self._t_views)
+        out.update(cam)
+        return out
 
     def render(self):
         raise NotImplementedError("rendering is outside the accelerated path")

@@ -46,6 +46,15 @@ MAX_TRACK_TILES = 2048       # T2D_MAX_TRACK_TILES: tiles of one racing track (t
 TRACK_MASK_WORDS = MAX_TRACK_TILES // 32
 TRACK_RULE_REFERENCE, TRACK_RULE_FORWARD = 0, 1   # T2D_TRACK_RULE_*
 PROFILE_TRACK_PROGRESS = 10  # kernel id of t2d_track_progress in t2d_profile_read
+# BEV camera (t2d_camera_config): layer bits, formats, classes
+CAMERA_MAX_SIDE = 4096
+CAMERA_LAYER_STATIC, CAMERA_LAYER_LANES, CAMERA_LAYER_TRACKS, CAMERA_LAYER_TARGET = 1, 2, 4, 8
+CAMERA_LAYER_PARTICIPANTS, CAMERA_LAYER_ARROWS, CAMERA_LAYER_ALL = 16, 32, 63
+CAMERA_FORMAT_CLASS, CAMERA_FORMAT_RGB, CAMERA_FORMAT_NAIVE = 1, 2, 4
+CAMERA_CLASS_BACKGROUND, CAMERA_CLASS_LANE, CAMERA_CLASS_OBSTACLE, CAMERA_CLASS_TARGET = 0, 1, 2, 3
+CAMERA_CLASS_VEHICLE, CAMERA_CLASS_CYCLIST, CAMERA_CLASS_PEDESTRIAN, CAMERA_CLASS_HEADING_ARROW = 4, 5, 6, 7
+CAMERA_N_CLASS = 8
+PROFILE_CAMERA = 11          # kernel id of t2d_camera_render in t2d_profile_read
 # IDM controller parameter sets (t2d_set_idm)
 IDM_DESIRED_SPEED, IDM_TIME_HEADWAY, IDM_MIN_SPACING, IDM_MAX_ACCEL, IDM_COMF_DECEL, IDM_DELTA = range(6)
 IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7

@@ -497,6 +497,53 @@ class ParticipantPool:
         out["mask"] = out["mask"].view(np.uint32)
         return out
 
+    # ---------------------------------------------------------------- BEV camera
+    def camera_config(self, width, height, perception_range, bind_slot=0, heading_up=True, layers=L.CAMERA_LAYER_ALL,
+                      format=L.CAMERA_FORMAT_CLASS | L.CAMERA_FORMAT_RGB):
+        """Configure the BEV camera of every env (t2d_camera_config): width x height pixels, perception_range = (left,
+        right, front, back) in metres around participant `bind_slot`, heading_up (the participant points to the front of
+        the image) or north-up, layers / format = layout.CAMERA_LAYER_* / CAMERA_FORMAT_* bits.  width = 0 removes it."""
+        l, r, f, b = (0.0,) * 4 if not width else [float(v) for v in perception_range]
+        self._ck(self._lib.t2d_camera_config(self._h, int(width), int(height), l, r, f, b, int(bind_slot), int(bool(heading_up)),
+                                             int(layers), int(format)))
+        self._camera_shape = (int(height), int(width)) if width else None
+
+    def camera_set_palette(self, rgb):
+        """Colours of classes 0 .. len(rgb) - 1: uint8 [n_class, 3] (t2d_camera_set_palette)."""
+        a = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        self._ck(self._lib.t2d_camera_set_palette(self._h, _p(a), len(a)))
+
+    def camera_set_style(self, class_of_type=None, z_of_class=None):
+        """class_of_type uint8[MAX_TYPES]: the class participants of each parameter row are drawn as (None: boxes are
+        vehicles, discs pedestrians; CAMERA_CLASS_BACKGROUND = not drawn); z_of_class uint8[CAMERA_N_CLASS] (None: the
+        reference's resolved z-orders)."""
+        c = None if class_of_type is None else _arr(class_of_type, np.uint8, L.MAX_TYPES, "class_of_type")
+        z = None if z_of_class is None else _arr(z_of_class, np.uint8, L.CAMERA_N_CLASS, "z_of_class")
+        self._ck(self._lib.t2d_camera_set_style(self._h, _p(c), _p(z)))
+
+    def camera_render(self, stream=None, out_class=None, out_rgb=None):
+        """One launch, asynchronous on `stream`: the camera image of every env from the pool's current state
+        (t2d_camera_render).  out_class / out_rgb: device pointers (both None: the library's own images, camera_views())."""
+        self._ck(self._lib.t2d_camera_render(self._h, out_class, out_rgb, stream))
+
+    def camera_buffers(self):
+        """Device pointers and byte sizes of the library's own images: dict(image_class=(ptr, nbytes), image=(ptr, nbytes));
+        the pointer of a format that was not configured is None."""
+        pc, pr, nc, nr = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._ck(self._lib.t2d_camera_buffers(self._h, C.byref(pc), C.byref(pr), C.byref(nc), C.byref(nr)))
+        return dict(image_class=(pc.value, nc.value), image=(pr.value, nr.value))
+
+    def camera_views(self):
+        """Zero-copy torch views of the library's own images (valid until camera_config / close): image_class uint8
+        [n_env, H, W] and image uint8 [n_env, H, W, 3]; a format that was not configured is absent."""
+        import torch
+        b, (H, W), dev = self.camera_buffers(), self._camera_shape, f"cuda:{self.device_id}"
+        out = {}
+        for k, shape in (("image_class", (self.n_env, H, W)), ("image", (self.n_env, H, W, 3))):
+            if b[k][0]:
+                out[k] = torch.as_tensor(_DevArray(b[k][0], shape, "|u1", self), device=dev)
+        return out
+
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):
         """Device-side ParkingLotGenerator writing straight into this pool (one participant per env): obstacles,
