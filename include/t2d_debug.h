@@ -6,8 +6,9 @@
  * through tactics2d_amd/debug.py; no product module imports that.  The reference's operator API has no counterpart of any of
  * this (fault injection, a delayed collective, a stand-in policy, placement maps): they are how the build is TESTED.
  *
- * The -DT2D_DEBUG_HOOKS build differs from the product in exactly: these entry points, tactics2d_amd/csrc/t2d_loop.hip, and two
- * reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
+ * The -DT2D_DEBUG_HOOKS build differs from the product in exactly: these entry points, tactics2d_amd/csrc/t2d_loop.hip, the
+ * math probe (tactics2d_amd/csrc/t2d_math_probe.hip and t2d_math_probe_table.hip, which compile t2d_math.h once more and touch
+ * no product kernel), and two reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
  */
 #ifndef T2D_DEBUG_H_
 #define T2D_DEBUG_H_
@@ -62,6 +63,33 @@ int t2d_debug_closed_loop_create(t2d_pool* const* pools, void* const* hip_stream
                                  int32_t interval_ms, int32_t launcher, int32_t graph_steps, t2d_closed_loop** out);
 int t2d_debug_closed_loop_run(t2d_closed_loop* loop, int32_t n_steps);
 int t2d_debug_closed_loop_destroy(t2d_closed_loop* loop);
+
+/* ---- the device math primitives, one at a time (tactics2d_amd/csrc/t2d_math_probe.hip; tests/test_gpu_math.py) ------------------
+ * Evaluates ONE function of tactics2d_amd/csrc/t2d_math.h over host arrays on device `device_id`, compiled with the product's
+ * flags.  fn = T2D_MATH_*; a_host / b_host = n inputs each (b_host is read by the two-argument functions only and may be NULL
+ * otherwise); out_host = outputs(fn) * n doubles, PLANAR: output j of element i at out_host[j * n + i].
+ *     fn                  inputs                     outputs
+ *     SINCOS              a = x                      sin, cos                       sincos_det
+ *     SINCOS_SMALL        a = x, |x| <= 0.78         sin, cos                       sincos_det_small (no reduction)
+ *     SINCOS_STEER        a = x                      sin, cos                       sincos_det_steer (wave-uniform shortcut)
+ *     SINCOS_STEER_AND    a = steering, b = heading  sin a, cos a, sin b, cos b     sincos_det_steer_and
+ *     TAN, ATAN           a = x                      one                            tan_det, atan_det
+ *     ATAN2               a = y, b = x               one                            atan2_det
+ *     MOD_TWO_PI, LOG, EXP  a = x                    one                            mod_two_pi, log_det, exp_det
+ *     POW                 a = x, b = y               one                            pow_det(x, y)
+ * Element i is computed by lane i % 64 of wave i / 64 in workgroups of 256, and the lanes past n leave before any wave-level
+ * operation: the caller decides which inputs share a wave (the __ballot shortcuts of the steer variants).
+ * table = 1 runs the same function compiled with T2D_TRIG_TABLE (constants from __constant__ tables, as t2d_collide.hip compiles
+ * the header): SINCOS .. ATAN2 only.  Synchronous; uses the device's default stream.
+ * Errors (the text: t2d_last_error(NULL)): T2D_ERR_INVALID for an unknown fn, table outside {0, 1} or = 1 for a function without
+ * a table variant, n outside [1, T2D_MATH_MAX_N], a null array, an unknown device; T2D_ERR_HIP for a failing runtime call.   */
+enum {
+    T2D_MATH_SINCOS = 0, T2D_MATH_SINCOS_SMALL = 1, T2D_MATH_SINCOS_STEER = 2, T2D_MATH_SINCOS_STEER_AND = 3, T2D_MATH_TAN = 4,
+    T2D_MATH_ATAN = 5, T2D_MATH_ATAN2 = 6, T2D_MATH_MOD_TWO_PI = 7, T2D_MATH_LOG = 8, T2D_MATH_EXP = 9, T2D_MATH_POW = 10
+};
+#define T2D_MATH_MAX_N 16777216
+int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int64_t n, const double* a_host, const double* b_host,
+                   double* out_host);
 
 #ifdef __cplusplus
 }

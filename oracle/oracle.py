@@ -332,6 +332,46 @@ def det_log(x):
     return f(float(x))
 
 
+# the deterministic math primitives over arrays (t2do_math_batch; fn numbers = T2D_MATH_* of include/t2d_debug.h)
+MATH_FUNCTIONS = {"sincos": (0, 2), "sincos_small": (1, 2), "sincos_steer": (2, 2), "sincos_steer_and": (3, 4), "tan": (4, 1),
+                  "atan": (5, 1), "atan2": (6, 1), "mod_two_pi": (7, 1), "log": (8, 1), "exp": (9, 1), "pow": (10, 1)}
+
+
+def det_math(fn, a, b=None):
+    """The spec of one device math primitive (tactics2d_amd/csrc/t2d_math.h) over fp64 arrays: fn = a key of MATH_FUNCTIONS,
+    b = sincos_steer_and's heading, atan2's x, pow's exponent.  The small / steer variants are t2do_sincos -- the device's
+    shortcuts promise its bits.  Returns fp64 [outputs, n], [n] for one output."""
+    code, nout = MATH_FUNCTIONS[fn]
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    bp = None
+    if b is not None:
+        b = np.ascontiguousarray(b, np.float64).reshape(-1)
+        assert b.size == a.size
+        bp = b.ctypes.data_as(C.c_void_p)
+    out = np.empty((nout, a.size), np.float64)
+    f = lib().t2do_math_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_longlong, _f64p, C.c_void_p, _f64p]
+    if f(code, a.size, a, bp, out.reshape(-1)) != 0:
+        raise ValueError(f"t2do_math_batch refused {fn}")
+    return out[0] if nout == 1 else out
+
+
+def det_atan2(y, x):
+    f = lib().t2do_atan2; f.restype = C.c_double; f.argtypes = [C.c_double, C.c_double]
+    return f(float(y), float(x))
+
+
+def det_tan(x):
+    f = lib().t2do_tan; f.restype = C.c_double; f.argtypes = [C.c_double]
+    return f(float(x))
+
+
+def det_mod_two_pi(phi):
+    f = lib().t2do_mod_two_pi; f.restype = C.c_double; f.argtypes = [C.c_double]
+    return f(float(phi))
+
+
 def idm(ctrl_rows, ctrl_id, n_env, A, x, y, heading, speed, active, act0, act1, forced_leader=None, trig=1):
     """Batched IDM with the build-defined leader rule.  Returns (act0, act1, leader) -- act0/act1 are
     copies of the inputs with the controlled participants' entries replaced."""

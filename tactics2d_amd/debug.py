@@ -12,6 +12,7 @@ libt2d_hip.so exports no t2d_debug_* symbol.
     delay_gather(pool, us)            hold the pool's gather stream (a slow peer)
     feedback_policy(pool, act, ...)   the stand-in policy kernel
     env_groups(scene, G) / ClosedLoop policy kernel -> t2d_step per env group, enqueued by one C call
+    math(fn, a, b=None, table=False)  one device function of csrc/t2d_math.h over arrays (tests/test_gpu_math.py)
 """
 import ctypes as C
 import os
@@ -35,6 +36,7 @@ DEBUG_SYMBOLS = {
     "t2d_debug_closed_loop_run": (C.c_int, [_vp, C.c_int32]),
     "t2d_debug_closed_loop_destroy": (C.c_int, [_vp]),
     "t2d_debug_last_step_kernel": (C.c_char_p, []),
+    "t2d_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
 }
 
 _debug_lib = None
@@ -95,6 +97,28 @@ def feedback_policy(p, act_out_ptr, v_target, k_speed, k_steer, stream=None):
     """t2d_debug_feedback_policy: the stand-in policy, one launch; act_out_ptr = device f32 [N][2] (steering, accel)"""
     _need(p)
     p._ck(p._lib.t2d_debug_feedback_policy(p._h, act_out_ptr, v_target, k_speed, k_steer, stream))
+
+
+# t2d_debug_math's fn (include/t2d_debug.h: T2D_MATH_*) -> number of outputs
+MATH_FUNCTIONS = {"sincos": (0, 2), "sincos_small": (1, 2), "sincos_steer": (2, 2), "sincos_steer_and": (3, 4), "tan": (4, 1),
+                  "atan": (5, 1), "atan2": (6, 1), "mod_two_pi": (7, 1), "log": (8, 1), "exp": (9, 1), "pow": (10, 1)}
+
+
+def math(fn, a, b=None, table=False, device_id=0):
+    """t2d_debug_math: the device function `fn` of csrc/t2d_math.h (a key of MATH_FUNCTIONS, or a raw T2D_MATH_* value) over the
+    fp64 array a (and b: sincos_steer_and's heading, atan2's x, pow's exponent).  Element i runs in lane i % 64 of wave i // 64.
+    table=True: the T2D_TRIG_TABLE compilation.  Returns fp64 [outputs, n] -- [n] for a function with one output."""
+    code, nout = MATH_FUNCTIONS[fn] if fn in MATH_FUNCTIONS else (int(fn), 4)
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    if b is not None:
+        b = np.ascontiguousarray(b, np.float64).reshape(-1)
+        if b.size != a.size:
+            raise ValueError("a and b differ in length")
+    out = np.empty((nout, a.size), np.float64)
+    rc = lib().t2d_debug_math(int(device_id), code, int(table), a.size, a.ctypes.data, None if b is None else b.ctypes.data,
+                              out.ctypes.data)
+    _ffi.check(rc, None, lib())
+    return out[0] if nout == 1 else out
 
 
 class ClosedLoop:
