@@ -46,6 +46,8 @@
  *   t2d_off_route            Trajectory.get_trace (trace routes)  participant/trajectory/trajectory.py:151-168
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
+ *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
+ *   t2d_set_tracks_generated / t2d_tracks_regenerate   RacingEnv.reset: a new track per episode   envs/racing.py:374-383
  *   t2d_step_host         <- ParkingEnv.step as its caller sees it: host action in, host 5-tuple out
  *                            envs/parking.py:219-256, _get_infos / _get_relative_pose :190-217
  *
@@ -786,6 +788,90 @@ int t2d_track_progress(t2d_pool* pool, int32_t write_status, void* hip_stream);
 int t2d_track_buffers(t2d_pool* pool, void** tile_visiting_dev, void** num_visited_dev, void** mask_dev, void** status_dev,
                       void** reward_dev, size_t* n_env);
 
+/* Racing tracks generated on the device (kernel: tactics2d_amd/csrc/t2d_trackgen.hip) -- RacingTrackGenerator.generate
+ * (map/generator/generate_racing_track.py) as the host class tactics2d_amd/generator.py::RacingTrackGenerator restates it, for
+ * many tracks in one launch, and RacingEnv.reset's "a new track for every episode" (envs/racing.py:374-383) without the host.
+ *
+ * THE STREAM.  Like the parking generator the build draws from a counter stream of its own, not numpy's MT19937: splitmix64,
+ * the top 53 bits of each output as a uniform u in [0, 1) (tactics2d_amd/csrc/t2d_rng.h).  With fin() the splitmix64 finaliser
+ * (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31; all modulo 2^64), ATTEMPT a
+ * OF TRACK t draws from the stream whose state before its first draw is
+ *     fin(fin(seed + (t + 1) * T2D_TRACKGEN_KEY_TRACK) + (a + 1) * T2D_TRACKGEN_KEY_ATTEMPT)
+ * and draw k (k = 0 first) of a stream in state s is u = (fin(s + (k + 1) * 0x9E3779B97F4A7C15) >> 11) * 2^-53.
+ * randint(10, 20) is 10 + floor(10 u), uniform(a, b) is a + (b - a) u, and within an attempt the draws are asked for in the
+ * order RacingTrackGenerator._get_checkpoints asks numpy for them: n; n noises; n radii; then per pass and turn t1, t2 and,
+ * for a rejected turn, the radius step and the angle step.
+ * THE RULE.  An attempt succeeds as in the reference: all n turns glued within 100 passes AND the angles still sorted (a turn
+ * whose three points are collinear, |denominator| < 1e-10, where the reference raises, fails its attempt).  THE TRACK IS THE
+ * ONE MADE FROM THE SUCCESSFUL ATTEMPT WITH THE LOWEST INDEX; attempts 0 .. T2D_TRACKGEN_MAX_ATTEMPTS - 1 are tried (one in
+ * six succeeds: 0.83^128 = 4e-11).  The kernel runs T2D_TRACKGEN_ROUND consecutive attempts side by side; the result does not
+ * depend on that, on the launch or on how a batch is split: track first_track + i of one call is track i of a call that
+ * starts there.  A track that hits the cap (T2D_TRACKGEN_CAPPED) or has more than T2D_MAX_TRACK_TILES tiles
+ * (T2D_TRACKGEN_OVERFLOW) comes back FLAGGED, without tiles, and is never installed.
+ * THE BUILD restates the host class step by step in fp64, one rounding per operation, trigonometry = the deterministic
+ * sincos / atan2 / mod 2 pi of t2d_math.h: _circle_radius, the control points of the accepted pass, _get_start_point (with
+ * its Frobenius-norm measure of a straight, and "the first of the three longest that is < 200, else the third"), _bezier2
+ * (50 points per turn), _Polyline.length as a running sum in segment order, n_tile = ceil(length / 10), _get_tiles (a point at
+ * distance d lies on the first segment k with before[k] + seg[k] > d), the shift to the centre of the fp64 bounding box of
+ * the tile vertices, rounding to fp32, RacingTrack.start_pose from the shifted fp64 start line (car_length = the ego's
+ * length; heading reduced to [0, 2 pi)) and the boundary (floor min x, ceil max x, floor min y, ceil max y) over the fp32
+ * tile vertices and the fp32 shifted centre-line points.  np.linalg.norm sums in an order BLAS chooses; here the norm of 2
+ * numbers is sqrt(a*a + b*b) and of 4 numbers sqrt(((a*a + b*b) + c*c) + d*d).  tests/trackgen_ref.py states all of this in
+ * Python; the kernel agrees with it bit for bit, and it agrees with the host class (fed the same draws) to one fp32 ulp.
+ * PARITY with the reference: by construction different in the random stream, the attempt cap and the norms' summation order.
+ *
+ *   t2d_generate_tracks  the stand-alone batch generator (no pool), one launch, asynchronous on hip_stream.  Every output is
+ *                        DEVICE memory, one record per track, tiles in the CAPACITY LAYOUT: tiles f32 [n_tracks]
+ *                        [T2D_MAX_TRACK_TILES][4][2] (64 KiB per track; only the first n_tile records of a track are written),
+ *                        n_tile / n_checkpoint / attempt i32 [n_tracks] (attempt = index of the accepted attempt, -1 at the
+ *                        cap), start_pose f64 [n_tracks][3], start_line f32 [n_tracks][2][2], boundary f32 [n_tracks][4],
+ *                        flags u32 [n_tracks].  Of a flagged track only flags, attempt, n_checkpoint and n_tile (0 at the
+ *                        cap, the refused count beyond the capacity) are written.  tiles, start_line and boundary are written
+ *                        with 16-byte vector stores: these three pointers must be 16-byte aligned (hipMalloc's are), and
+ *                        T2D_ERR_INVALID is returned for one that is not.
+ *   t2d_set_tracks_generated  generates n_sets tracks (streams first_track .. first_track + n_sets - 1) INTO the pool and
+ *                        installs them as t2d_set_tracks would: the tiles are the pool's track sets in the capacity layout,
+ *                        with a per-set tile count the progress launch and the camera's track layer read (host-uploaded tracks
+ *                        fill the same array); each env's out-bound boundary, the ego's start pose in the state columns and in
+ *                        the episode snapshot (speed 0) and the progress state as after t2d_track_reset are installed too, all
+ *                        on the device.  Needs a parameter table, t2d_reset, t2d_snapshot and a boundary array
+ *                        (t2d_set_static_geometry) to write into.  Synchronous, as t2d_set_tracks is; reads n_tile back (so that
+ *                        t2d_track_upload keeps validating).  check_off_road is not supported with generated tracks: the
+ *                        function has no such argument, so there is nothing for it to refuse with T2D_ERR_INVALID -- the refusal
+ *                        is the binding's (ParticipantPool.set_tracks_generated(check_off_road=True) and VecRacingEnv raise
+ *                        ValueError), and the progress launch runs as with check_off_road = 0.  Any flagged track: T2D_ERR_GEOMETRY, the message names it, nothing is installed.
+ *                        regenerate = 1 needs n_sets == n_env, the identity set_of_env (or NULL then) and track_stride >=
+ *                        n_env (T2D_ERR_INVALID otherwise).
+ *   t2d_tracks_regenerate  ONE launch, asynchronous, for between t2d_track_progress(write_status = 1) and t2d_restore(pool, 1):
+ *                        every env whose track status says terminated or truncated moves on to its next episode k (its count
+ *                        goes up by one): the track of stream first_track + e + k * track_stride is generated IN PLACE into
+ *                        the env's slot, and its tile count, its boundary and the start pose in the snapshot replace the old
+ *                        ones; the restore launch that follows starts the episode there.  Terminal status and reward stay
+ *                        readable.  An env whose new track is flagged keeps its old track, and the pool's sticky error word is
+ *                        raised: the next t2d_sync / t2d_download reports T2D_ERR_STATE once.  Its episode count does NOT go
+ *                        up then, so its next finish asks for the same stream and is flagged again: such an env stays on its old
+ *                        track until t2d_set_tracks_generated re-keys it (about 4e-11 per track at the cap).  Workgroups of envs that did not
+ *                        finish exit on their first load.  T2D_ERR_STATE unless t2d_set_tracks_generated(regenerate = 1)
+ *                        preceded it.  kernel_id 12 in t2d_profile_read.  No stepping call launches it.                        */
+#define T2D_TRACKGEN_MAX_ATTEMPTS 128
+#define T2D_TRACKGEN_ROUND 16
+#define T2D_TRACKGEN_CAPPED 1u
+#define T2D_TRACKGEN_OVERFLOW 2u
+#define T2D_TRACKGEN_KEY_TRACK 0xD1B54A32D192ED03ull
+#define T2D_TRACKGEN_KEY_ATTEMPT 0x8CB92BA72F3D8DD7ull
+#define T2D_PROFILE_TRACKGEN 12
+int t2d_generate_tracks(int32_t device_id, int32_t n_tracks, uint64_t seed, int64_t first_track, double car_length,
+                        float* tiles_dev, int32_t* n_tile_dev, int32_t* n_checkpoint_dev, int32_t* attempt_dev,
+                        double* start_pose_dev, float* start_line_dev, float* boundary_dev, uint32_t* flags_dev, void* hip_stream);
+int t2d_set_tracks_generated(t2d_pool* pool, int32_t n_sets, uint64_t seed, int64_t first_track, int64_t track_stride,
+                             double car_length, const int32_t* set_of_env, int32_t ego_index, int32_t rule, int32_t max_advance, int32_t regenerate);
+int t2d_tracks_regenerate(t2d_pool* pool, void* hip_stream);
+/* device pointers of the generated tracks' records (n_sets of each, layouts as t2d_generate_tracks'; valid until the tracks
+ * are replaced): T2D_ERR_STATE without generated tracks                                                                     */
+int t2d_generated_track_buffers(t2d_pool* pool, void** tiles_dev, void** n_tile_dev, void** n_checkpoint_dev, void** attempt_dev,
+                                void** start_pose_dev, void** start_line_dev, void** boundary_dev, void** episode_dev,
+                                size_t* n_sets);
+
 /* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
  * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
  *
@@ -936,7 +1022,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
 /* Per-kernel timing with HIP events recorded on the launch stream around each kernel.
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
- * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render).                                       */
+ * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
+ * (t2d_tracks_regenerate).                                       */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -111,6 +111,11 @@ SYMBOLS = {
     "t2d_track_upload": (C.c_int, [_vp, _vp, _vp, _vp]),
     "t2d_track_progress": (C.c_int, [_vp, C.c_int32, _vp]),
     "t2d_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 5 + [C.POINTER(C.c_size_t)]),
+    "t2d_generate_tracks": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_double] + [_vp] * 9),
+    "t2d_set_tracks_generated": (C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_double, _vp, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32]),
+    "t2d_tracks_regenerate": (C.c_int, [_vp, _vp]),
+    "t2d_generated_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 8 + [C.POINTER(C.c_size_t)]),
     "t2d_camera_config": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                     C.c_uint32, C.c_uint32]),
     "t2d_camera_set_palette": (C.c_int, [_vp, _vp, C.c_int32]),

@@ -131,6 +131,15 @@ hipError_t quiesce(t2d_pool* p) {
             p->scene_commit_failed = true;
         }
     }
+    if (e == hipSuccess && p->trackgen_used && p->trackgen.err) {
+        uint32_t err = 0;
+        e = hipMemcpy(&err, p->trackgen.err, sizeof(err), hipMemcpyDeviceToHost);
+        p->trackgen_used = false;
+        if (e == hipSuccess && err) {
+            (void)hipMemset(p->trackgen.err, 0, sizeof(err));
+            p->trackgen_failed = true;
+        }
+    }
     if (e == hipSuccess && p->chain_used) {   // a chained launch reports a broken hand-off through two words in device memory
         uint32_t err[2] = {0, 0};   // {1: a bounded wait ran out | 2: producer and consumer on different XCDs, ckpt_tag of the fragment}
         e = hipMemcpy(err, p->d_chain + p->chain_slots, sizeof(err), hipMemcpyDeviceToHost);
@@ -170,6 +179,11 @@ int report_chain_failure(t2d_pool* p) {
         p->scene_commit_failed = false;
         return fail(p, T2D_ERR_STATE, "scene regeneration: an env whose episode ended found no staged scene for its next episode and "
                                       "kept its old one -- call t2d_parking_scenes again before stepping on");
+    }
+    if (p->trackgen_failed) {
+        p->trackgen_failed = false;
+        return fail(p, T2D_ERR_STATE, "track regeneration: an env's next track came back flagged (the attempt cap, or more tiles than "
+                                      "T2D_MAX_TRACK_TILES) and the env kept its old track");
     }
     if (!p->chain_failed) return T2D_OK;
     p->chain_failed = false;
@@ -1871,7 +1885,7 @@ int t2d_download(t2d_pool* p, int32_t f, void* host_dst, size_t nbytes) {
                                             std::to_string(f >= 0 && f < T2D_F_COUNT ? p->field_bytes[f] : 0) + " bytes)");
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
-    if (p->chain_failed || p->scene_commit_failed) return report_chain_failure(p);
+    if (p->chain_failed || p->scene_commit_failed || p->trackgen_failed) return report_chain_failure(p);
     T2D_HIP(p, hipMemcpy(host_dst, p->field_ptr[f], nbytes, hipMemcpyDeviceToHost));
     return T2D_OK;
 }
@@ -1903,7 +1917,7 @@ int t2d_sync(t2d_pool* p) {
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
-    if (p->chain_failed || p->scene_commit_failed) return report_chain_failure(p);
+    if (p->chain_failed || p->scene_commit_failed || p->trackgen_failed) return report_chain_failure(p);
     return T2D_OK;
 }
 
@@ -2814,6 +2828,8 @@ static void track_release(t2d_pool* p) {
     p->d_track = nullptr;
     p->track = t2d::TrackView{};
     p->track_n_tile.clear();
+    p->trackgen = t2d::TrackGenView{};
+    p->trackgen_regen = p->trackgen_used = p->trackgen_failed = false;
 }
 
 namespace {
@@ -2821,11 +2837,14 @@ constexpr int kTrackWords = T2D_MAX_TRACK_TILES / 32;
 // byte offsets of the sections of the one allocation behind a TrackView, each on a 256-byte boundary.  The per-env state
 // (visiting .. start_mask) is contiguous: t2d_track_reset / t2d_track_upload move it in one copy each way.
 struct TrackLayout {
-    size_t tiles, set_start, set_of_env, visiting, num_visited, mask, status, reward, start_visiting, start_mask, bytes;
-    TrackLayout(size_t n_tile, size_t n_sets, size_t E) {
+    size_t tiles, set_start, n_tile, set_of_env, visiting, num_visited, mask, status, reward, start_visiting, start_mask, bytes;
+    size_t g_ncp, g_attempt, g_pose, g_line, g_bound, g_flags, g_episode, g_err;   // generated tracks only (gen_sets records)
+    TrackLayout(size_t n_tile_all, size_t n_sets, size_t E, size_t gen_sets = 0) {
         size_t o = 0;
         auto take = [&](size_t b) { const size_t at = o; o += (b + 255) & ~(size_t)255; return at; };
-        tiles = take(n_tile * 32); set_start = take((n_sets + 1) * 4); set_of_env = take(E * 4);
+        tiles = take(n_tile_all * 32); set_start = take((n_sets + 1) * 4); n_tile = take(n_sets * 4); set_of_env = take(E * 4);
+        g_ncp = take(gen_sets * 4); g_attempt = take(gen_sets * 4); g_pose = take(gen_sets * 24); g_line = take(gen_sets * 16);
+        g_bound = take(gen_sets * 16); g_flags = take(gen_sets * 4); g_episode = take(gen_sets ? E * 4 : 0); g_err = take(gen_sets ? 4 : 0);
         visiting = take(E * 4); num_visited = take(E * 4); mask = take(E * kTrackWords * 4); status = take(E * 4);
         reward = take(E * 4); start_visiting = take(E * 4); start_mask = take(E * kTrackWords * 4);
         bytes = o;
@@ -2859,6 +2878,11 @@ void track_assign_host(char* buf, const TrackLayout& lay, int E, const uint8_t* 
 int track_assign(t2d_pool* p, const char* who, const uint8_t* env_mask, const int32_t* visiting, const uint32_t* mask) {
     if (!p->track.installed) return fail(p, T2D_ERR_STATE, std::string("t2d_set_tracks must precede ") + who);
     const int E = p->v.n_env;
+    if (p->trackgen_regen && (visiting || mask)) {   // (regenerated tracks: the tile counts are the device's)
+        T2D_HIP(p, hipSetDevice(p->device));
+        T2D_HIP(p, quiesce(p));
+        T2D_HIP(p, hipMemcpy(p->track_n_tile.data(), p->track.n_tile, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
     for (int e = 0; e < E; ++e) {
         if (env_mask && !env_mask[e]) continue;
         const int n = p->track_n_tile[e];
@@ -2928,6 +2952,7 @@ int t2d_set_tracks(t2d_pool* p, int32_t n_sets, const int32_t* set_tile_offsets,
     std::vector<char> img(lay.bytes);
     memcpy(img.data() + lay.tiles, tiles_xy, (size_t)n_tile * 32);
     memcpy(img.data() + lay.set_start, set_tile_offsets, (size_t)(n_sets + 1) * sizeof(int32_t));
+    for (int s = 0; s < n_sets; ++s) ((int32_t*)(img.data() + lay.n_tile))[s] = set_tile_offsets[s + 1] - set_tile_offsets[s];
     for (int e = 0; e < E; ++e) ((int32_t*)(img.data() + lay.set_of_env))[e] = set_of_env ? set_of_env[e] : 0;
     track_assign_host(img.data(), lay, E, nullptr, nullptr, nullptr);
     char* d = nullptr;
@@ -2948,6 +2973,7 @@ int t2d_set_tracks(t2d_pool* p, int32_t n_sets, const int32_t* set_tile_offsets,
     tv.installed = 1; tv.ego_index = ego_index; tv.rule = rule; tv.max_advance = max_advance; tv.check_off_road = check_off_road != 0;
     tv.tiles = (const float*)(d + lay.tiles);
     tv.set_start = (const int32_t*)(d + lay.set_start);
+    tv.n_tile = (const int32_t*)(d + lay.n_tile);
     tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
     tv.visiting = (int32_t*)(d + lay.visiting);
     tv.num_visited = (int32_t*)(d + lay.num_visited);
@@ -2956,6 +2982,143 @@ int t2d_set_tracks(t2d_pool* p, int32_t n_sets, const int32_t* set_tile_offsets,
     tv.reward = (float*)(d + lay.reward);
     tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
     tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+    return T2D_OK;
+}
+
+int t2d_set_tracks_generated(t2d_pool* p, int32_t n_sets, uint64_t seed, int64_t first_track, int64_t track_stride,
+                             double car_length, const int32_t* set_of_env, int32_t ego_index, int32_t rule, int32_t max_advance,
+                             int32_t regenerate) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    const int E = p->v.n_env;
+    const std::string who = "t2d_set_tracks_generated: ";
+    if (n_sets < 1 || n_sets > E) return fail(p, T2D_ERR_INVALID, who + "n_sets must be in 1 .. n_env");
+    if (first_track < 0) return fail(p, T2D_ERR_INVALID, who + "first_track must be >= 0");
+    if (!(car_length > 0.0)) return fail(p, T2D_ERR_INVALID, who + "car_length must be > 0");
+    if (ego_index < 0 || ego_index >= p->v.A)
+        return fail(p, T2D_ERR_INVALID, who + "ego_index " + std::to_string(ego_index) + " outside [0, max_agents)");
+    if (rule != T2D_TRACK_RULE_REFERENCE && rule != T2D_TRACK_RULE_FORWARD) return fail(p, T2D_ERR_INVALID, who + "unknown rule " + std::to_string(rule));
+    if (max_advance < 0) return fail(p, T2D_ERR_INVALID, who + "max_advance must be >= 0 (0 = the whole ring)");
+    if (!set_of_env && n_sets != 1 && n_sets != E)
+        return fail(p, T2D_ERR_INVALID, who + "a NULL set_of_env needs n_sets = 1 (every env on track 0) or n_sets = n_env (the identity)");
+    std::vector<int32_t> soe(E);
+    for (int e = 0; e < E; ++e) {
+        soe[e] = set_of_env ? set_of_env[e] : (n_sets == 1 ? 0 : e);
+        if (soe[e] < 0 || soe[e] >= n_sets)
+            return fail(p, T2D_ERR_INVALID, who + "set_of_env[" + std::to_string(e) + "] = " + std::to_string(soe[e]) + " outside [0, " + std::to_string(n_sets) + ")");
+    }
+    if (regenerate) {
+        bool identity = n_sets == E;
+        for (int e = 0; e < E && identity; ++e) identity = soe[e] == e;
+        if (!identity) return fail(p, T2D_ERR_INVALID, who + "regenerate = 1 needs a track set of its own for every env (n_sets == n_env, set_of_env the identity)");
+        if (track_stride < E) return fail(p, T2D_ERR_INVALID, who + "regenerate = 1 needs track_stride >= n_env (two episodes would share a stream otherwise)");
+    }
+    if (!p->have_params || !p->have_reset || !p->have_snapshot)
+        return fail(p, T2D_ERR_STATE, who + "t2d_set_param_table, t2d_reset and t2d_snapshot must precede it");
+    if (!p->d_boundary) return fail(p, T2D_ERR_STATE, who + "the pool has no out-bound boundary array to write into (t2d_set_static_geometry with a boundary)");
+    const TrackLayout lay((size_t)n_sets * T2D_MAX_TRACK_TILES, (size_t)n_sets, (size_t)E, (size_t)n_sets);
+    // the host image holds everything behind the tiles: the same layout without tiles, every offset lower by lay.set_start
+    const TrackLayout tail(0, (size_t)n_sets, (size_t)E, (size_t)n_sets);
+    if (tail.bytes + lay.set_start != lay.bytes) return fail(p, T2D_ERR_STATE, who + "internal: the two track layouts disagree");
+    std::vector<char> img(tail.bytes);
+    for (int s = 0; s <= n_sets; ++s) ((int32_t*)(img.data() + tail.set_start))[s] = s * T2D_MAX_TRACK_TILES;
+    memcpy(img.data() + tail.set_of_env, soe.data(), (size_t)E * sizeof(int32_t));
+    track_assign_host(img.data(), tail, E, nullptr, nullptr, nullptr);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, lay.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(p, T2D_ERR_NOMEM, who + std::to_string(lay.bytes) + " bytes of device memory");
+    }
+    t2d::TrackGenView g{};
+    g.seed = seed; g.first_track = first_track; g.track_stride = track_stride; g.car_length = car_length;
+    g.tiles = (float*)(d + lay.tiles); g.n_tile = (int32_t*)(d + lay.n_tile); g.n_checkpoint = (int32_t*)(d + lay.g_ncp);
+    g.attempt = (int32_t*)(d + lay.g_attempt); g.start_pose = (double*)(d + lay.g_pose); g.start_line = (float*)(d + lay.g_line);
+    g.boundary = (float*)(d + lay.g_bound); g.flags = (uint32_t*)(d + lay.g_flags);
+    g.status = (const uint8_t*)(d + lay.status); g.episode = (int32_t*)(d + lay.g_episode); g.err = (uint32_t*)(d + lay.g_err);
+    g.env_boundary = p->d_boundary;
+    for (int k = 0; k < 6; ++k) g.snap[k] = p->d_snap[k];
+    g.ego_index = ego_index; g.A = p->v.A;
+    std::vector<uint32_t> flags(n_sets);
+    std::vector<int32_t> n_of_set(n_sets);
+    hipError_t he = quiesce(p);
+    if (he == hipSuccess) he = hipMemcpy(d + lay.set_start, img.data(), img.size(), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = t2d::launch_trackgen(g, n_sets, 0, nullptr);
+    if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+    if (he == hipSuccess) he = hipMemcpy(flags.data(), g.flags, (size_t)n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(n_of_set.data(), g.n_tile, (size_t)n_sets * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) {
+        (void)hipFree(d);
+        return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
+    }
+    for (int s = 0; s < n_sets; ++s)
+        if (flags[s] || n_of_set[s] < 3) {
+            (void)hipFree(d);
+            return fail(p, T2D_ERR_GEOMETRY, who + "track " + std::to_string(s) + " (stream " + std::to_string((long long)(first_track + s)) + ") came back flagged (" +
+                                                 (flags[s] & T2D_TRACKGEN_CAPPED ? "no attempt succeeded" : "more tiles than T2D_MAX_TRACK_TILES") + "): nothing was installed");
+        }
+    // the envs' boundary, the ego's state and snapshot, from the tracks just made (nothing of them crosses to the host)
+    he = t2d::launch_track_install(p->v, g, (const int32_t*)(d + lay.set_of_env), nullptr);
+    if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+    if (he != hipSuccess) {
+        (void)hipFree(d);
+        return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
+    }
+    track_release(p);   // nothing can fail from here on
+    p->d_track = d;
+    p->track_n_tile.resize(E);
+    for (int e = 0; e < E; ++e) p->track_n_tile[e] = n_of_set[soe[e]];
+    p->trackgen = g;
+    p->trackgen_sets = n_sets;
+    p->trackgen_regen = regenerate != 0;
+    t2d::TrackView& tv = p->track;
+    tv.installed = 1; tv.ego_index = ego_index; tv.rule = rule; tv.max_advance = max_advance; tv.check_off_road = 0;
+    tv.tiles = (const float*)(d + lay.tiles);
+    tv.set_start = (const int32_t*)(d + lay.set_start);
+    tv.n_tile = (const int32_t*)(d + lay.n_tile);
+    tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
+    tv.visiting = (int32_t*)(d + lay.visiting);
+    tv.num_visited = (int32_t*)(d + lay.num_visited);
+    tv.mask = (uint32_t*)(d + lay.mask);
+    tv.status = (uint8_t*)(d + lay.status);
+    tv.reward = (float*)(d + lay.reward);
+    tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
+    tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+    return T2D_OK;
+}
+
+int t2d_tracks_regenerate(t2d_pool* p, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->track.installed || !p->trackgen.tiles || !p->trackgen_regen)
+        return fail(p, T2D_ERR_STATE, "t2d_set_tracks_generated with regenerate = 1 must precede t2d_tracks_regenerate");
+    // (the launch writes through pointers taken at the install: a boundary array or a snapshot made anew since is not theirs)
+    bool same = p->trackgen.env_boundary == p->d_boundary && p->have_snapshot;
+    for (int k = 0; k < 6; ++k) same = same && p->trackgen.snap[k] == p->d_snap[k];
+    if (!same)
+        return fail(p, T2D_ERR_STATE, "t2d_tracks_regenerate: the pool's boundary array or snapshot was replaced since "
+                                      "t2d_set_tracks_generated -- install the tracks again");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, T2D_PROFILE_TRACKGEN, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_trackgen(p->trackgen, p->v.n_env, 2, s));
+    p->trackgen_used = true;
+    return record_event(p, T2D_PROFILE_TRACKGEN, s, false);
+}
+
+int t2d_generated_track_buffers(t2d_pool* p, void** tiles_dev, void** n_tile_dev, void** n_checkpoint_dev, void** attempt_dev,
+                                void** start_pose_dev, void** start_line_dev, void** boundary_dev, void** episode_dev,
+                                size_t* n_sets) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!tiles_dev || !n_tile_dev || !n_checkpoint_dev || !attempt_dev || !start_pose_dev || !start_line_dev || !boundary_dev ||
+        !episode_dev || !n_sets)
+        return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->track.installed || !p->trackgen.tiles)
+        return fail(p, T2D_ERR_STATE, "t2d_set_tracks_generated must precede t2d_generated_track_buffers");
+    const t2d::TrackGenView& g = p->trackgen;
+    *tiles_dev = g.tiles; *n_tile_dev = g.n_tile; *n_checkpoint_dev = g.n_checkpoint; *attempt_dev = g.attempt;
+    *start_pose_dev = g.start_pose; *start_line_dev = g.start_line; *boundary_dev = g.boundary; *episode_dev = g.episode;
+    *n_sets = (size_t)p->trackgen_sets;
     return T2D_OK;
 }
 

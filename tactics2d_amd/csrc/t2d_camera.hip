@@ -128,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void camera_kernel(PoolView pv, CameraView 
     if ((cv.layers & T2D_CAMERA_LAYER_TRACKS) && tv.installed) {
         const int set = tv.set_of_env[e];
         t0 = tv.set_start[set];
-        n_tile = tv.set_start[set + 1] - t0;
+        n_tile = tv.n_tile[set];
     }
     const int n_part = (cv.layers & T2D_CAMERA_LAYER_PARTICIPANTS) ? pv.A : 0;
     const int b1 = n_target, b2 = b1 + n_static, b3 = b2 + n_lane, b4 = b3 + n_tile, total = sane ? b4 + n_part : 0;

@@ -21,6 +21,7 @@
 
 #include "t2d_math.h"
 #include "t2d_pool.h"
+#include "t2d_rng.h"
 #include "t2d_scene_dev.h"
 
 namespace t2d {
@@ -30,32 +31,9 @@ namespace {
 constexpr int kGenBlock = 64;
 constexpr int kListCap = 24;  // obstacle list entries per scene (3 rejected attempts' worth; more is flagged)
 constexpr double kPi = 3.141592653589793;
-constexpr double kTwoPi = 2.0 * 3.141592653589793;
 
 struct Quad {
     double v[8];
-};
-
-struct Stream {  // splitmix64 counter stream, one per scene
-    uint64_t s;
-    T2D_DEV double u() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-    }
-    T2D_DEV double uniform(double a, double b) { return a + (b - a) * u(); }
-    T2D_DEV double normal(double mean, double std) {  // Box-Muller, cosine branch
-        const double u1 = 1.0 - u(), u2 = u();
-        const double rad = __builtin_sqrt(-2.0 * log_det(u1));
-        double sn, cs;
-        sincos_det(kTwoPi * u2, sn, cs);
-        return mean + std * (rad * cs);
-    }
-    T2D_DEV double trunc_gauss(double mean, double std, double lo, double hi) {  // :60-62
-        return clipd(normal(mean, std), lo, hi);
-    }
 };
 
 // _get_bbox: body-frame ring (+L/2,-W/2), (+L/2,+W/2), (-L/2,+W/2), (-L/2,-W/2) through [cos, -sin, sin, cos, cx, cy]

@@ -271,7 +271,8 @@ struct RouteView {
 struct TrackView {
     int32_t installed, ego_index, rule, max_advance, check_off_road, pad;
     const float* tiles;            // [n_tile of all sets][4][2] ring vertices, 32-byte records
-    const int32_t* set_start;      // [n_sets + 1] first tile of each set
+    const int32_t* set_start;      // [n_sets + 1] first tile of each set (generated tracks: set * T2D_MAX_TRACK_TILES, the capacity layout)
+    const int32_t* n_tile;         // [n_sets] tiles of each set's ring (what lies beyond them in a generated set's slot is never read)
     const int32_t* set_of_env;     // [E]
     int32_t *visiting, *num_visited;   // [E]
     uint32_t* mask;                // [E][T2D_MAX_TRACK_TILES / 32] bit t of an env: tile t visited
@@ -279,6 +280,27 @@ struct TrackView {
     float* reward;                 // [E]
     const int32_t* start_visiting; // [E]
     const uint32_t* start_mask;    // [E][T2D_MAX_TRACK_TILES / 32]
+};
+
+// The device track generator (t2d_trackgen.hip).  Track t of a launch is the track of the counter stream (seed, first_track +
+// t [+ episode * track_stride]); its record goes to slot t of the arrays below, tiles in the capacity layout.
+struct TrackGenView {
+    uint64_t seed;
+    int64_t first_track, track_stride;
+    double car_length;             // the start pose puts the nose of a car of this length on the start line
+    float* tiles;                  // [n][T2D_MAX_TRACK_TILES][4][2]
+    int32_t *n_tile, *n_checkpoint, *attempt;   // [n]
+    double* start_pose;            // [n][3] x, y, heading in [0, 2 pi)
+    float* start_line;             // [n][2][2]
+    float* boundary;               // [n][4] xmin, xmax, ymin, ymax
+    uint32_t* flags;               // [n] T2D_TRACKGEN_*
+    // installed tracks only (t2d_set_tracks_generated / t2d_tracks_regenerate)
+    const uint8_t* status;         // [E][4] the progress launch's status: who finished
+    int32_t* episode;              // [E] episodes each env has finished
+    uint32_t* err;                 // sticky: a regenerated track came back flagged (its env kept the old one)
+    float* env_boundary;           // [E][4] the pool's out-bound boundary
+    float* snap[6];                // the episode snapshot
+    int32_t ego_index, A;
 };
 
 // BEV camera (t2d_camera.hip): the window, the style tables and the camera's own device copy of the caller's static and lane
@@ -385,6 +407,11 @@ struct t2d_pool {
     t2d::TrackView track{};
     void* d_track = nullptr;
     std::vector<int32_t> track_n_tile;      // [E]
+    t2d::TrackGenView trackgen{};           // generated tracks (t2d_set_tracks_generated); tiles == nullptr: host-uploaded ones
+    int trackgen_sets = 0;
+    bool trackgen_regen = false;            // t2d_tracks_regenerate is allowed
+    bool trackgen_used = false;             // a regenerate launch since the last host synchronisation (its sticky word is read then)
+    bool trackgen_failed = false;
     // BEV camera (t2d_camera_config): the view, the library's own images, the device copy of the rings (one allocation) and
     // the geometry generation it was made of (geo_gen counts every change of the host rings / the scene mode)
     t2d::CameraView camera{};
@@ -506,6 +533,8 @@ hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hi
 hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s);
 // racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
 hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
+hipError_t launch_trackgen(const TrackGenView& g, int n, int mode, hipStream_t s);
+hipError_t launch_track_install(const PoolView& v, const TrackGenView& g, const int32_t* set_of_env, hipStream_t s);
 // BEV camera (t2d_camera.hip): the class and / or RGB image of every env (null: not written); naive = every pixel tests every element
 hipError_t launch_camera(const PoolView& v, const CameraView& cv, const TrackView& tv, uint8_t* out_class, uint8_t* out_rgb, int naive,
                          hipStream_t s);

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kBlock) void track_progress_kernel(PoolView pv, Tra
     const uchar4 pst = reinterpret_cast<const uchar4*>(pv.status)[e];
     const uint32_t flags = pv.flags[idx];
     const int cnt = pv.cnt_step[e];
-    const int t0 = tv.set_start[set], n = tv.set_start[set + 1] - t0;
+    const int t0 = tv.set_start[set], n = tv.n_tile[set];
     const float4* tiles = reinterpret_cast<const float4*>(tv.tiles) + 2 * (size_t)t0;
 
     const int visiting = restart ? start_visiting : visiting0;

@@ -300,13 +300,31 @@ class VecRacingEnv:
     tiles and a few steps without contact at the template's top speed (6.9 m per step, less than one 10 m tile) and is far
     below half of any generated ring, so a car that backs onto the tile behind it is not credited with a lap.
     check_off_road=True installs the tiles as lane geometry and ends an episode when the car leaves them (traffic status
-    OFF_LANE, reward -5; build-defined); False is the reference, whose off-road detector never fires."""
+    OFF_LANE, reward -5; build-defined); False is the reference, whose off-road detector never fires.
+
+    track_source="device": the tracks come from the device generator instead (t2d_set_tracks_generated, include/t2d.h): reset()
+    installs ONE TRACK PER ENV in one launch -- env e drives on the track of the counter stream (seed, e), first_track = 0;
+    reset(seed=...) re-keys -- and nothing but the tile counts crosses to the host (n_tracks is not used, `self.tracks` stays
+    empty; pool.generated_tracks() downloads them).  The stream is the build's own: these are not the tracks the host class
+    makes from numpy's stream.  new_track_per_episode=True (needs track_source="device" and auto_reset=True) is the
+    reference's RacingEnv.reset (racing.py:374-383): step() / step_torch() put one regenerate launch between the progress and
+    the restore launch, and a finished episode continues on a NEW track -- episode k of env e on the track of stream
+    (seed, e + k n_envs) -- at its start pose; infos["num_tile"] / step_torch's `num_tile` are then the device's own counts.
+    check_off_road=True needs the host's lane geometry and raises ValueError with track_source="device"."""
 
     _max_steer, _max_accel, _min_accel = 0.5, 2.0, -4.0   # envs/racing.py:24-26
 
     def __init__(self, n_envs, max_step=int(1e5), continuous=True, auto_reset=False, seed=0, n_tracks=1,
-                 progress_rule="forward", max_advance=8, check_off_road=False, device_id=0, observation="state"):
+                 progress_rule="forward", max_advance=8, check_off_road=False, device_id=0, observation="state",
+                 track_source="host", new_track_per_episode=False):
         self.observation = _check_observation(observation)
+        if track_source not in ("host", "device"):
+            raise ValueError(f"unknown track_source {track_source!r}")
+        if track_source == "device" and check_off_road:
+            raise ValueError("check_off_road is not supported with track_source='device' (the lane geometry is built on the host)")
+        if new_track_per_episode and not (track_source == "device" and auto_reset):
+            raise ValueError("new_track_per_episode needs track_source='device' and auto_reset=True")
+        self.track_source, self.new_track_per_episode = track_source, bool(new_track_per_episode)
         self.camera = None
         if progress_rule not in ("forward", "reference"):
             raise ValueError(f"unknown progress_rule {progress_rule!r}")
@@ -336,6 +354,8 @@ class VecRacingEnv:
         if not self._seeded:
             np.random.seed(self._seed)
             self._seeded = True
+        if self.track_source == "device":
+            return self._reset_device()
         gen = RacingTrackGenerator()
         length, width = VEHICLE_TEMPLATE["medium_car"][:2]
         tiles, poses, bounds = [], [], []
@@ -391,6 +411,40 @@ class VecRacingEnv:
             obs = self.camera.render_numpy()["image"]
         return obs, infos
 
+    def _reset_device(self):
+        """reset() with track_source="device": the pool is set up with placeholder poses and boundaries, then one generator
+        launch and one install launch put every env's track, boundary, start pose and snapshot in place on the device"""
+        from .participant import VEHICLE_TEMPLATE, vehicle_model
+        length, width = VEHICLE_TEMPLATE["medium_car"][:2]
+        E = self.n_envs
+        m = self.scenario_manager
+        ego = vehicle_model("medium_car", "kinematics", steer_range=(-self._max_steer, self._max_steer),
+                            accel_range=(self._min_accel, self._max_accel))
+        m.configure(ego.param_row(L.SHAPE_OBB, length, width)[None], check_dynamic=False, check_off_lane=False, check_arrival=0,
+                    check_no_action=1, no_action_max_step=100, shaped_reward=0)
+        m.status_checklist["out_bound"].reset(np.zeros((E, 4), np.float32))
+        m.status_checklist["off_lane"].lanes = None
+        m._lanes = None
+        m.pool.set_lane_geometry(None)
+        z = np.zeros(E)
+        m.reset(z, z, z, z, np.zeros(E, np.uint8))
+        m.pool.bind_actions(None, None)
+        m.pool.set_auto_reset(False)
+        m.pool.set_tracks_generated(E, self._seed, 0, E, None, 0, self.progress_rule, self.max_advance,
+                                    regenerate=self.new_track_per_episode, car_length=length)
+        self.tracks, self.generated = [], []
+        self.track_of_env = np.arange(E, dtype=np.int32)
+        self._t_views = None
+        self.num_tile = m.pool.track_n_tile
+        obs = m.get_observation()
+        st = np.tile(np.uint8([1, 1, 0, 0]), (E, 1))
+        infos = self._infos(obs, st, np.zeros(E, np.int32), np.ones(E, np.int32))
+        if self.observation == "camera":
+            from .sensor import BEVCamera
+            self.camera = BEVCamera(m.pool, (30, 30, 50, 10), CAMERA_WINDOW, 0, True, ("tracks", "participants", "arrows"))
+            obs = self.camera.render_numpy()["image"]
+        return obs, infos
+
     def _infos(self, obs, st, visiting, n_visited):
         return dict(state=dict(x=obs[:, 0], y=obs[:, 1], heading=obs[:, 2], speed=obs[:, 3], vx=obs[:, 4], vy=obs[:, 5]),
                     scenario_status=st[:, 0], traffic_status=st[:, 1], tile_visiting=visiting, num_visited_tile=n_visited,
@@ -427,10 +481,14 @@ class VecRacingEnv:
         m.pool.set_actions(a[:, 1], a[:, 0])
         m.pool.step(100)
         m.pool.track_progress(True)
+        if self.new_track_per_episode:
+            m.pool.regenerate_tracks()
         if self.auto_reset:
             m.pool.restore(done_only=True)
         m._flags_cache = None
         ts = m.pool.track_state()
+        if self.new_track_per_episode:
+            self.num_tile = ts["num_tile"]
         obs = m.get_observation()
         st = ts["status"]
         infos = self._infos(obs, st, ts["tile_visiting"], ts["num_visited"])
@@ -443,7 +501,7 @@ class VecRacingEnv:
         launch -> progress launch (-> t2d_restore of finished episodes with auto_reset), nothing is copied to the host and
         nothing synchronises.  Returns a dict of torch tensors that are ZERO-COPY VIEWS (valid until the next step / reset):
         x, y, heading, speed, vx, vy, reward, status (u8 [n, 4]: scenario, traffic, terminated, truncated), tile_visiting,
-        num_visited -- and with observation="camera" image (u8 [n, 200, 200, 3]) and image_class (u8 [n, 200, 200]).  Out-of-range actions are the caller's responsibility here."""
+        num_visited, num_tile -- and with observation="camera" image (u8 [n, 200, 200, 3]) and image_class (u8 [n, 200, 200]).  Out-of-range actions are the caller's responsibility here."""
         import torch
         if self.tracks is None:
             raise RuntimeError("call reset() first")
@@ -461,6 +519,8 @@ class VecRacingEnv:
             pool.bind_actions(base + 4, base, stride=2)
             pool.step(100, st.cuda_stream)
             pool.track_progress(True, st.cuda_stream)
+            if self.new_track_per_episode:
+                pool.regenerate_tracks(st.cuda_stream)
             if self.auto_reset:
                 pool.restore(done_only=True, stream=st.cuda_stream)
             if self._t_views is None:
@@ -468,7 +528,7 @@ class VecRacingEnv:
                 tv = pool.track_views()
                 self._t_views = dict(x=view(L.F_X), y=view(L.F_Y), heading=view(L.F_HEADING), speed=view(L.F_SPEED),
                                      vx=view(L.F_VX), vy=view(L.F_VY), reward=tv["reward"], status=tv["status"],
-                                     tile_visiting=tv["tile_visiting"], num_visited=tv["num_visited"])
+                                     tile_visiting=tv["tile_visiting"], num_visited=tv["num_visited"], num_tile=tv["num_tile"])
             cam = self.camera.render(st.cuda_stream) if self.observation == "camera" else {}
         self.scenario_manager._flags_cache = None
         out = dict(self._t_views)

@@ -210,8 +210,7 @@ class RacingTrackGenerator:
         self._bezier_interpolation = int(bezier_interpolation)
         self.max_tiles = int(max_tiles)
 
-    def _get_checkpoints(self):
-        rnd = np.random
+    def _get_checkpoints(self, rnd=np.random):
         n = rnd.randint(*self._n_checkpoint)
         noise = rnd.uniform(0, 2 * np.pi / n, n)
         alpha = 2 * np.pi * np.arange(n) / n + noise
@@ -275,11 +274,13 @@ class RacingTrackGenerator:
         ln, rn = np.roll(left, -1, axis=0), np.roll(right, -1, axis=0)
         return np.stack([left, ln, rn, right], 1)
 
-    def generate(self):
-        """One track from numpy's global random stream -> RacingTrack (fp64, the reference's coordinates)."""
+    def generate(self, rng=None):
+        """One track -> RacingTrack (fp64, the reference's coordinates).  rng: the draw source, an object with numpy's
+        `randint(low, high)` and `uniform(low, high, size=None)`; None is numpy's global random stream."""
+        rnd = np.random if rng is None else rng
         success = False
         while not success:
-            cp, control, success = self._get_checkpoints()
+            cp, control, success = self._get_checkpoints(rnd)
         n = cp.shape[1]
         start_point, start_id = self._get_start_point(n, control)
         center = self._get_center_line(start_point, start_id, cp, control)
@@ -291,3 +292,46 @@ class RacingTrackGenerator:
         tiles = self._get_tiles(n_tile, line)
         return RacingTrack(tiles, np.array([tiles[0, 1], tiles[0, 2]]), np.array([tiles[0, 0], tiles[0, 3]]), center,
                            start_point, n)
+
+    def generate_batch(self, n_tracks, seed, first_track=0, device=0):
+        """n_tracks tracks from the DEVICE generator (t2d_generate_tracks, one launch): track t of the batch is the track of the
+        counter stream (seed, first_track + t) -- the same track whatever the batch split -- already shifted to the centre of
+        its bounding box and rounded to fp32, as VecRacingEnv installs it.  The random stream is the build's own (include/
+        t2d.h), not numpy's: these are not the tracks `generate()` makes.  -> TrackBatch (host arrays)."""
+        import torch
+        n = int(n_tracks)
+        if n < 0 or int(first_track) < 0:
+            raise ValueError("n_tracks and first_track must be >= 0")
+        if self.max_tiles != L.MAX_TRACK_TILES:
+            raise ValueError("the device generator writes tracks of capacity T2D_MAX_TRACK_TILES")
+        dev = f"cuda:{int(device)}"
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        tiles, n_tile, n_cp, attempt = z((n, self.max_tiles, 4, 2), torch.float32), z(n, torch.int32), z(n, torch.int32), z(n, torch.int32)
+        pose, line, bound, flags = z((n, 3), torch.float64), z((n, 2, 2), torch.float32), z((n, 4), torch.float32), z(n, torch.int32)
+        _ffi.check(_ffi.lib().t2d_generate_tracks(int(device), n, int(seed) & (2**64 - 1), int(first_track),
+                                                  VEHICLE_TEMPLATE["medium_car"][0], tiles.data_ptr(), n_tile.data_ptr(),
+                                                  n_cp.data_ptr(), attempt.data_ptr(), pose.data_ptr(), line.data_ptr(),
+                                                  bound.data_ptr(), flags.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.current_stream(dev).synchronize()
+        nt = n_tile.cpu().numpy()
+        fl = flags.cpu().numpy().view(np.uint32)
+        keep = np.where(fl == 0, nt, 0)
+        host = [tiles[t, :int(keep[t])].cpu().numpy() for t in range(n)]
+        return TrackBatch(host, nt, n_cp.cpu().numpy(), attempt.cpu().numpy(), pose.cpu().numpy(), line.cpu().numpy(),
+                          bound.cpu().numpy(), fl)
+
+
+TRACK_CAPPED, TRACK_OVERFLOW = 1, 2     # T2D_TRACKGEN_CAPPED / T2D_TRACKGEN_OVERFLOW
+
+
+@dataclass
+class TrackBatch:
+    """What `RacingTrackGenerator.generate_batch` returns.  A flagged track (flags != 0) has no tiles."""
+    tiles: list                 # n arrays float32 [n_tile, 4, 2]
+    n_tile: np.ndarray          # (n,) int32
+    n_checkpoint: np.ndarray    # (n,) int32
+    attempt: np.ndarray         # (n,) int32 index of the accepted attempt, -1 when the cap was hit
+    start_pose: np.ndarray      # (n, 3) f64 x, y, heading in [0, 2 pi)
+    start_line: np.ndarray      # (n, 2, 2) f32
+    boundary: np.ndarray        # (n, 4) f32 xmin, xmax, ymin, ymax
+    flags: np.ndarray           # (n,) uint32 TRACK_CAPPED | TRACK_OVERFLOW

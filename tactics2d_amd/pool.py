@@ -114,6 +114,8 @@ class ParticipantPool:
         self.n_env, self.max_agents = int(n_env), int(max_agents)
         self.n = self.n_env * self.max_agents
         self.device_id = int(device_id)
+        # the installed racing tracks: tiles of each env's ring; whether they were generated on the device, and each env's set then
+        self.track_n_tile, self._tracks_generated, self.track_n_tile_set = None, False, None
         _ffi.check(self._lib.t2d_create(self.n_env, self.max_agents, self.device_id, C.byref(self._h)), None, self._lib)
 
     # ---------------------------------------------------------------- lifetime
@@ -434,6 +436,7 @@ class ParticipantPool:
         if tracks is None:
             self._ck(self._lib.t2d_set_tracks(self._h, 0, None, None, None, 0, 0, 0, 0))
             self.track_n_tile = None
+            self._tracks_generated = False
             return
         rules = {"reference": L.TRACK_RULE_REFERENCE, "forward": L.TRACK_RULE_FORWARD}
         if rule not in rules:
@@ -446,6 +449,69 @@ class ParticipantPool:
                                           int(max_advance), int(bool(check_off_road))))
         n = np.diff(off)
         self.track_n_tile = (n[se] if se is not None else np.full(self.n_env, n[0])).astype(np.int32)
+        self._tracks_generated = False
+
+    def set_tracks_generated(self, n_sets, seed, first_track=0, track_stride=None, set_of_env=None, ego_index=0, rule="forward",
+                             max_advance=8, regenerate=False, car_length=None, check_off_road=False):
+        """Generate n_sets racing tracks ON THE DEVICE and install them (t2d_set_tracks_generated): set s is the track of the
+        counter stream (seed, first_track + s) -- what RacingTrackGenerator.generate_batch returns for the same key; env e
+        drives on set_of_env[e] (None: n_sets == 1 -> track 0, n_sets == n_env -> its own).  Besides the tiles the call puts each
+        env's out-bound boundary, the ego's start pose (state columns and episode snapshot, speed 0) and the progress state of
+        track_reset() in place; only the tile counts come back to the host (`track_n_tile`).  Needs set_param_table, reset,
+        snapshot and a boundary array first.  regenerate=True (every env its own set, track_stride >= n_env, default n_env)
+        allows regenerate_tracks().  car_length: the ego's length (None: the medium car's).  Off-road detection needs the
+        host's lane geometry: check_off_road=True raises ValueError."""
+        if check_off_road:
+            raise ValueError("check_off_road is not supported with generated tracks (the lane geometry is built on the host)")
+        rules = {"reference": L.TRACK_RULE_REFERENCE, "forward": L.TRACK_RULE_FORWARD}
+        if rule not in rules:
+            raise ValueError(f"unknown progress rule {rule!r}")
+        if car_length is None:
+            from .participant import VEHICLE_TEMPLATE
+            car_length = VEHICLE_TEMPLATE["medium_car"][0]
+        se = _arr(set_of_env, np.int32, self.n_env, "set_of_env")
+        stride = self.n_env if track_stride is None else int(track_stride)
+        self._ck(self._lib.t2d_set_tracks_generated(self._h, int(n_sets), int(seed) & (2**64 - 1), int(first_track), stride,
+                                                    float(car_length), _p(se), int(ego_index), rules[rule], int(max_advance),
+                                                    int(bool(regenerate))))
+        self._tracks_generated = True
+        import torch
+        b, S = self.generated_track_buffers()      # (the call was synchronous) -- the tile counts alone cross to the host
+        n = torch.as_tensor(_DevArray(b["n_tile"], (S,), "<i4", self), device=f"cuda:{self.device_id}").cpu().numpy()
+        soe = se if se is not None else (np.zeros(self.n_env, np.int32) if int(n_sets) == 1 else np.arange(self.n_env))
+        self.track_n_tile = n[soe].astype(np.int32)
+        self.track_n_tile_set = np.asarray(soe, np.int64)
+
+    def regenerate_tracks(self, stream=None):
+        """One launch between track_progress(True) and restore(done_only=True) (t2d_tracks_regenerate): every env whose track
+        status says its episode ended gets the track of its next episode, generated in place into its own set, with its tile
+        count, boundary and snapshot start pose; asynchronous on `stream`.  Needs set_tracks_generated(regenerate=True)."""
+        self._ck(self._lib.t2d_tracks_regenerate(self._h, stream))
+
+    def generated_track_buffers(self):
+        """Device pointers of the generated track sets' records + their number: dict(tiles, n_tile, n_checkpoint, attempt,
+        start_pose, start_line, boundary, episode), n_sets."""
+        ptrs = [C.c_void_p() for _ in range(8)]
+        n = C.c_size_t()
+        self._ck(self._lib.t2d_generated_track_buffers(self._h, *[C.byref(q) for q in ptrs], C.byref(n)))
+        names = ("tiles", "n_tile", "n_checkpoint", "attempt", "start_pose", "start_line", "boundary", "episode")
+        return dict(zip(names, (q.value for q in ptrs))), int(n.value)
+
+    def generated_tracks(self, tiles=True):
+        """The generated track sets as numpy, after the pool's work: n_tile, n_checkpoint, attempt int32[n_sets], start_pose
+        f64[n_sets, 3], start_line f32[n_sets, 2, 2], boundary f32[n_sets, 4], episode int32[n_env] and (tiles=True) `tiles`, a
+        list of float32 [n_tile, 4, 2] arrays (the 64 KiB slot of every set is downloaded: a test / inspection helper)."""
+        import torch
+        self.sync()
+        b, S = self.generated_track_buffers()
+        dev = f"cuda:{self.device_id}"
+        shapes = dict(n_tile=((S,), "<i4"), n_checkpoint=((S,), "<i4"), attempt=((S,), "<i4"), start_pose=((S, 3), "<f8"),
+                      start_line=((S, 2, 2), "<f4"), boundary=((S, 4), "<f4"), episode=((self.n_env,), "<i4"))
+        out = {k: torch.as_tensor(_DevArray(b[k], sh, ts, self), device=dev).cpu().numpy() for k, (sh, ts) in shapes.items()}
+        if tiles:
+            t = torch.as_tensor(_DevArray(b["tiles"], (S, L.MAX_TRACK_TILES, 4, 2), "<f4", self), device=dev)
+            out["tiles"] = [t[s, :int(out["n_tile"][s])].cpu().numpy() for s in range(S)]
+        return out
 
     def _track_env_mask(self, env_mask):
         return None if env_mask is None else _arr(np.asarray(env_mask, bool), np.uint8, self.n_env, "env_mask")
@@ -478,7 +544,8 @@ class ParticipantPool:
         return dict(zip(("tile_visiting", "num_visited", "mask", "status", "reward"), (q.value for q in ptrs)))
 
     def track_views(self):
-        """Zero-copy torch views of track_buffers() (valid until set_tracks / close)."""
+        """Zero-copy torch views of track_buffers() (valid until set_tracks / close), and `num_tile` int32[n_env], the tiles
+        of each env's ring: a view of the device's counts when every env owns a generated set, else a gathered / uploaded copy."""
         import torch
         b, E, dev = self.track_buffers(), self.n_env, f"cuda:{self.device_id}"
         shapes = dict(tile_visiting=((E,), "<i4"), num_visited=((E,), "<i4"), mask=((E, L.TRACK_MASK_WORDS), "<u4"),
@@ -487,11 +554,20 @@ class ParticipantPool:
         out = {}
         for k, (shape, ts) in shapes.items():
             out[k] = torch.as_tensor(_DevArray(b[k], shape, "<i4" if ts == "<u4" else ts, self), device=dev)
+        # the tiles of each env's ring: the device's own counts for generated tracks (regeneration changes them), one per env
+        if self._tracks_generated:
+            g, S = self.generated_track_buffers()
+            n = torch.as_tensor(_DevArray(g["n_tile"], (S,), "<i4", self), device=dev)
+            own = S == E and np.array_equal(self.track_n_tile_set, np.arange(E))
+            out["num_tile"] = n if own else n[torch.as_tensor(self.track_n_tile_set, device=dev)]
+        else:
+            out["num_tile"] = torch.as_tensor(self.track_n_tile, device=dev)
         return out
 
     def track_state(self):
         """The progress results as numpy, after the pool's work: dict(tile_visiting int32[n_env], num_visited int32[n_env],
-        mask uint32[n_env, TRACK_MASK_WORDS], status uint8[n_env, 4], reward float32[n_env])."""
+        mask uint32[n_env, TRACK_MASK_WORDS], status uint8[n_env, 4], reward float32[n_env], num_tile int32[n_env]: the tiles
+        of each env's ring -- the device's own counts with generated tracks, which regeneration changes)."""
         self.sync()
         out = {k: v.cpu().numpy() for k, v in self.track_views().items()}
         out["mask"] = out["mask"].view(np.uint32)
