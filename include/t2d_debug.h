@@ -8,7 +8,7 @@
  *
  * The -DT2D_DEBUG_HOOKS build differs from the product in exactly: these entry points, tactics2d_amd/csrc/t2d_loop.hip, the
  * math probe (tactics2d_amd/csrc/t2d_math_probe.hip and t2d_math_probe_table.hip, which compile t2d_math.h once more and touch
- * no product kernel), and two reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
+ * no product kernel), the geometry probe (t2d_geom_probe.hip: t2d_geom_dev.h once more, likewise), and two reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
  */
 #ifndef T2D_DEBUG_H_
 #define T2D_DEBUG_H_
@@ -90,6 +90,32 @@ enum {
 #define T2D_MATH_MAX_N 16777216
 int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int64_t n, const double* a_host, const double* b_host,
                    double* out_host);
+
+/* ---- the device geometry predicates, one at a time (tactics2d_amd/csrc/t2d_geom_probe.hip; tests/test_gpu_geom.py) --------------
+ * Evaluates ONE predicate of tactics2d_amd/csrc/t2d_geom_dev.h over host arrays on device `device_id`, compiled with the product's
+ * flags.  Everything is fp64, so that a test can place vertices closer to each other than fp32 poses allow, and PLANAR: component j
+ * of element i at a_host[j * n + i] (b_host, out_host alike).  A quad is 8 components x0 y0 .. x3 y3, counter-clockwise; a triangle
+ * repeats vertex 0 as its fourth (what load_quad_f32 does).  Integer results come back as doubles.
+ *     fn                          a (components)       b (components)        outputs
+ *     SAT_QUADS                   quad A (8)           quad B (8)            0 / 1                  sat_quads(A, B)
+ *     RECT_PAIR_FILTER            rectangle A (8)      rectangle B (8)       0 / 1 / 2              rect_pair_filter(A, B)
+ *     RECT_VS_CONVEX_FILTER       rectangle A (8)      convex B (8)          0 / 1 / 2              rect_vs_convex_filter(A, B)
+ *     POINT_IN_QUAD               quad B (8)           point x y (2)         0 / 1                  point_in_quad(B, x, y)
+ *     SEG_DIST2                   p q c (6)            -- (may be NULL)      the double             seg_dist2(p, q, c)
+ *     PIECE_MEETS_QUAD_INTERIOR   quad P (8)           piece ax ay bx by (4) 0 / 1                  piece_meets_quad_interior(P, a, b)
+ *     IOU_TERMS                   quad A (8)           quad B (8)            10: the eight clipped_edge_term values in the order
+ *                                 quad_iou (t2d_collide.hip) forms and sums them -- s0..s3 = A's edges clipped to closed B (not
+ *                                 strict), s4..s7 = B's edges clipped to A (strict), origin A[0] --, then quad_area2(A), quad_area2(B)
+ * Element i is computed by lane i % 64 of wave i / 64 in workgroups of 256.  Synchronous; uses the device's default stream.  The
+ * outputs are filled with 0xff bytes before the launch: an element the kernel did not write reads as that NaN.
+ * Errors (the text: t2d_last_error(NULL)): T2D_ERR_INVALID for an unknown fn, n outside [1, T2D_GEOM_MAX_N], a null array (b_host of
+ * SEG_DIST2 excepted), an unknown device; T2D_ERR_HIP for a failing runtime call.                                                  */
+enum {
+    T2D_GEOM_SAT_QUADS = 0, T2D_GEOM_RECT_PAIR_FILTER = 1, T2D_GEOM_RECT_VS_CONVEX_FILTER = 2, T2D_GEOM_POINT_IN_QUAD = 3,
+    T2D_GEOM_SEG_DIST2 = 4, T2D_GEOM_PIECE_MEETS_QUAD_INTERIOR = 5, T2D_GEOM_IOU_TERMS = 6
+};
+#define T2D_GEOM_MAX_N 65536
+int t2d_debug_geom(int32_t device_id, int32_t fn, int64_t n, const double* a_host, const double* b_host, double* out_host);
 
 #ifdef __cplusplus
 }

@@ -511,3 +511,30 @@ def generate_parking_replay(tape_kind, tape_val, type_proportion=0.5, vehicle_si
     finally:
         lib().t2do_set_trig(0)
     return out, int(used), int(desync[0])
+
+
+# the geometry predicates over arrays (t2do_geom_batch; fn numbers = T2D_GEOM_* of include/t2d_debug.h)
+GEOM_FUNCTIONS = {"sat_quads": (0, 8, 8, 1), "point_in_quad": (3, 8, 2, 1), "seg_dist2": (4, 6, 0, 1),
+                  "piece_meets_quad_interior": (5, 8, 4, 1), "iou": (6, 8, 8, 2)}
+
+
+def geom(fn, a, b=None):
+    """The spec of one device predicate (tactics2d_amd/csrc/t2d_geom_dev.h) over fp64 arrays, one element per row: a = [n, 8]
+    quads (seg_dist2: [n, 6] = p, q, c), b = [n, 8] quads, [n, 2] points or [n, 4] pieces.  "sat_quads" = convex_intersects (a
+    quad whose last vertex repeats its first is passed as the triangle it is), "iou" = (quad_intersection_area2, quad_iou).
+    Returns fp64 [n], [2, n] for "iou"."""
+    code, na, nb, nout = GEOM_FUNCTIONS[fn]
+    a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, na).T)
+    n = a.shape[1]
+    bp = None
+    if nb:
+        b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1, nb).T)
+        assert b.shape[1] == n
+        bp = b.ctypes.data_as(C.c_void_p)
+    out = np.empty((nout, n), np.float64)
+    f = lib().t2do_geom_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_longlong, _f64p, C.c_void_p, _f64p]
+    if f(code, n, a.reshape(-1), bp, out.reshape(-1)) != 0:
+        raise ValueError(f"t2do_geom_batch refused {fn}")
+    return out[0] if nout == 1 else out

@@ -924,7 +924,8 @@ void t2do_collide(const double* rows, int row_stride, int n_env, int A, const fl
  * no_action.py:44-46: iou = intersection.area / union.area).  The reference delegates to GEOS
  * overlay (parity unpinned); this restatement integrates the boundary of A n B directly:
  * every edge of A is clipped to the closed polygon B, every edge of B to the OPEN side of A's
- * edge lines where they are parallel (so coincident boundary pieces count once), and
+ * edge lines where they are parallel (so coincident boundary pieces count once; a piece of A that
+ * runs along an edge of B in the opposite direction -- contact from outside -- counts not at all), and
  * 2*area = sum of cross(a - O, b - O) over the kept oriented pieces (Green's theorem), O = A[0].
  * Partial sums are combined in the fixed tree order the GPU uses.  Both quads CCW.
  * ---------------------------------------------------------------------------------------- */
@@ -940,7 +941,9 @@ static double clipped_edge_term(const double* p0, const double* p1, const double
         const double num = ex * (p0[1] - q0[1]) - ey * (p0[0] - q0[0]); /* inside <=> num + t*den >= 0 */
         const double den = ex * dy - ey * dx;
         if (den == 0.0) {
-            if (num < 0.0 || (strict && num == 0.0)) ok = 0;
+            /* on the line of a parallel edge: kept once (by the non-strict clip) when the two edges run the same
+             * way; when they run against each other the quads touch from outside along it -- no area, no piece */
+            if (num < 0.0 || ((strict || ex * dx + ey * dy < 0.0) && num == 0.0)) ok = 0;
         } else {
             const double tc = -num / den;
             if (den > 0.0) t0 = tc > t0 ? tc : t0;
@@ -1859,6 +1862,42 @@ int t2do_math_batch(int fn, long long n, const double* a, const double* b, doubl
             case 8: out[i] = t2do_log(a[i]); break;
             case 9: out[i] = t2do_exp(a[i]); break;
             default: out[i] = t2do_pow(a[i], b[i]); break;
+        }
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * The geometry predicates over arrays, one per call: what tests/test_gpu_geom.py holds the device
+ * code of tactics2d_amd/csrc/t2d_geom_dev.h against, and tests/test_geom_cases.py holds against
+ * exact rational arithmetic.  fn follows T2D_GEOM_* of include/t2d_debug.h; everything is PLANAR
+ * like the device probe: component j of element i at a[j * n + i].  The two certifying filters
+ * have no spec of their own: wherever they answer they promise t2do_convex_intersects, fn 0.
+ *   0 (1, 2 alike)  a = quad A, b = quad B            -> t2do_convex_intersects(A, 3 or 4, B, 3 or 4)
+ *   3               a = quad B, b = point              -> t2do_point_in_convex
+ *   4               a = p, q, c                        -> t2do_seg_dist2
+ *   5               a = quad P, b = piece ax ay bx by  -> t2do_piece_meets_quad_interior
+ *   6               a = quad A, b = quad B             -> t2do_quad_intersection_area2, t2do_quad_iou
+ * ---------------------------------------------------------------------------------------- */
+double t2do_seg_dist2(const double* p, const double* q, const double* c) { return seg_dist2(p, q, c); }
+
+int t2do_geom_batch(int fn, long long n, const double* a, const double* b, double* out) {
+    if (fn < 0 || fn > 6 || n < 0 || !a || !out || (fn != 4 && !b)) return -1;
+    for (long long i = 0; i < n; i++) {
+        double A[8], B[8];
+        const int na = fn == 4 ? 6 : 8, nb = fn == 4 ? 0 : (fn == 3 ? 2 : (fn == 5 ? 4 : 8));
+        for (int j = 0; j < na; j++) A[j] = a[j * n + i];
+        for (int j = 0; j < nb; j++) B[j] = b[j * n + i];
+        switch (fn) {
+            /* a triangle padded with its vertex 0 (load_quad_f32) is handed over as the triangle it is */
+            case 0: case 1: case 2: out[i] = t2do_convex_intersects(A, 4 - (A[6] == A[0] && A[7] == A[1]), B, 4 - (B[6] == B[0] && B[7] == B[1])); break;
+            case 3: out[i] = t2do_point_in_convex(A, 4 - (A[6] == A[0] && A[7] == A[1]), B); break;
+            case 4: out[i] = t2do_seg_dist2(A, A + 2, A + 4); break;
+            case 5: out[i] = t2do_piece_meets_quad_interior(B, A); break;
+            default:
+                out[i] = t2do_quad_intersection_area2(A, B);
+                out[n + i] = t2do_quad_iou(A, B);
+                break;
         }
     }
     return 0;

@@ -156,7 +156,8 @@ T2D_DEV bool piece_meets_quad_interior(const Quad& P, double ax, double ay, doub
 
 
 // ---- IoU of two convex quads (Arrival / NoAction), oracle t2do_quad_iou: the boundary of A n B is
-// integrated directly -- every edge of A clipped to closed B, every edge of B clipped to A with
+// integrated directly -- every edge of A clipped to closed B (a piece that runs along an edge of B in the
+// opposite direction dropped: contact from outside), every edge of B clipped to A with
 // coincident (parallel, on-the-line) pieces dropped -- and the 8 partial sums are combined in a
 // fixed tree order.  Out of line: only the ego lane of an env runs it.
 // Branch-free on purpose: the four clip parameters of a term -- and the 8 terms of an IoU -- are independent IEEE
@@ -175,7 +176,11 @@ T2D_DEV double clipped_edge_term(double p0x, double p0y, double p1x, double p1y,
         const double den = ex * dy - ey * dx;
         const double tc = -num / den;
         const bool par = den == 0.0;   // (bitwise, not short-circuit: no control flow)
-        ok = ok & !(par & ((num < 0.0) | (strict & (num == 0.0))));
+        // on the line of a parallel edge (num == 0): the piece counts once when both edges run the same way -- the interiors lie on
+        // the same side, the non-strict clip keeps it -- and not at all when they run against each other: the quads touch from
+        // outside along it, and a kept piece would be an open path whose term is twice a triangle's area, not zero
+        const bool against = ex * dx + ey * dy < 0.0;
+        ok = ok & !(par & ((num < 0.0) | ((strict | against) & (num == 0.0))));
         t0 = (!par & (den > 0.0) & (tc > t0)) ? tc : t0;
         t1 = (!par & (den < 0.0) & (tc < t1)) ? tc : t1;
     }

@@ -13,6 +13,7 @@ libt2d_hip.so exports no t2d_debug_* symbol.
     feedback_policy(pool, act, ...)   the stand-in policy kernel
     env_groups(scene, G) / ClosedLoop policy kernel -> t2d_step per env group, enqueued by one C call
     math(fn, a, b=None, table=False)  one device function of csrc/t2d_math.h over arrays (tests/test_gpu_math.py)
+    geom(fn, a, b=None)               one device predicate of csrc/t2d_geom_dev.h over arrays (tests/test_gpu_geom.py)
 """
 import ctypes as C
 import os
@@ -37,6 +38,7 @@ DEBUG_SYMBOLS = {
     "t2d_debug_closed_loop_destroy": (C.c_int, [_vp]),
     "t2d_debug_last_step_kernel": (C.c_char_p, []),
     "t2d_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
+    "t2d_debug_geom": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
 }
 
 _debug_lib = None
@@ -117,6 +119,30 @@ def math(fn, a, b=None, table=False, device_id=0):
     out = np.empty((nout, a.size), np.float64)
     rc = lib().t2d_debug_math(int(device_id), code, int(table), a.size, a.ctypes.data, None if b is None else b.ctypes.data,
                               out.ctypes.data)
+    _ffi.check(rc, None, lib())
+    return out[0] if nout == 1 else out
+
+
+# t2d_debug_geom's fn (include/t2d_debug.h: T2D_GEOM_*) -> (code, components of a, components of b, outputs)
+GEOM_FUNCTIONS = {"sat_quads": (0, 8, 8, 1), "rect_pair_filter": (1, 8, 8, 1), "rect_vs_convex_filter": (2, 8, 8, 1),
+                  "point_in_quad": (3, 8, 2, 1), "seg_dist2": (4, 6, 0, 1), "piece_meets_quad_interior": (5, 8, 4, 1),
+                  "iou_terms": (6, 8, 8, 10)}
+GEOM_MAX_N = 65536
+
+
+def geom(fn, a, b=None, device_id=0):
+    """t2d_debug_geom: the device predicate `fn` of csrc/t2d_geom_dev.h (a key of GEOM_FUNCTIONS) over fp64 arrays, one element
+    per row: a = [n, 8] quads x0 y0 .. x3 y3 (seg_dist2: [n, 6] = p, q, c), b = [n, 8] quads, [n, 2] points or [n, 4] pieces (the
+    header's table).  Element i runs in lane i % 64 of wave i // 64.  Returns fp64 [n] -- [10, n] for iou_terms."""
+    code, na, nb, nout = GEOM_FUNCTIONS[fn]
+    a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, na).T)
+    n = a.shape[1]
+    if nb:
+        b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1, nb).T)
+        if b.shape[1] != n:
+            raise ValueError("a and b differ in length")
+    out = np.empty((nout, n), np.float64)
+    rc = lib().t2d_debug_geom(int(device_id), code, n, a.ctypes.data, b.ctypes.data if nb else None, out.ctypes.data)
     _ffi.check(rc, None, lib())
     return out[0] if nout == 1 else out
 
