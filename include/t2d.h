@@ -872,6 +872,93 @@ int t2d_generated_track_buffers(t2d_pool* pool, void** tiles_dev, void** n_tile_
                                 void** start_pose_dev, void** start_line_dev, void** boundary_dev, void** episode_dev,
                                 size_t* n_sets);
 
+/* Reeds-Shepp curves and the parking tutorial's planner on the device.
+ *
+ * The curve family is ReedsShepp of interpolator/reeds_shepp.py: get_all_path (:495-527) normalises the goal into the start
+ * frame in units of the radius and returns T2D_RS_SLOTS = 48 slots in a fixed order -- _CSC 0-7 (:207-257), _CCC 8-19
+ * (:259-312), _CCCC 20-27 (:314-374), _CCSC 28-43 (:376-449), _CCSCC 44-47 (:451-493) -- each None or a ReedsSheppPath
+ * whose `segments`, `signs` and `length` are those of :19-44.  get_path (:529-558) keeps the LAST of several equal shortest
+ * lengths; the tutorial's planner pops a heap of (length, index) and so takes the LOWEST index.
+ *   t2d_rs_slot_info  the constants of one slot, host only (no device needed): letters[5] +1 L / -1 R / 0 S, signs[5] the
+ *                     `signs` of its paths, zero padded both; n_seg; curve_type 0 CSC, 1 CCC, 2 CCCC, 3 CCSC, 4 CCSCC.
+ *   t2d_rs_paths      get_all_path for n independent queries in ONE launch, asynchronous on hip_stream, no pool:
+ *                     start_dev / goal_dev f64 [n][3] (x, y, heading; device memory) and one radius ->
+ *                     valid_dev u64 [n] (bit s: slot s is a path), segments_dev f64 [n][48][5] (signs[i] * segments[i], in
+ *                     units of the radius, zero padded, all zero for None), length_dev f64 [n][48] (metres, +inf for None),
+ *                     shortest_dev i32 [n][2]: get_path's slot, then the lowest-index shortest one (-1: no slot is a
+ *                     path, as for a query that is not finite).  T2D_ERR_INVALID for radius <= 0 (ReedsShepp.__init__
+ *                     :153-156 raises ValueError), n < 0 or a null pointer: nothing is launched.
+ *
+ * The planner is cell 9 of docs/tutorial/train_parking_demo.ipynb for the ego of every env, one launch:
+ *   get_rs_path          both poses shifted to the rear axle (ego: the state columns; goal: the mean of the target quad's
+ *                        four vertices and the target heading, read from the device copies of t2d_set_target_areas /
+ *                        t2d_set_target_headings or of the generated scenes); no plan beyond threshold_distance;
+ *                        candidates in ascending (length, slot) up to length_ratio x the shortest; the first whose
+ *                        swept box crosses no obstacle edge is the plan.
+ *   construct_obstacles  the scan clipped to [0, max_range] (+inf: max_range), minus distance_tolerance, floored at
+ *                        vehicle_base[k]; point k at angle k * pi / n_beams * 2, shifted by center_shift in x; n_beams edges
+ *                        joining consecutive points in a closed chain; edges that touch the box at the goal are dropped.
+ *   is_traj_valid        the LINES of the box's four edges against the line of every chain edge; a hit is an intersection
+ *                        point within both edges' coordinate ranges +- edge_tolerance; parallel lines never hit.
+ * BUILD-DEFINED: (1) sampling -- segment i of a path is checked at the arc lengths k * sample_step, k = 0 .. ceil(len_i /
+ * sample_step), the last one clipped to len_i, so every segment's start and end pose is checked (the reference's arcs come
+ * from its compiled Circle.get_arc, omit their end point and take their yaw from a linspace); a path of more than
+ * T2D_RS_MAX_POSES poses is not checked: status T2D_RS_UNCHECKED, the plan stops there.  (2) the goal box of
+ * construct_obstacles stands at the goal IN THE FRAME OF THE CHAIN (the ego's rear axle); the notebook passes the world-frame
+ * pose there, which is that frame only for an ego at the origin.  (3) all arithmetic is fp64 on the fp32 scan values (numpy
+ * keeps `lidar_obs - distance_tolerance` in fp32).  (4) a NaN scan value gives T2D_RS_UNCHECKED for that env.
+ *   t2d_rs_config   cfg: see t2d_rs_params (all finite; radius, half_length, half_width, sample_step > 0, length_ratio >= 1,
+ *                   the others >= 0; T2D_ERR_INVALID otherwise).  vehicle_base_host: n_beams floats (RSPlanner.
+ *                   init_vehicle_base: the distance from the box centre to the box outline along each beam), or NULL: computed
+ *                   from half_length / half_width.  Needs t2d_lidar_config (T2D_ERR_STATE) with at most T2D_RS_MAX_BEAMS beams
+ *                   (T2D_ERR_INVALID); takes its beam count and range.  Allocates the pool's own plan records.
+ *                   The chain is built at the angles k * 2 pi / n_beams: a lidar configured with beam tables that are not
+ *                   those angles (to 1e-9 in sin and cos) is refused with T2D_ERR_STATE, here and in t2d_rs_plan.
+ *   t2d_rs_plan     one launch, asynchronous on hip_stream, no host synchronisation: behind t2d_step + t2d_lidar_scan on the
+ *                   same stream it plans from that step's poses and scan.  lidar_dev: f32 [n_env][n_beams] device memory, or
+ *                   NULL = the pool's T2D_F_LIDAR buffer.  out_dev: t2d_rs_plan_record [n_env] (8-byte aligned), or NULL =
+ *                   the pool's own records.  T2D_ERR_STATE before t2d_rs_config, after the lidar's beam count changed,
+ *                   before t2d_reset, and without target areas and headings.  kernel_id T2D_PROFILE_RS_PLAN in t2d_profile_read.
+ *   t2d_rs_plan_buffers  pointer and size in bytes of the pool's own records; T2D_ERR_STATE before t2d_rs_config.
+ * Rows that cannot plan: an inactive ego, or a pose / target that is not finite: T2D_RS_NO_TARGET.                      */
+#define T2D_RS_SLOTS 48
+#define T2D_RS_MAX_SEGMENTS 5
+#define T2D_RS_MAX_POSES 1024
+#define T2D_RS_MAX_BEAMS 1024
+#define T2D_RS_NO_TARGET 0   /* the ego is inactive, or its pose or the target is not finite */
+#define T2D_RS_FAR 1         /* the goal is farther than threshold_distance */
+#define T2D_RS_FOUND 2
+#define T2D_RS_NONE_FREE 3   /* every candidate within length_ratio x the shortest crosses an obstacle edge */
+#define T2D_RS_UNCHECKED 4   /* a NaN in the scan (slot -1), or the candidate `slot` has more than T2D_RS_MAX_POSES poses */
+#define T2D_PROFILE_RS_PLAN 13
+typedef struct t2d_rs_params {
+    double radius;              /* wheel_base / tan(steer_ratio * steer_hi) */
+    double center_shift;        /* length / 2 - rear_overhang: box centre ahead of the rear axle */
+    double half_length, half_width;
+    double distance_tolerance;  /* 0.05 */
+    double threshold_distance;  /* lidar_range - 5 */
+    double sample_step;         /* 0.1 */
+    double length_ratio;        /* 2 */
+    double edge_tolerance;      /* 1e-4 */
+} t2d_rs_params;
+typedef struct t2d_rs_plan_record {   /* 96 bytes */
+    int32_t status;             /* T2D_RS_* */
+    int32_t slot;               /* the chosen slot (T2D_RS_FOUND), the unchecked one, or -1 */
+    int32_t n_seg;              /* segments of that slot, else 0 */
+    int32_t n_visited;          /* candidates visited */
+    int32_t steer[T2D_RS_MAX_SEGMENTS];   /* per segment +1 L / -1 R / 0 S */
+    int32_t reserved;
+    double distance[T2D_RS_MAX_SEGMENTS]; /* per segment the signed distance in metres (what RSAgent.calculate_target_points consumes) */
+    double length;              /* of the chosen slot, NaN without one */
+    double shortest;            /* the shortest candidate's length, NaN for NO_TARGET / FAR */
+} t2d_rs_plan_record;
+int t2d_rs_slot_info(int32_t slot, int8_t* letters, int8_t* signs, int32_t* n_seg, int32_t* curve_type);
+int t2d_rs_paths(int32_t device_id, int32_t n, double radius, const double* start_dev, const double* goal_dev, uint64_t* valid_dev,
+                 double* segments_dev, double* length_dev, int32_t* shortest_dev, void* hip_stream);
+int t2d_rs_config(t2d_pool* pool, const t2d_rs_params* cfg, const float* vehicle_base_host);
+int t2d_rs_plan(t2d_pool* pool, const float* lidar_dev, t2d_rs_plan_record* out_dev, void* hip_stream);
+int t2d_rs_plan_buffers(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
+
 /* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
  * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
  *
@@ -1023,7 +1110,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
- * (t2d_tracks_regenerate).                                       */
+ * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

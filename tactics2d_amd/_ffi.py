@@ -45,6 +45,12 @@ class FrameLayout(C.Structure):
                [("n_env", C.c_int32), ("n_beams", C.c_int32)]
 
 
+class RSParams(C.Structure):
+    """t2d_rs_params (include/t2d.h)."""
+    _fields_ = [(k, C.c_double) for k in ("radius", "center_shift", "half_length", "half_width", "distance_tolerance",
+                                          "threshold_distance", "sample_step", "length_ratio", "edge_tolerance")]
+
+
 # every symbol include/t2d.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -116,6 +122,11 @@ SYMBOLS = {
                                            C.c_int32, C.c_int32]),
     "t2d_tracks_regenerate": (C.c_int, [_vp, _vp]),
     "t2d_generated_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 8 + [C.POINTER(C.c_size_t)]),
+    "t2d_rs_slot_info": (C.c_int, [C.c_int32, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "t2d_rs_paths": (C.c_int, [C.c_int32, C.c_int32, C.c_double] + [_vp] * 7),
+    "t2d_rs_config": (C.c_int, [_vp, C.POINTER(RSParams), _vp]),
+    "t2d_rs_plan": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "t2d_rs_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "t2d_camera_config": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                     C.c_uint32, C.c_uint32]),
     "t2d_camera_set_palette": (C.c_int, [_vp, _vp, C.c_int32]),

@@ -584,6 +584,8 @@ int t2d_destroy(t2d_pool* p) {
         if (b) (void)hipFree(b);
     frame_release(p);
     if (p->d_target_heading) (void)hipFree(p->d_target_heading);
+    if (p->d_rs_beam_tab) (void)hipFree(p->d_rs_beam_tab);
+    if (p->d_rs_plan) (void)hipFree(p->d_rs_plan);
     if (p->comm && rccl().ok) (void)rccl().CommDestroy((ncclComm_t)p->comm);
     if (p->gather_stream) (void)hipStreamDestroy(p->gather_stream);
     if (p->ev_frag_ready) (void)hipEventDestroy(p->ev_frag_ready);
@@ -2146,10 +2148,13 @@ int t2d_lidar_config(t2d_pool* p, int32_t n_beams, float max_range, int32_t incl
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
     std::vector<double> bs(n_beams), bc(n_beams);
+    bool regular = true;   // the beams stand at k * 2 pi / n_beams (what t2d_rs_config builds its obstacle chain on)
     for (int k = 0; k < n_beams; ++k) {
         if (beam_sin) {
             bs[k] = beam_sin[k];
             bc[k] = beam_cos[k];
+            const double th = (double)k * ((2.0 * 3.141592653589793) / (double)n_beams);
+            regular = regular && fabs(bs[k] - sin(th)) <= 1e-9 && fabs(bc[k] - cos(th)) <= 1e-9;
         } else {  // linspace(0, 2 pi, n, endpoint=False) = k * (2 pi / n)
             const double th = (double)k * ((2.0 * 3.141592653589793) / (double)n_beams);
             bs[k] = sin(th);
@@ -2194,6 +2199,7 @@ int t2d_lidar_config(t2d_pool* p, int32_t n_beams, float max_range, int32_t incl
     p->lidar.n_beams = n_beams;
     p->lidar.include_participants = include_participants != 0;
     p->lidar_on = true;
+    p->lidar_regular = regular;
     rc = rebuild_lidar_geo(p);
     if (rc != T2D_OK) return rc;
     return T2D_OK;
@@ -2239,6 +2245,92 @@ int t2d_lidar_all_buffer(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
         return fail(p, T2D_ERR_STATE, "a t2d_lidar_scan_all with a NULL destination must precede t2d_lidar_all_buffer");
     *dev_ptr = p->d_lidar_all;
     *nbytes = p->lidar_all_bytes;
+    return T2D_OK;
+}
+
+int t2d_rs_config(t2d_pool* p, const t2d_rs_params* cfg, const float* vehicle_base_host) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!cfg) return fail(p, T2D_ERR_INVALID, "t2d_rs_config: null configuration");
+    const double vals[9] = {cfg->radius, cfg->center_shift, cfg->half_length, cfg->half_width, cfg->distance_tolerance,
+                            cfg->threshold_distance, cfg->sample_step, cfg->length_ratio, cfg->edge_tolerance};
+    for (double v : vals)
+        if (!std::isfinite(v)) return fail(p, T2D_ERR_INVALID, "t2d_rs_config: every value must be finite");
+    if (!(cfg->radius > 0.0 && cfg->half_length > 0.0 && cfg->half_width > 0.0 && cfg->sample_step > 0.0 && cfg->length_ratio >= 1.0 &&
+          cfg->distance_tolerance >= 0.0 && cfg->threshold_distance >= 0.0 && cfg->edge_tolerance >= 0.0))
+        return fail(p, T2D_ERR_INVALID, "t2d_rs_config: need radius, half_length, half_width, sample_step > 0, length_ratio >= 1 "
+                                        "and tolerances / threshold >= 0");
+    if (!p->lidar_on) return fail(p, T2D_ERR_STATE, "t2d_lidar_config must precede t2d_rs_config");
+    if (!p->lidar_regular)
+        return fail(p, T2D_ERR_STATE, "t2d_rs_config: the lidar's beam tables are not the angles k * 2 pi / n_beams the planner's chain is built on");
+    const int n = p->lidar.n_beams;
+    if (n > T2D_RS_MAX_BEAMS) return fail(p, T2D_ERR_INVALID, "t2d_rs_config: the planner takes at most 1024 beams");
+    T2D_HIP(p, hipSetDevice(p->device));
+    T2D_HIP(p, quiesce(p));
+    // per beam: cos, sin of np.arange(n) * np.pi / n * 2 (cell 9 :164) and vehicle_base (init_vehicle_base :23-44)
+    std::vector<double> tab(3 * (size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const double th = (double)k * 3.141592653589793 / (double)n * 2.0;
+        const double cs = cos(th), sn = sin(th);
+        tab[3 * (size_t)k] = cs;
+        tab[3 * (size_t)k + 1] = sn;
+        if (vehicle_base_host) {
+            tab[3 * (size_t)k + 2] = (double)vehicle_base_host[k];
+        } else {   // the ray from the centre leaves the box through the nearer of the two pairs of sides
+            const double dx = fabs(cs) > 0.0 ? cfg->half_length / fabs(cs) : INFINITY;
+            const double dy = fabs(sn) > 0.0 ? cfg->half_width / fabs(sn) : INFINITY;
+            tab[3 * (size_t)k + 2] = dx < dy ? dx : dy;
+        }
+        if (!std::isfinite(tab[3 * (size_t)k + 2])) return fail(p, T2D_ERR_INVALID, "t2d_rs_config: vehicle_base must be finite");
+    }
+    int rc;
+    if ((rc = dev_replace(p, &p->d_rs_beam_tab, tab.data(), tab.size()))) return rc;
+    if (!p->d_rs_plan) {
+        T2D_HIP(p, hipMalloc((void**)&p->d_rs_plan, (size_t)p->v.n_env * sizeof(t2d_rs_plan_record)));
+        T2D_HIP(p, hipMemset(p->d_rs_plan, 0, (size_t)p->v.n_env * sizeof(t2d_rs_plan_record)));
+    }
+    p->rs.cfg = *cfg;
+    p->rs.lidar_range = p->lidar.max_range;
+    p->rs.beam_tab = p->d_rs_beam_tab;
+    p->rs.n_beams = n;
+    p->rs_on = true;
+    return T2D_OK;
+}
+
+int t2d_rs_plan(t2d_pool* p, const float* lidar_dev, t2d_rs_plan_record* out_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->rs_on) return fail(p, T2D_ERR_STATE, "t2d_rs_config must precede t2d_rs_plan");
+    if (!p->lidar_on || !p->lidar_regular || p->lidar.n_beams != p->rs.n_beams || p->lidar.max_range != p->rs.lidar_range)
+        return fail(p, T2D_ERR_STATE, "the lidar configuration changed: call t2d_rs_config again");
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_rs_plan");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(p, T2D_ERR_INVALID, "t2d_rs_plan: out_dev must be 8-byte aligned");
+    t2d::RsPlanView rv = p->rs;
+    if (p->scene_mode) {
+        rv.target_xy = nullptr;
+        rv.target_quads = p->scene.live.target;
+        rv.target_heading = p->scene.live.target_heading;
+    } else {
+        rv.target_xy = p->have_target ? p->d_target_xy : nullptr;
+        rv.target_quads = nullptr;
+        rv.target_heading = p->d_target_heading;
+    }
+    if ((!rv.target_xy && !rv.target_quads) || !rv.target_heading)
+        return fail(p, T2D_ERR_STATE, "t2d_rs_plan needs target areas and target headings");
+    rv.ego_index = p->status_cfg.ego_index;
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc;
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_RS_PLAN, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_rs_plan(p->v, rv, lidar_dev ? lidar_dev : (const float*)p->field_ptr[T2D_F_LIDAR],
+                                   out_dev ? out_dev : p->d_rs_plan, s));
+    return record_event(p, T2D_PROFILE_RS_PLAN, s, false);
+}
+
+int t2d_rs_plan_buffers(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!dev_ptr || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->rs_on) return fail(p, T2D_ERR_STATE, "t2d_rs_config must precede t2d_rs_plan_buffers");
+    *dev_ptr = p->d_rs_plan;
+    *nbytes = (size_t)p->v.n_env * sizeof(t2d_rs_plan_record);
     return T2D_OK;
 }
 

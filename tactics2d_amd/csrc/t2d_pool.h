@@ -319,6 +319,17 @@ struct CameraView {
     uint8_t class_of_type[T2D_MAX_TYPES];
 };
 
+// The Reeds-Shepp planner (t2d_rs.hip): the configuration of t2d_rs_config and where a plan launch reads the target from.
+struct RsPlanView {
+    t2d_rs_params cfg;
+    double lidar_range;            // the scan is clipped to it (t2d_lidar_config's max_range)
+    const double* beam_tab;        // [n_beams][3] cos, sin of k * pi / n_beams * 2 and vehicle_base[k]
+    const double* target_xy;       // [E][8] the pool's target quads, or
+    const float* target_quads;     // [E][8] the generated scenes' live ones (then target_xy is not read)
+    const double* target_heading;  // [E]
+    int32_t n_beams, ego_index;
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -379,6 +390,7 @@ struct t2d_pool {
     bool have_target = false;
     // lidar (row f2)
     bool lidar_on = false;
+    bool lidar_regular = true;   // the configured beams are linspace(0, 2 pi, n_beams, endpoint=False) to 1e-9 (t2d_rs_config needs that)
     t2d::LidarView lidar{};
     int32_t *d_lidar_env_off = nullptr, *d_lidar_next = nullptr;
     uint8_t* d_lidar_meta = nullptr;
@@ -497,6 +509,11 @@ struct t2d_pool {
     bool act_in_frame = false;        // v.act0 / v.act1 point into d_actions / the mapped h_actions (set by t2d_step_host)
     int64_t act_extent = 0;       // elements readable behind each bound action pointer (t2d_set_action_extent; 0 = not declared)
     double* d_target_heading = nullptr;
+    // Reeds-Shepp planner (t2d_rs_config): the view, its beam table and the pool's own plan records
+    bool rs_on = false;
+    t2d::RsPlanView rs{};
+    double* d_rs_beam_tab = nullptr;
+    t2d_rs_plan_record* d_rs_plan = nullptr;
     // profiling
     bool profiling = false;
     static constexpr int kMaxProfSteps = 4096;
@@ -538,6 +555,8 @@ hipError_t launch_track_install(const PoolView& v, const TrackGenView& g, const 
 // BEV camera (t2d_camera.hip): the class and / or RGB image of every env (null: not written); naive = every pixel tests every element
 hipError_t launch_camera(const PoolView& v, const CameraView& cv, const TrackView& tv, uint8_t* out_class, uint8_t* out_rgb, int naive,
                          hipStream_t s);
+// Reeds-Shepp planner (t2d_rs.hip): one plan record per env from the scan [n_env][n_beams]
+hipError_t launch_rs_plan(const PoolView& v, const RsPlanView& rv, const float* scan, t2d_rs_plan_record* out, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

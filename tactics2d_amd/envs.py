@@ -73,7 +73,7 @@ class VecParkingEnv:
 
     def __init__(self, n_envs, max_step=int(2e4), continuous=True, auto_reset=False, seed=0, device_id=0,
                  scene_source="layout", type_proportion=0.5, info_lidar=True, copy=True, zero_copy=None, lidar_beams=360,
-                 observation="state"):
+                 observation="state", rs_planner=False):
         """scene_source: "generator" = the device-side ParkingLotGenerator (tactics2d_amd.generator; bay and
         parallel scenes with the reference's rejection sampler, `type_proportion` as in envs/parking.py:331-333),
         "layout" = the fixed bay layout of scenarios.parking (BASELINE config 2).
@@ -91,8 +91,12 @@ class VecParkingEnv:
         8 B per env of the actions would cross PCIe inside the step kernel).
         observation: "state" = the ego's 6-vector; "camera" = the reference's observation, the uint8 [200, 200, 3] image of a
         BEVCamera with perception_range (20, 20, 20, 20) bound to the agent (envs/parking.py:130, :306-308): reset() and step()
-        return [n_envs, 200, 200, 3] arrays (downloaded: 120 KB per env), step_torch() adds `image` / `image_class`."""
+        return [n_envs, 200, 200, 3] arrays (downloaded: 120 KB per env), step_torch() adds `image` / `image_class`.
+        rs_planner: step_torch() adds `rs_plan`, the tutorial's Reeds-Shepp plan of every env (planner.RSPlanner: dict of views
+        of the plan records), one launch behind the scan on the same stream."""
         self.observation = _check_observation(observation)
+        self.rs_planner = bool(rs_planner)
+        self.planner = None
         if scene_source not in ("layout", "generator"):
             raise ValueError(f"unknown scene_source {scene_source!r}")
         self.scene_source = scene_source
@@ -162,6 +166,10 @@ class VecParkingEnv:
         self._moving_targets = self.scene_source == "generator" and self.auto_reset
         m.pool.frame_config(lidar=self.info_lidar, target=self._moving_targets, zero_copy=self.zero_copy)
         self._target_area, self._target_heading = self._scene.target, self._scene.target_heading
+        if self.rs_planner:
+            from .planner import RSPlanner
+            # RSPlanner(scenario_manager.agent, lidar_num, lidar_range)  tutorial cell 9; the ego is a medium_car with steer_range 0.524
+            self.planner = RSPlanner(m.pool, "medium_car", lidar_range=20.0, steer_hi=0.524)
         fr = m.pool.frame_fetch(fresh=self.copy)
         fr = self._last = fr.copy() if self.copy_always else fr
         if self.observation == "camera":
@@ -244,8 +252,11 @@ class VecParkingEnv:
                                      iou=view(L.F_IOU))
             pool.lidar_scan(self._t_lidar.data_ptr(), st.cuda_stream)
             cam = self.camera.render(st.cuda_stream) if self.observation == "camera" else {}
+            plan = self.planner.plan(self._t_lidar, st) if self.planner is not None else None
         out = dict(self._t_views)
         out["lidar"] = self._t_lidar
+        if plan is not None:
+            out["rs_plan"] = plan
         out.update(cam)   # image, image_class: the poses (and, with regenerated scenes, the lots) the returned state shows
         return out
 

@@ -55,6 +55,11 @@ CAMERA_CLASS_BACKGROUND, CAMERA_CLASS_LANE, CAMERA_CLASS_OBSTACLE, CAMERA_CLASS_
 CAMERA_CLASS_VEHICLE, CAMERA_CLASS_CYCLIST, CAMERA_CLASS_PEDESTRIAN, CAMERA_CLASS_HEADING_ARROW = 4, 5, 6, 7
 CAMERA_N_CLASS = 8
 PROFILE_CAMERA = 11          # kernel id of t2d_camera_render in t2d_profile_read
+# Reeds-Shepp curves and planner (t2d_rs_paths / t2d_rs_plan): sizes, the plan's status values, the record's size in bytes
+RS_SLOTS, RS_MAX_SEGMENTS, RS_MAX_POSES, RS_MAX_BEAMS = 48, 5, 1024, 1024
+RS_NO_TARGET, RS_FAR, RS_FOUND, RS_NONE_FREE, RS_UNCHECKED = range(5)
+RS_RECORD_BYTES = 96
+PROFILE_RS_PLAN = 13         # kernel id of t2d_rs_plan in t2d_profile_read
 # IDM controller parameter sets (t2d_set_idm)
 IDM_DESIRED_SPEED, IDM_TIME_HEADWAY, IDM_MIN_SPACING, IDM_MAX_ACCEL, IDM_COMF_DECEL, IDM_DELTA = range(6)
 IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7

@@ -229,6 +229,42 @@ class ParticipantPool:
         self.sync()
         return torch.as_tensor(view, device=f"cuda:{self.device_id}").cpu().numpy()
 
+    # ---------------------------------------------------------------- Reeds-Shepp planner
+    def rs_config(self, radius, center_shift, half_length, half_width, distance_tolerance=0.05, threshold_distance=15.0,
+                  sample_step=0.1, length_ratio=2.0, edge_tolerance=1e-4, vehicle_base=None):
+        """t2d_rs_config: the tutorial planner's configuration (docs/tutorial/train_parking_demo.ipynb cell 9; planner.RSPlanner
+        derives it from a vehicle template).  Needs lidar_config; vehicle_base: n_beams floats or None (computed from the box)."""
+        cfg = _ffi.RSParams(radius, center_shift, half_length, half_width, distance_tolerance, threshold_distance, sample_step,
+                            length_ratio, edge_tolerance)
+        vb = _arr(vehicle_base, np.float32, getattr(self, "n_beams", None), "vehicle_base")
+        self._ck(self._lib.t2d_rs_config(self._h, C.byref(cfg), _p(vb)))
+        self.rs_params = cfg
+
+    def rs_plan(self, lidar_ptr=None, out_ptr=None, stream=None):
+        """t2d_rs_plan: one plan record per env (layout.RS_RECORD_BYTES each) from the scan at lidar_ptr (None: the pool's own
+        lidar buffer) into out_ptr (None: the pool's own records, rs_plan_views()).  Asynchronous on `stream`."""
+        self._ck(self._lib.t2d_rs_plan(self._h, lidar_ptr, out_ptr, stream))
+
+    def rs_plan_buffer(self):
+        """(device pointer, bytes) of the pool's own plan records"""
+        ptr, nb = C.c_void_p(), C.c_size_t()
+        self._ck(self._lib.t2d_rs_plan_buffers(self._h, C.byref(ptr), C.byref(nb)))
+        return ptr.value, nb.value
+
+    def rs_plan_views(self, ptr=None, owner=None):
+        """Zero-copy torch views of t2d_rs_plan_record [n_env] at `ptr` (None: the pool's own records): status, slot, n_seg,
+        n_visited int32 [n]; steer int32 [n, 5] (+1 L, -1 R, 0 S); distance float64 [n, 5] (signed, metres); length, shortest
+        float64 [n]."""
+        import torch
+        if ptr is None:
+            ptr = self.rs_plan_buffer()[0]
+        dev, n = f"cuda:{self.device_id}", self.n_env
+        keep = owner if owner is not None else self
+        i32 = torch.as_tensor(_DevArray(ptr, (n, L.RS_RECORD_BYTES // 4), "<i4", keep), device=dev)
+        f64 = torch.as_tensor(_DevArray(ptr, (n, L.RS_RECORD_BYTES // 8), "<f8", keep), device=dev)
+        return dict(status=i32[:, 0], slot=i32[:, 1], n_seg=i32[:, 2], n_visited=i32[:, 3], steer=i32[:, 4:9],
+                    distance=f64[:, 5:10], length=f64[:, 10], shortest=f64[:, 11])
+
     def set_idm(self, ctrl_rows, ctrl_id):
         """Install IDM controllers: ctrl_rows [n_ctrl, 8] (layout.IDM_*), ctrl_id [n] uint8 (IDM_NONE =
         action supplied by the caller).  ctrl_rows=None uninstalls."""
