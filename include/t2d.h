@@ -959,6 +959,82 @@ int t2d_rs_config(t2d_pool* pool, const t2d_rs_params* cfg, const float* vehicle
 int t2d_rs_plan(t2d_pool* pool, const float* lidar_dev, t2d_rs_plan_record* out_dev, void* hip_stream);
 int t2d_rs_plan_buffers(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
 
+/* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
+ * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
+ * over the action row of an env while a path is being executed and leaves the policy's row alone otherwise.
+ *
+ * State per env, struct-of-arrays in pool-owned device memory (one array per field, contiguous over envs): the adopted
+ * segments (at most T2D_RS_MAX_SEGMENTS: steer +1 / 0 / -1, signed distance, target point x / y / yaw, arc centre, start
+ * point) with the index of the head, the last distance_to_go (+inf: none), and prev_error / integral / target of the velocity,
+ * acceleration and steer controller.  One call does for env e, in this order:
+ *   1. episode end = agent.reset(): if the env's status word left by the last step says terminated or truncated (the
+ *      condition of t2d_restore(mode 1) and of the fused auto-reset, which keeps that status readable until the next step),
+ *      path, last distance and the controllers' prev_error / integral are cleared.
+ *   2. adopt = RSAgent.plan -> calculate_target_points: if no path is held and the env's plan record reads T2D_RS_FOUND with
+ *      1 .. T2D_RS_MAX_SEGMENTS segments, the target points are chained over steer[i] / distance[i] from the ego's pose moved to
+ *      the rear axle by dr, with the notebook's three branches as written.  While a path is held the record is not read.
+ *   3. act = RSAgent.get_action: distance_to_go d to the head's target; the head is popped if d < reach_radius or (last < d and
+ *      d < rising_radius), once per call (last := +inf on a pop, else d); nothing left: the action is (0, 0) and the path is
+ *      finished.  Otherwise velocity PID on -d * sign(distance) clipped to +-max_speed, acceleration PID on the speed clipped to
+ *      +-max_acceleration, arc or line error + yaw_weight * wrapped yaw error, steer PID, steer * steer_ratio + delta clipped to
+ *      +-1; the normalised action is (target_steer, target_a / max_acceleration).  Controller state survives pops and a path's
+ *      end; only 1. clears it.
+ *   4. the action row (steering, accel): executing -> the normalised action through the tutorial wrapper's _preprocess_action for
+ *      the symmetric box (+-steer_bound, +-accel_bound) in fp32 and in its order (round to fp32, clip to +-1,
+ *      * (high - low) / 2 + (high + low) / 2); otherwise the policy's row, bit for bit.
+ * All arithmetic is fp64 on the pool's fp32 state columns, with the library's own sincos / atan2.
+ * BUILD-DEFINED: (a) a non-finite x / y / heading / speed of an active ego, or a computed action that is not finite (the
+ * notebook's zero-length S segment divides 0 by 0 when it is the head), drops the env's path, raises T2D_RS_FOLLOW_DROPPED and
+ * passes the policy's row through; the controllers keep the state they had before that call: a NaN never reaches the step from
+ * here.  (b) an inactive ego neither adopts nor acts.  (c) there is no timeout: a follower that never reaches its target keeps
+ * executing until the episode ends, as the notebook's does; t2d_rs_follow_reset with a mask drops paths.
+ *   t2d_rs_follow_config   all values finite; radius, max_speed, max_acceleration, reach_radius, rising_radius, steer_bound,
+ *                          accel_bound > 0 (T2D_ERR_INVALID otherwise); T2D_ERR_STATE before t2d_rs_config.  Allocates and clears
+ *                          the state and the pool's own records.
+ *   t2d_rs_follow          one launch, asynchronous on hip_stream, no host synchronisation.  plan_dev: t2d_rs_plan_record [n_env]
+ *                          or NULL = the pool's own plan records; act_in_dev / act_out_dev: f32 [n_env][2] (steering, accel),
+ *                          may be the same memory; act_in_dev NULL = zeros; out_dev: t2d_rs_follow_record [n_env] (8-byte
+ *                          aligned) or NULL = the pool's own.  T2D_ERR_STATE before t2d_rs_follow_config or t2d_reset,
+ *                          T2D_ERR_INVALID without act_out_dev.  kernel_id T2D_PROFILE_RS_FOLLOW in t2d_profile_read.
+ *   t2d_rs_follow_reset    agent.reset() for the envs whose mask byte (device memory) is non-zero, NULL = all; asynchronous on
+ *                          hip_stream.  A t2d_reset without a mask and t2d_parking_scenes do the same for every env.
+ *   t2d_rs_follow_buffers  pointer and size in bytes of the pool's own records.                                          */
+#define T2D_RS_FOLLOW_ADOPTED 1u       /* a plan was adopted in this call */
+#define T2D_RS_FOLLOW_POP_REACHED 2u   /* the head was popped: d < reach_radius */
+#define T2D_RS_FOLLOW_POP_RISING 4u    /* the head was popped: last < d < rising_radius */
+#define T2D_RS_FOLLOW_FINISHED 8u      /* the last segment was popped: the action is (0, 0) */
+#define T2D_RS_FOLLOW_RESET 16u        /* the episode ended in the last step: agent.reset() */
+#define T2D_RS_FOLLOW_DROPPED 32u      /* non-finite input or result: the path was dropped */
+#define T2D_PROFILE_RS_FOLLOW 14
+typedef struct t2d_rs_follow_params {
+    double radius;                  /* execute_radius: the planner's radius */
+    double dr;                      /* rear axle behind the centre: the planner's center_shift */
+    double steer_ratio;             /* 0.98 */
+    double max_speed;               /* 0.5 */
+    double max_acceleration;        /* 2.0 */
+    double kp_v, ki_v, kd_v;        /* velocity controller: 0.8, 0, 0 */
+    double kp_a, ki_a, kd_a;        /* acceleration controller: 2.0, 0, 0 */
+    double kp_s, ki_s, kd_s;        /* steer controller: 5.0, 0, 0 */
+    double yaw_weight;              /* 0.5 */
+    double reach_radius;            /* 0.02 */
+    double rising_radius;           /* 0.1 */
+    double steer_bound, accel_bound;   /* the env's action box, rounded to fp32: 0.524, 2.0 */
+} t2d_rs_follow_params;
+typedef struct t2d_rs_follow_record {   /* 48 bytes */
+    int32_t executing;              /* segments left after the call */
+    int32_t segment;                /* index of the head within the adopted plan, -1 without a path */
+    uint32_t events;                /* T2D_RS_FOLLOW_* of this call */
+    int32_t steps;                  /* calls that acted on the path since its adoption, this one included */
+    double action[2];               /* the normalised action (steer, accel), NaN when the policy's row went through */
+    double distance_to_go;          /* to the head's target (to the last popped one in a finishing call), else NaN */
+    double total_error;             /* what the steer controller saw, else NaN */
+} t2d_rs_follow_record;
+int t2d_rs_follow_config(t2d_pool* pool, const t2d_rs_follow_params* cfg);
+int t2d_rs_follow(t2d_pool* pool, const t2d_rs_plan_record* plan_dev, const float* act_in_dev, float* act_out_dev,
+                  t2d_rs_follow_record* out_dev, void* hip_stream);
+int t2d_rs_follow_reset(t2d_pool* pool, const uint8_t* mask_dev, void* hip_stream);
+int t2d_rs_follow_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
+
 /* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
  * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
  *
@@ -1110,7 +1186,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
- * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan).  */
+ * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -51,6 +51,13 @@ class RSParams(C.Structure):
                                           "threshold_distance", "sample_step", "length_ratio", "edge_tolerance")]
 
 
+class RSFollowParams(C.Structure):
+    """t2d_rs_follow_params (include/t2d.h)."""
+    _fields_ = [(k, C.c_double) for k in ("radius", "dr", "steer_ratio", "max_speed", "max_acceleration", "kp_v", "ki_v", "kd_v",
+                                          "kp_a", "ki_a", "kd_a", "kp_s", "ki_s", "kd_s", "yaw_weight", "reach_radius",
+                                          "rising_radius", "steer_bound", "accel_bound")]
+
+
 # every symbol include/t2d.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -127,6 +134,10 @@ SYMBOLS = {
     "t2d_rs_config": (C.c_int, [_vp, C.POINTER(RSParams), _vp]),
     "t2d_rs_plan": (C.c_int, [_vp, _vp, _vp, _vp]),
     "t2d_rs_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "t2d_rs_follow_config": (C.c_int, [_vp, C.POINTER(RSFollowParams)]),
+    "t2d_rs_follow": (C.c_int, [_vp] * 6),
+    "t2d_rs_follow_reset": (C.c_int, [_vp, _vp, _vp]),
+    "t2d_rs_follow_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "t2d_camera_config": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                     C.c_uint32, C.c_uint32]),
     "t2d_camera_set_palette": (C.c_int, [_vp, _vp, C.c_int32]),

@@ -586,6 +586,9 @@ int t2d_destroy(t2d_pool* p) {
     if (p->d_target_heading) (void)hipFree(p->d_target_heading);
     if (p->d_rs_beam_tab) (void)hipFree(p->d_rs_beam_tab);
     if (p->d_rs_plan) (void)hipFree(p->d_rs_plan);
+    if (p->rs_follow.f64) (void)hipFree(p->rs_follow.f64);
+    if (p->rs_follow.i32) (void)hipFree(p->rs_follow.i32);
+    if (p->d_rs_follow_rec) (void)hipFree(p->d_rs_follow_rec);
     if (p->comm && rccl().ok) (void)rccl().CommDestroy((ncclComm_t)p->comm);
     if (p->gather_stream) (void)hipStreamDestroy(p->gather_stream);
     if (p->ev_frag_ready) (void)hipEventDestroy(p->ev_frag_ready);
@@ -898,6 +901,7 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
     // (an armed auto-reset may put the snapshot's ids back into any env from the next step on)
     p->types_used = types_used | (p->auto_reset ? p->snap_types : 0u);
     p->have_reset = true;
+    if (!partial && p->rs_follow_on) return t2d_rs_follow_reset(p, nullptr, nullptr);   // new episodes everywhere: agent.reset()
     return T2D_OK;
 }
 
@@ -1645,6 +1649,7 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     p->v.snap_ids = p->d_snap_ids;
     p->v.snap_omega[0] = p->v.snap_omega[1] = nullptr;
     p->v.auto_reset = p->auto_reset ? 1 : 0;
+    if (p->rs_follow_on) return t2d_rs_follow_reset(p, nullptr, nullptr);
     return T2D_OK;
 }
 
@@ -2331,6 +2336,77 @@ int t2d_rs_plan_buffers(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
     if (!p->rs_on) return fail(p, T2D_ERR_STATE, "t2d_rs_config must precede t2d_rs_plan_buffers");
     *dev_ptr = p->d_rs_plan;
     *nbytes = (size_t)p->v.n_env * sizeof(t2d_rs_plan_record);
+    return T2D_OK;
+}
+
+static int rs_follow_clear(t2d_pool* p) {
+    const size_t E = (size_t)p->v.n_env;
+    T2D_HIP(p, hipMemset(p->rs_follow.f64, 0, (size_t)t2d::kRfF64Rows * E * sizeof(double)));
+    T2D_HIP(p, hipMemset(p->rs_follow.i32, 0, (size_t)t2d::kRfI32Rows * E * sizeof(int32_t)));
+    T2D_HIP(p, hipMemset(p->d_rs_follow_rec, 0, E * sizeof(t2d_rs_follow_record)));
+    std::vector<double> inf(E, INFINITY);   // distance_record is empty
+    T2D_HIP(p, hipMemcpy(p->rs_follow.f64 + (size_t)t2d::kRfLast * E, inf.data(), E * sizeof(double), hipMemcpyHostToDevice));
+    return T2D_OK;
+}
+
+int t2d_rs_follow_config(t2d_pool* p, const t2d_rs_follow_params* cfg) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!cfg) return fail(p, T2D_ERR_INVALID, "t2d_rs_follow_config: null configuration");
+    const double* vals = reinterpret_cast<const double*>(cfg);
+    for (size_t k = 0; k < sizeof(*cfg) / sizeof(double); ++k)
+        if (!std::isfinite(vals[k])) return fail(p, T2D_ERR_INVALID, "t2d_rs_follow_config: every value must be finite");
+    if (!(cfg->radius > 0.0 && cfg->max_speed > 0.0 && cfg->max_acceleration > 0.0 && cfg->reach_radius > 0.0 &&
+          cfg->rising_radius > 0.0 && cfg->steer_bound > 0.0 && cfg->accel_bound > 0.0))
+        return fail(p, T2D_ERR_INVALID, "t2d_rs_follow_config: need radius, max_speed, max_acceleration, reach_radius, rising_radius, "
+                                        "steer_bound, accel_bound > 0");
+    if (!p->rs_on) return fail(p, T2D_ERR_STATE, "t2d_rs_config must precede t2d_rs_follow_config");
+    T2D_HIP(p, hipSetDevice(p->device));
+    T2D_HIP(p, quiesce(p));
+    const size_t E = (size_t)p->v.n_env;
+    if (!p->rs_follow.f64) T2D_HIP(p, hipMalloc((void**)&p->rs_follow.f64, (size_t)t2d::kRfF64Rows * E * sizeof(double)));
+    if (!p->rs_follow.i32) T2D_HIP(p, hipMalloc((void**)&p->rs_follow.i32, (size_t)t2d::kRfI32Rows * E * sizeof(int32_t)));
+    if (!p->d_rs_follow_rec) T2D_HIP(p, hipMalloc((void**)&p->d_rs_follow_rec, E * sizeof(t2d_rs_follow_record)));
+    int rc;
+    if ((rc = rs_follow_clear(p))) return rc;
+    p->rs_follow.cfg = *cfg;
+    p->rs_follow_on = true;
+    return T2D_OK;
+}
+
+int t2d_rs_follow(t2d_pool* p, const t2d_rs_plan_record* plan_dev, const float* act_in_dev, float* act_out_dev,
+                  t2d_rs_follow_record* out_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->rs_follow_on) return fail(p, T2D_ERR_STATE, "t2d_rs_follow_config must precede t2d_rs_follow");
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_rs_follow");
+    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, "t2d_rs_follow: act_out_dev is required");
+    if ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(plan_dev)) & 7u)
+        return fail(p, T2D_ERR_INVALID, "t2d_rs_follow: plan_dev and out_dev must be 8-byte aligned");
+    t2d::RsFollowView fv = p->rs_follow;
+    fv.ego_index = p->status_cfg.ego_index;
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc;
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_RS_FOLLOW, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_rs_follow(p->v, fv, plan_dev ? plan_dev : p->d_rs_plan, act_in_dev, act_out_dev,
+                                     out_dev ? out_dev : p->d_rs_follow_rec, s));
+    return record_event(p, T2D_PROFILE_RS_FOLLOW, s, false);
+}
+
+int t2d_rs_follow_reset(t2d_pool* p, const uint8_t* mask_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->rs_follow_on) return fail(p, T2D_ERR_STATE, "t2d_rs_follow_config must precede t2d_rs_follow_reset");
+    hipStream_t s = (hipStream_t)hip_stream;
+    touch(p, s);
+    T2D_HIP(p, t2d::launch_rs_follow_reset(p->v, p->rs_follow, mask_dev, s));
+    return T2D_OK;
+}
+
+int t2d_rs_follow_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->rs_follow_on) return fail(p, T2D_ERR_STATE, "t2d_rs_follow_config must precede t2d_rs_follow_buffers");
+    *records_dev = p->d_rs_follow_rec;
+    *nbytes = (size_t)p->v.n_env * sizeof(t2d_rs_follow_record);
     return T2D_OK;
 }
 

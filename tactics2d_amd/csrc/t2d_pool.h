@@ -330,6 +330,19 @@ struct RsPlanView {
     int32_t n_beams, ego_index;
 };
 
+// The Reeds-Shepp path follower (t2d_rs_follow.hip): its configuration and its struct-of-arrays state, row r of a table = n_env
+// consecutive values.  f64 rows: the last distance_to_go; target / prev_error / integral of the velocity, acceleration and steer
+// controller; per segment its signed distance, target x / y / yaw, arc centre x / y (NaN on a line) and start x / y.  i32 rows:
+// segments of the adopted plan, index of the head (executing: head < n_seg), calls since adoption, per segment the steer sign.
+constexpr int kRfLast = 0, kRfPid = 1, kRfSeg = 10, kRfSegFields = 8, kRfF64Rows = kRfSeg + kRfSegFields * T2D_RS_MAX_SEGMENTS;
+constexpr int kRfNSeg = 0, kRfHead = 1, kRfSteps = 2, kRfSteer = 3, kRfI32Rows = kRfSteer + T2D_RS_MAX_SEGMENTS;
+struct RsFollowView {
+    t2d_rs_follow_params cfg;
+    double* f64;      // [kRfF64Rows][n_env]
+    int32_t* i32;     // [kRfI32Rows][n_env]
+    int32_t ego_index;
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -514,6 +527,10 @@ struct t2d_pool {
     t2d::RsPlanView rs{};
     double* d_rs_beam_tab = nullptr;
     t2d_rs_plan_record* d_rs_plan = nullptr;
+    // Reeds-Shepp path follower (t2d_rs_follow_config): the view, its state tables and the pool's own records
+    bool rs_follow_on = false;
+    t2d::RsFollowView rs_follow{};
+    t2d_rs_follow_record* d_rs_follow_rec = nullptr;
     // profiling
     bool profiling = false;
     static constexpr int kMaxProfSteps = 4096;
@@ -557,6 +574,10 @@ hipError_t launch_camera(const PoolView& v, const CameraView& cv, const TrackVie
                          hipStream_t s);
 // Reeds-Shepp planner (t2d_rs.hip): one plan record per env from the scan [n_env][n_beams]
 hipError_t launch_rs_plan(const PoolView& v, const RsPlanView& rv, const float* scan, t2d_rs_plan_record* out, hipStream_t s);
+// Reeds-Shepp path follower (t2d_rs_follow.hip): one action row and one record per env; agent.reset() for the masked envs (null: all)
+hipError_t launch_rs_follow(const PoolView& v, const RsFollowView& fv, const t2d_rs_plan_record* plan, const float* act_in,
+                            float* act_out, t2d_rs_follow_record* out, hipStream_t s);
+hipError_t launch_rs_follow_reset(const PoolView& v, const RsFollowView& fv, const uint8_t* mask, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,

@@ -73,7 +73,7 @@ class VecParkingEnv:
 
     def __init__(self, n_envs, max_step=int(2e4), continuous=True, auto_reset=False, seed=0, device_id=0,
                  scene_source="layout", type_proportion=0.5, info_lidar=True, copy=True, zero_copy=None, lidar_beams=360,
-                 observation="state", rs_planner=False):
+                 observation="state", rs_planner=False, rs_follow=False):
         """scene_source: "generator" = the device-side ParkingLotGenerator (tactics2d_amd.generator; bay and
         parallel scenes with the reference's rejection sampler, `type_proportion` as in envs/parking.py:331-333),
         "layout" = the fixed bay layout of scenarios.parking (BASELINE config 2).
@@ -93,10 +93,18 @@ class VecParkingEnv:
         BEVCamera with perception_range (20, 20, 20, 20) bound to the agent (envs/parking.py:130, :306-308): reset() and step()
         return [n_envs, 200, 200, 3] arrays (downloaded: 120 KB per env), step_torch() adds `image` / `image_class`.
         rs_planner: step_torch() adds `rs_plan`, the tutorial's Reeds-Shepp plan of every env (planner.RSPlanner: dict of views
-        of the plan records), one launch behind the scan on the same stream."""
+        of the plan records), one launch behind the scan on the same stream.
+        rs_follow (needs rs_planner): the tutorial's hybrid policy.  step_torch() puts the path follower (planner.RSFollower, the
+        notebook's RSAgent) in front of the step: an env that holds a path, or whose last plan was found, is stepped with the
+        follower's action, the others with the caller's; `actions` itself is never written.  The result gains `action` (float32
+        [n, 2]: what was stepped) and `rs_follow` (the follower's record views); reset() clears the follower and ends with a scan
+        and a plan of the reset state, so the first step has a record to adopt."""
         self.observation = _check_observation(observation)
         self.rs_planner = bool(rs_planner)
-        self.planner = None
+        self.rs_follow = bool(rs_follow)
+        if self.rs_follow and not self.rs_planner:
+            raise ValueError("rs_follow=True needs rs_planner=True")
+        self.planner = self.follower = None
         if scene_source not in ("layout", "generator"):
             raise ValueError(f"unknown scene_source {scene_source!r}")
         self.scene_source = scene_source
@@ -170,6 +178,17 @@ class VecParkingEnv:
             from .planner import RSPlanner
             # RSPlanner(scenario_manager.agent, lidar_num, lidar_range)  tutorial cell 9; the ego is a medium_car with steer_range 0.524
             self.planner = RSPlanner(m.pool, "medium_car", lidar_range=20.0, steer_hi=0.524)
+        if self.rs_follow:
+            # agent.reset(); choose_action(info0, ...)  tutorial cell 18: a cleared follower and a plan of the reset state
+            import torch
+            from .planner import RSFollower
+            self.follower = RSFollower(m.pool, self.planner)
+            dev = torch.device("cuda", self.device_id)
+            self._t_lidar = torch.empty((self.n_envs, self.lidar_beams), dtype=torch.float32, device=dev)
+            self._t_views = None
+            st = torch.cuda.current_stream(dev)
+            m.pool.lidar_scan(self._t_lidar.data_ptr(), st.cuda_stream)
+            self.planner.plan(self._t_lidar, st)
         fr = m.pool.frame_fetch(fresh=self.copy)
         fr = self._last = fr.copy() if self.copy_always else fr
         if self.observation == "camera":
@@ -241,11 +260,13 @@ class VecParkingEnv:
             if actions.dtype != torch.float32 or tuple(actions.shape) != (self.n_envs, 2):
                 raise ValueError(f"actions must be float32 [{self.n_envs}, 2]")
             self._act = actions if actions.is_contiguous() else actions.contiguous()
-            base = self._act.data_ptr()
+            follow = self.follower.follow(self._act, stream=st) if self.follower is not None else None
+            base = self._act.data_ptr() if follow is None else follow["action_rows"].data_ptr()
             pool.bind_actions(base + 4, base, stride=2)
             pool.step(100, st.cuda_stream)
-            if getattr(self, "_t_lidar", None) is None or self._t_lidar.device != dev:
-                self._t_lidar = torch.empty((self.n_envs, self.lidar_beams), dtype=torch.float32, device=dev)
+            if getattr(self, "_t_lidar", None) is None or self._t_lidar.device != dev or getattr(self, "_t_views", None) is None:
+                if getattr(self, "_t_lidar", None) is None or self._t_lidar.device != dev:
+                    self._t_lidar = torch.empty((self.n_envs, self.lidar_beams), dtype=torch.float32, device=dev)
                 view = lambda f: torch.as_tensor(pool.device_array(f), device=dev)
                 self._t_views = dict(x=view(L.F_X), y=view(L.F_Y), heading=view(L.F_HEADING), speed=view(L.F_SPEED),
                                      vx=view(L.F_VX), vy=view(L.F_VY), reward=view(L.F_REWARD), status=view(L.F_STATUS),
@@ -257,6 +278,9 @@ class VecParkingEnv:
         out["lidar"] = self._t_lidar
         if plan is not None:
             out["rs_plan"] = plan
+        if follow is not None:
+            out["action"] = follow.pop("action_rows")
+            out["rs_follow"] = follow
         out.update(cam)   # image, image_class: the poses (and, with regenerated scenes, the lots) the returned state shows
         return out
 

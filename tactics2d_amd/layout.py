@@ -60,6 +60,11 @@ RS_SLOTS, RS_MAX_SEGMENTS, RS_MAX_POSES, RS_MAX_BEAMS = 48, 5, 1024, 1024
 RS_NO_TARGET, RS_FAR, RS_FOUND, RS_NONE_FREE, RS_UNCHECKED = range(5)
 RS_RECORD_BYTES = 96
 PROFILE_RS_PLAN = 13         # kernel id of t2d_rs_plan in t2d_profile_read
+# Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
+RS_FOLLOW_RECORD_BYTES = 48
+RS_FOLLOW_ADOPTED, RS_FOLLOW_POP_REACHED, RS_FOLLOW_POP_RISING, RS_FOLLOW_FINISHED, RS_FOLLOW_RESET, RS_FOLLOW_DROPPED = \
+    1, 2, 4, 8, 16, 32
+PROFILE_RS_FOLLOW = 14
 # IDM controller parameter sets (t2d_set_idm)
 IDM_DESIRED_SPEED, IDM_TIME_HEADWAY, IDM_MIN_SPACING, IDM_MAX_ACCEL, IDM_COMF_DECEL, IDM_DELTA = range(6)
 IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7

@@ -2,8 +2,9 @@
 
 RSPlanner.plan() is RSPlanner.get_rs_path of the notebook for the ego of every env in one launch of t2d_rs_plan
 (include/t2d.h): candidates from the ego's rear axle to the target pose, obstacle edges from the lidar scan, the first
-candidate in ascending (length, slot) whose swept box crosses no edge.  Following the chosen path (the notebook's RSAgent) is
-not part of it.  There is no CPU path.
+candidate in ascending (length, slot) whose swept box crosses no edge.  RSFollower.follow() is the notebook's RSAgent (cells 14
+and 17) for the ego of every env in one launch of t2d_rs_follow: it adopts a found plan, and while a path is being executed it
+replaces the env's action row by the PID follower's.  There is no CPU path.
 """
 import numpy as np
 
@@ -65,3 +66,65 @@ class RSPlanner:
             self._views = pool.rs_plan_views(self._out.data_ptr(), owner=self._out)
         pool.rs_plan(None if lidar is None else lidar.data_ptr(), self._out.data_ptr(), st.cuda_stream)
         return self._views
+
+
+FOLLOW_EVENTS = ("adopted", "pop_reached", "pop_rising", "finished", "reset", "dropped")   # bit k: layout.RS_FOLLOW_*
+
+
+def rs_follow_params(planner_params, steer_ratio=0.98, max_speed=0.5, max_acceleration=2.0, steer_bound=0.524, accel_bound=2.0):
+    """The configuration of the notebook's RSAgent (cell 17 and cell 20: execute_radius = the planner's radius, dr = its
+    center_shift), its three PIDController gains, its thresholds, and the action box of the wrapper (cell 7)."""
+    return dict(radius=planner_params["radius"], dr=planner_params["center_shift"], steer_ratio=steer_ratio, max_speed=max_speed,
+                max_acceleration=max_acceleration, kp_v=0.8, ki_v=0.0, kd_v=0.0, kp_a=2.0, ki_a=0.0, kd_a=0.0, kp_s=5.0, ki_s=0.0,
+                kd_s=0.0, yaw_weight=0.5, reach_radius=0.02, rising_radius=0.1, steer_bound=steer_bound, accel_bound=accel_bound)
+
+
+class RSFollower:
+    """pool: the ParticipantPool of `planner` (an RSPlanner, whose radius and center_shift it takes).  follow() returns zero-copy
+    torch views of the follower's records (ParticipantPool.rs_follow_views) beside the action rows it wrote."""
+
+    def __init__(self, pool, planner, **overrides):
+        self.pool, self.planner = pool, planner
+        self.params = rs_follow_params(planner.params)
+        unknown = set(overrides) - set(self.params)
+        if unknown:
+            raise TypeError(f"unknown follower options {sorted(unknown)}")
+        self.params.update(overrides)
+        self._rec = self._views = self._act = None
+        pool.rs_follow_config(**self.params)
+
+    def follow(self, actions, plan=None, out=None, stream=None):
+        """actions: float32 CUDA tensor [n_env, 2] (steering, accel), the policy's rows (None: zeros), never written unless it is
+        also `out`; plan: the dict RSPlanner.plan() returned (None: its last one, or the pool's own records if it never planned);
+        out: float32 [n_env, 2] tensor for the rows to step (None: a buffer of the follower's own).  Asynchronous on `stream`.
+        Returns dict(action_rows, executing, segment, events, steps, action, distance_to_go, total_error), valid until the
+        next follow()."""
+        import torch
+        pool = self.pool
+        dev = torch.device("cuda", pool.device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        for t in (actions, out):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n_env, 2) or not t.is_contiguous()):
+                raise ValueError(f"action rows must be a contiguous float32 [{pool.n_env}, 2] tensor")
+        if self._rec is None:
+            self._rec = torch.zeros((pool.n_env, L.RS_FOLLOW_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
+            self._views = pool.rs_follow_views(self._rec.data_ptr(), owner=self._rec)
+            self._act = torch.zeros((pool.n_env, 2), dtype=torch.float32, device=dev)
+        rows = self._act if out is None else out
+        if plan is not None:
+            plan_ptr = plan["status"].data_ptr()   # (the record's first word)
+        else:
+            plan_ptr = self.planner._out.data_ptr() if self.planner._out is not None else None
+        pool.rs_follow(None if actions is None else actions.data_ptr(), rows.data_ptr(), plan_ptr, self._rec.data_ptr(), st.cuda_stream)
+        return dict(self._views, action_rows=rows)
+
+    def reset(self, mask=None, stream=None):
+        """agent.reset() for the envs where `mask` (a uint8 / bool CUDA tensor [n_env]) is non-zero; None: every env"""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.pool.device_id))
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+            if tuple(mask.shape) != (self.pool.n_env,):
+                raise ValueError(f"mask must have {self.pool.n_env} elements")
+            self._mask = mask   # (kept alive until the launch has run)
+        self.pool.rs_follow_reset(None if mask is None else mask.data_ptr(), st.cuda_stream)

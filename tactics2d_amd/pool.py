@@ -265,6 +265,39 @@ class ParticipantPool:
         return dict(status=i32[:, 0], slot=i32[:, 1], n_seg=i32[:, 2], n_visited=i32[:, 3], steer=i32[:, 4:9],
                     distance=f64[:, 5:10], length=f64[:, 10], shortest=f64[:, 11])
 
+    # ---------------------------------------------------------------- Reeds-Shepp path follower
+    def rs_follow_config(self, **params):
+        """t2d_rs_follow_config: the tutorial follower's configuration (_ffi.RSFollowParams, every field by name; planner.RSFollower
+        supplies the notebook's defaults).  Needs rs_config; allocates and clears the follower's state."""
+        cfg = _ffi.RSFollowParams(**params)
+        self._ck(self._lib.t2d_rs_follow_config(self._h, C.byref(cfg)))
+        self.rs_follow_params = cfg
+
+    def rs_follow(self, act_in_ptr, act_out_ptr, plan_ptr=None, out_ptr=None, stream=None):
+        """t2d_rs_follow: one launch; float32 [n_env, 2] (steering, accel) rows from act_in_ptr (None: zeros) to act_out_ptr (may
+        be the same memory), plan records at plan_ptr (None: the pool's own), records to out_ptr (None: the pool's own)."""
+        self._ck(self._lib.t2d_rs_follow(self._h, plan_ptr, act_in_ptr, act_out_ptr, out_ptr, stream))
+
+    def rs_follow_reset(self, mask_ptr=None, stream=None):
+        """t2d_rs_follow_reset: agent.reset() for the envs whose byte at mask_ptr (device memory) is non-zero; None: all"""
+        self._ck(self._lib.t2d_rs_follow_reset(self._h, mask_ptr, stream))
+
+    def rs_follow_views(self, ptr=None, owner=None):
+        """Zero-copy torch views of t2d_rs_follow_record [n_env] at `ptr` (None: the pool's own records): executing, segment,
+        events, steps int32 [n]; action float64 [n, 2] (normalised; NaN: the policy's row went through); distance_to_go,
+        total_error float64 [n]."""
+        import torch
+        if ptr is None:
+            p_, nb = C.c_void_p(), C.c_size_t()
+            self._ck(self._lib.t2d_rs_follow_buffers(self._h, C.byref(p_), C.byref(nb)))
+            ptr = p_.value
+        dev, n = f"cuda:{self.device_id}", self.n_env
+        keep = owner if owner is not None else self
+        i32 = torch.as_tensor(_DevArray(ptr, (n, L.RS_FOLLOW_RECORD_BYTES // 4), "<i4", keep), device=dev)
+        f64 = torch.as_tensor(_DevArray(ptr, (n, L.RS_FOLLOW_RECORD_BYTES // 8), "<f8", keep), device=dev)
+        return dict(executing=i32[:, 0], segment=i32[:, 1], events=i32[:, 2], steps=i32[:, 3], action=f64[:, 2:4],
+                    distance_to_go=f64[:, 4], total_error=f64[:, 5])
+
     def set_idm(self, ctrl_rows, ctrl_id):
         """Install IDM controllers: ctrl_rows [n_ctrl, 8] (layout.IDM_*), ctrl_id [n] uint8 (IDM_NONE =
         action supplied by the caller).  ctrl_rows=None uninstalls."""
