@@ -117,6 +117,12 @@ enum {
 #define T2D_GEOM_MAX_N 65536
 int t2d_debug_geom(int32_t device_id, int32_t fn, int64_t n, const double* a_host, const double* b_host, double* out_host);
 
+/* ---- memory bookkeeping (tactics2d_amd/csrc/t2d_devbuf.h; tests/test_gpu_lifetime.py) ------------------------------------------
+ * What the library (this copy of it: every pool, trajectory and probe call of the process) holds right now: out = {device bytes,
+ * device blocks, pinned host bytes, pinned host blocks}.  Every allocation of the library goes through one owning buffer type
+ * that keeps these four counts, so a pool that is destroyed must bring them back to what they were before it was created.   */
+int t2d_debug_memory(int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ int fail(t2d_pool* p, int code, const std::string& msg) {
 }
 const std::string& create_error() { return g_create_err; }
 }  // namespace host
+std::atomic<int64_t> g_mem_live[4];
 }  // namespace t2d
 using namespace t2d::host;
 namespace {
@@ -409,7 +410,7 @@ hipError_t launch_spin(long long ticks, hipStream_t s) {
     hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s, ticks);
     return hipGetLastError();
 }
-hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,
+hipError_t launch_restore(const PoolView& v, const float* const* snap, const uint32_t* snap_ids, int mode,
                           hipStream_t s) {
     SnapPtrs sp;
     for (int k = 0; k < 6; ++k) sp.f[k] = snap[k];
@@ -422,7 +423,6 @@ hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t*
 
 extern "C" {
 
-static void frame_release(t2d_pool* p);
 static void refresh_idm_view(t2d_pool* p);
 
 const char* t2d_last_error(const t2d_pool* pool) {
@@ -456,33 +456,28 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
             p->field_bytes[f] = 0;
             continue;
         }
-        hipError_t e = hipMalloc(&p->field_ptr[f], p->field_bytes[f]);
-        if (e == hipSuccess) e = hipMemset(p->field_ptr[f], 0, p->field_bytes[f]);
+        const hipError_t e = p->field_buf[f].alloc_zeroed(p->field_bytes[f]);
+        p->field_ptr[f] = p->field_buf[f];
         if (e != hipSuccess) {
             std::string msg = std::string("hipMalloc/hipMemset: ") + hipGetErrorString(e);
             t2d_destroy(p);
             return fail(nullptr, e == hipErrorOutOfMemory ? T2D_ERR_NOMEM : T2D_ERR_HIP, msg);
         }
     }
-    hipError_t e = hipMalloc((void**)&p->d_params, sizeof(double) * T2D_PARAM_COLS * T2D_MAX_TYPES);
+    hipError_t e = p->d_params.alloc(T2D_PARAM_COLS * T2D_MAX_TYPES);
     if (e != hipSuccess) {
         t2d_destroy(p);
         return fail(nullptr, T2D_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
     {
         const size_t E = (size_t)n_env;
-        hipError_t e2 = hipSuccess;
-        auto alloc = [&](void** ptr, size_t bytes) {
-            if (e2 == hipSuccess) e2 = hipMalloc(ptr, bytes);
-            if (e2 == hipSuccess) e2 = hipMemset(*ptr, 0, bytes);
-        };
-        alloc((void**)&p->d_last_pose, E * 8 * sizeof(double));
-        alloc((void**)&p->d_max_iou, E * sizeof(double));
-        alloc((void**)&p->d_min_dist, E * sizeof(double));
-        alloc((void**)&p->d_snap_min_dist, E * sizeof(double));
-        alloc((void**)&p->d_last_valid, E);
         p->chain_slots = (n_env + 7 + 8) & ~7;   // one counter per step workgroup (at most one per env) + padding; then the error word
-        alloc((void**)&p->d_chain, sizeof(unsigned long long) * ((size_t)p->chain_slots + 1));
+        hipError_t e2 = p->d_last_pose.alloc_zeroed(E * 8);
+        if (e2 == hipSuccess) e2 = p->d_max_iou.alloc_zeroed(E);
+        if (e2 == hipSuccess) e2 = p->d_min_dist.alloc_zeroed(E);
+        if (e2 == hipSuccess) e2 = p->d_snap_min_dist.alloc_zeroed(E);
+        if (e2 == hipSuccess) e2 = p->d_last_valid.alloc_zeroed(E);
+        if (e2 == hipSuccess) e2 = p->d_chain.alloc_zeroed((size_t)p->chain_slots + 1);
         if (e2 != hipSuccess) {
             t2d_destroy(p);
             return fail(nullptr, T2D_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e2));
@@ -534,8 +529,8 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
     {   // (T2D_TIMING_WORDS: room for the chained form's record per wave AND step, scripts/chain_timing.py)
         size_t words = (size_t)(n_env + 64) * 16 * 4;
         if (const char* e = getenv("T2D_TIMING_WORDS")) words = std::max(words, (size_t)strtoull(e, nullptr, 10));
-        (void)hipMalloc((void**)&v.dbg, words * sizeof(unsigned long long));
-        (void)hipMemset(v.dbg, 0, words * sizeof(unsigned long long));
+        (void)p->d_dbg.alloc_zeroed(words);
+        v.dbg = p->d_dbg;
     }
 #endif
     v.geo = nullptr;
@@ -556,39 +551,13 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
     return T2D_OK;
 }
 
-static void replay_release(t2d_pool* p);   // (drops a replay binding: defined with t2d_replay_bind)
-static void route_release(t2d_pool* p);    // (drops the installed routes: defined with t2d_set_routes)
-static void track_release(t2d_pool* p);    // (drops the installed tracks: defined with t2d_set_tracks)
-static void camera_release(t2d_pool* p);   // (drops the camera: defined with t2d_camera_config)
+static void unbind_trajectories(t2d_pool* p);   // (defined with struct t2d_traj)
 
 int t2d_destroy(t2d_pool* p) {
     if (!p) return T2D_OK;
     (void)hipSetDevice(p->device);
     (void)quiesce(p);  // nothing of this pool may still be running (incl. a scene refill on its own stream)
-    replay_release(p);
-    route_release(p);
-    track_release(p);
-    camera_release(p);
-    for (void* b : {(void*)p->d_route_of, (void*)p->d_route_thr, (void*)p->d_route_dist, (void*)p->d_route_off})
-        if (b) (void)hipFree(b);
-    for (int f = 0; f < T2D_F_COUNT; ++f)
-        if (p->field_ptr[f]) (void)hipFree(p->field_ptr[f]);
-    void* bufs[] = {p->d_params, p->d_geo, p->d_boundary, p->d_boundary_valid, p->d_target_xy, p->d_target_c,
-                    p->d_last_pose, p->d_max_iou, p->d_min_dist, p->d_snap_min_dist, p->d_last_valid,
-                    p->d_lidar_env_off, p->d_lidar_next, p->d_lidar_meta, p->d_lidar_xy, p->d_lidar_all, p->d_beam_sin, p->d_beam_cos,
-                    p->d_snap[0], p->d_snap[1], p->d_snap[2],
-                    p->d_snap[3], p->d_snap[4], p->d_snap[5], p->d_snap_ids, p->d_wgmap, p->d_idm_rows, p->d_idm_ctrl, p->d_snap_omega[0], p->d_snap_omega[1], p->d_time_penalty,
-                    p->d_scene_arrays, p->d_lidar_cnt, p->d_chain, p->d_ckpt, p->d_scene_view,
-                    p->d_grid_env, p->d_grid_cell_start, p->d_grid_items, p->d_map_flags, p->d_grid_bnd, p->d_grid_seg};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    frame_release(p);
-    if (p->d_target_heading) (void)hipFree(p->d_target_heading);
-    if (p->d_rs_beam_tab) (void)hipFree(p->d_rs_beam_tab);
-    if (p->d_rs_plan) (void)hipFree(p->d_rs_plan);
-    if (p->rs_follow.f64) (void)hipFree(p->rs_follow.f64);
-    if (p->rs_follow.i32) (void)hipFree(p->rs_follow.i32);
-    if (p->d_rs_follow_rec) (void)hipFree(p->d_rs_follow_rec);
+    unbind_trajectories(p);
     if (p->comm && rccl().ok) (void)rccl().CommDestroy((ncclComm_t)p->comm);
     if (p->gather_stream) (void)hipStreamDestroy(p->gather_stream);
     if (p->ev_frag_ready) (void)hipEventDestroy(p->ev_frag_ready);
@@ -601,7 +570,7 @@ int t2d_destroy(t2d_pool* p) {
         for (int i = 0; i < 2 * t2d_pool::kMaxProfSteps; ++i) (void)hipEventDestroy(p->prof_events[i]);
         delete[] p->prof_events;
     }
-    delete p;
+    delete p;   // (every buffer: the members free themselves)
     return T2D_OK;
 }
 
@@ -1348,8 +1317,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
             }
             if (!p->d_ckpt) {
                 const size_t words = 7 * (size_t)p->v.N + 2 * (size_t)p->v.n_env;
-                T2D_HIP(p, hipMalloc((void**)&p->d_ckpt, sizeof(uint32_t) * words));
-                T2D_HIP(p, hipMemset(p->d_ckpt, 0, sizeof(uint32_t) * words));
+                T2D_HIP(p, p->d_ckpt.alloc_zeroed(words));
             }
             v.ckpt = p->d_ckpt;
             v.ckpt_tag = (uint32_t)(p->step_count - n);   // (low half of the step count this fragment starts from)
@@ -1455,15 +1423,15 @@ int t2d_snapshot(t2d_pool* p) {
     const size_t nb = 4 * (size_t)p->v.N;
     float* src[6] = {p->v.x, p->v.y, p->v.heading, p->v.speed, p->v.vx, p->v.vy};
     for (int k = 0; k < 6; ++k) {
-        if (!p->d_snap[k]) T2D_HIP(p, hipMalloc((void**)&p->d_snap[k], nb));
+        if (!p->d_snap[k]) T2D_HIP(p, p->d_snap[k].alloc((size_t)p->v.N));
         T2D_HIP(p, hipMemcpy(p->d_snap[k], src[k], nb, hipMemcpyDeviceToDevice));
     }
     for (int k = 0; k < 2; ++k) {
-        if (!p->d_snap_omega[k]) T2D_HIP(p, hipMalloc((void**)&p->d_snap_omega[k], nb));
+        if (!p->d_snap_omega[k]) T2D_HIP(p, p->d_snap_omega[k].alloc((size_t)p->v.N));
         T2D_HIP(p, hipMemcpy(p->d_snap_omega[k], k ? p->v.omega_r : p->v.omega_f, nb, hipMemcpyDeviceToDevice));
         p->v.snap_omega[k] = p->has_drift ? p->d_snap_omega[k] : nullptr;
     }
-    if (!p->d_snap_ids) T2D_HIP(p, hipMalloc((void**)&p->d_snap_ids, nb));
+    if (!p->d_snap_ids) T2D_HIP(p, p->d_snap_ids.alloc((size_t)p->v.N));
     T2D_HIP(p, hipMemcpy(p->d_snap_ids, p->v.ids, nb, hipMemcpyDeviceToDevice));
     T2D_HIP(p, hipMemcpy(p->d_snap_min_dist, p->d_min_dist, sizeof(double) * p->v.n_env, hipMemcpyDeviceToDevice));
     p->have_snapshot = true;
@@ -1489,7 +1457,7 @@ int t2d_restore(t2d_pool* p, int32_t mode, void* hip_stream) {
     if (mode != 0 && mode != 1) return fail(p, T2D_ERR_INVALID, "mode must be 0 (all) or 1 (done envs)");
     touch(p, (hipStream_t)hip_stream);
     if (mode == 0) p->chain_failed = false;   // (see t2d_reset)
-    T2D_HIP(p, t2d::launch_restore(p->v, p->d_snap, p->d_snap_ids, mode, (hipStream_t)hip_stream));
+    T2D_HIP(p, t2d::launch_restore(p->v, p->v.snap, p->v.snap_ids, mode, (hipStream_t)hip_stream));
     p->types_used |= p->snap_types;
     return T2D_OK;
 }
@@ -1569,8 +1537,8 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     p->have_target = true;
     const size_t nbytes = 4 * (size_t)p->v.N;
     for (int k = 0; k < 6; ++k)
-        if (!p->d_snap[k]) T2D_HIP(p, hipMalloc((void**)&p->d_snap[k], nbytes));
-    if (!p->d_snap_ids) T2D_HIP(p, hipMalloc((void**)&p->d_snap_ids, nbytes));
+        if (!p->d_snap[k]) T2D_HIP(p, p->d_snap[k].alloc((size_t)p->v.N));
+    if (!p->d_snap_ids) T2D_HIP(p, p->d_snap_ids.alloc((size_t)p->v.N));
     // the per-scene arrays (layout of t2d_generate_parking's outputs): live [E] + the staging ring [E * ring] used when
     // scenes are regenerated (regenerate == 1; == 2 generates on the step's stream instead), episode counters
     const int ring = regenerate == 1 ? kSceneRing : 0;
@@ -1589,13 +1557,8 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
     off[19] = total; total += 256;                                                         // refill_count
     off[20] = total; total += ((size_t)E * ring * sizeof(uint2) + 255) & ~(size_t)255;     // refill_list
     if (p->scene_stream) T2D_HIP(p, hipStreamSynchronize(p->scene_stream));
-    if (p->d_scene_arrays) {
-        T2D_HIP(p, hipFree(p->d_scene_arrays));
-        p->d_scene_arrays = nullptr;
-    }
-    T2D_HIP(p, hipMalloc(&p->d_scene_arrays, total));
-    T2D_HIP(p, hipMemset(p->d_scene_arrays, 0, total));
-    char* base = (char*)p->d_scene_arrays;
+    T2D_HIP(p, p->d_scene_arrays.alloc_zeroed(total));   // (frees the previous arrays first)
+    char* base = (char*)p->d_scene_arrays.get();
     t2d::SceneView& sv = p->scene;
     sv = t2d::SceneView{};
     sv.seed = seed; sv.first_env = first_env; sv.env_stride = env_stride;
@@ -1631,7 +1594,7 @@ int t2d_parking_scenes(t2d_pool* p, uint64_t seed, int64_t first_env, int64_t en
                   (1u << t2d::kIdsActiveShift);
     p->scene_mode = true;
     p->scene_regen = regenerate != 0;
-    if (!p->d_scene_view) T2D_HIP(p, hipMalloc((void**)&p->d_scene_view, sizeof(t2d::SceneView)));
+    if (!p->d_scene_view) T2D_HIP(p, p->d_scene_view.alloc(1));
     T2D_HIP(p, hipMemcpy(p->d_scene_view, &sv, sizeof(sv), hipMemcpyHostToDevice));   // (what the ego step kernel's epilogue reads)
     if ((rc = rebuild_lidar_geo(p))) return rc;
     {  // t2d_reset's remaining columns: wheel speeds start at zero
@@ -1673,6 +1636,14 @@ int t2d_get_parking_scenes(t2d_pool* p, float* quads, int32_t* quad_id, int32_t*
     if (episode) T2D_HIP(p, hipMemcpy(episode, sv.episode, E * sizeof(int32_t), hipMemcpyDeviceToHost));
     return T2D_OK;
 }
+
+#ifdef T2D_DEBUG_HOOKS   // include/t2d_debug.h: libt2d_hip_debug.so only
+int t2d_debug_memory(int64_t out[4]) {
+    if (!out) return T2D_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = t2d::g_mem_live[k].load(std::memory_order_relaxed);
+    return T2D_OK;
+}
+#endif
 
 #ifdef T2D_TIMING
 // profiling builds only (not part of the ABI): read and clear the phase cycle accumulators
@@ -1836,7 +1807,7 @@ int t2d_debug_set_step_placement(t2d_pool* p, const uint32_t* map_host, int32_t 
         if (g >= (uint32_t)n_blocks || r > 3u || seen[g]) return fail(p, T2D_ERR_INVALID, "placement map is not a permutation with rotations 0..3");
         seen[g] = 1;
     }
-    if (!p->d_wgmap) T2D_HIP(p, hipMalloc((void**)&p->d_wgmap, sizeof(uint32_t) * 65536));
+    if (!p->d_wgmap) T2D_HIP(p, p->d_wgmap.alloc(65536));
     T2D_HIP(p, hipMemcpy(p->d_wgmap, map_host, sizeof(uint32_t) * (size_t)n_blocks, hipMemcpyHostToDevice));
     p->v.wgmap = p->d_wgmap;
     return T2D_OK;
@@ -1940,16 +1911,10 @@ static void frame_release(t2d_pool* p) {
         p->act_in_frame = false;
         refresh_idm_view(p);
     }
-    if (p->d_frame) (void)hipFree(p->d_frame);
-    if (p->d_actions) (void)hipFree(p->d_actions);
-    for (char*& h : p->h_frame) {
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-    }
-    if (p->h_actions) (void)hipHostFree(p->h_actions);
-    p->d_frame = nullptr;
-    p->d_actions = nullptr;
-    p->h_actions = nullptr;
+    p->d_frame = {};
+    p->d_actions = {};
+    for (auto& h : p->h_frame) h = {};
+    p->h_actions = {};
     p->frame_sections = 0;
     p->n_host_frames = 0;
     p->frame_layout = t2d_frame_layout{};
@@ -2000,18 +1965,16 @@ int t2d_frame_config(t2d_pool* p, uint32_t sections, int32_t n_host_frames, t2d_
     frame_release(p);
     const unsigned host_flags = hipHostMallocMapped | hipHostMallocCoherent;
     for (int k = 0; k < n_host_frames; ++k) {
-        T2D_HIP(p, hipHostMalloc((void**)&p->h_frame[k], total, host_flags));
+        T2D_HIP(p, p->h_frame[k].alloc(total, host_flags));
         memset(p->h_frame[k], 0, total);
     }
     p->n_host_frames = n_host_frames;
     const size_t act_bytes = (size_t)p->v.N * 2 * sizeof(float);
-    T2D_HIP(p, hipHostMalloc((void**)&p->h_actions, act_bytes, host_flags));
+    T2D_HIP(p, p->h_actions.alloc((size_t)p->v.N * 2, host_flags));
     memset(p->h_actions, 0, act_bytes);
     if (!(sections & T2D_FRAME_ZEROCOPY)) {
-        T2D_HIP(p, hipMalloc((void**)&p->d_frame, total));
-        T2D_HIP(p, hipMemset(p->d_frame, 0, total));
-        T2D_HIP(p, hipMalloc((void**)&p->d_actions, act_bytes));
-        T2D_HIP(p, hipMemset(p->d_actions, 0, act_bytes));
+        T2D_HIP(p, p->d_frame.alloc_zeroed(total));
+        T2D_HIP(p, p->d_actions.alloc_zeroed((size_t)p->v.N * 2));
     }
     p->frame_sections = sections | 0x80000000u;   // (configured, whatever the section bits)
     p->frame_layout = L;
@@ -2184,21 +2147,16 @@ int t2d_lidar_config(t2d_pool* p, int32_t n_beams, float max_range, int32_t incl
     // zero-copy view a caller took with t2d_get_field stays valid until the size really changes
     const size_t lidar_bytes = (size_t)p->v.n_env * n_beams * sizeof(float);
     if (!p->field_ptr[T2D_F_LIDAR] || p->field_bytes[T2D_F_LIDAR] != lidar_bytes) {
-        if (p->field_ptr[T2D_F_LIDAR]) {
-            T2D_HIP(p, hipFree(p->field_ptr[T2D_F_LIDAR]));
-            p->field_ptr[T2D_F_LIDAR] = nullptr;
-        }
+        p->field_ptr[T2D_F_LIDAR] = nullptr;   // (a failed allocation leaves the field empty: no pointer, no size)
+        p->field_bytes[T2D_F_LIDAR] = 0;
+        T2D_HIP(p, p->field_buf[T2D_F_LIDAR].alloc(lidar_bytes));
+        p->field_ptr[T2D_F_LIDAR] = p->field_buf[T2D_F_LIDAR];
         p->field_bytes[T2D_F_LIDAR] = lidar_bytes;
-        T2D_HIP(p, hipMalloc(&p->field_ptr[T2D_F_LIDAR], lidar_bytes));
     }
     T2D_HIP(p, hipMemset(p->field_ptr[T2D_F_LIDAR], 0, lidar_bytes));
     // the all-participants buffer follows the configuration: a new beam count drops it, the next NULL-destination
     // t2d_lidar_scan_all allocates it again (a view taken with t2d_lidar_all_buffer stays valid while the size does)
-    if (p->d_lidar_all && p->lidar_all_bytes != lidar_bytes * (size_t)p->v.A) {
-        T2D_HIP(p, hipFree(p->d_lidar_all));
-        p->d_lidar_all = nullptr;
-        p->lidar_all_bytes = 0;
-    }
+    if (p->d_lidar_all && p->d_lidar_all.bytes() != lidar_bytes * (size_t)p->v.A) T2D_HIP(p, p->d_lidar_all.reset());
     p->lidar.beam_pre = p->d_beam_sin;
     p->lidar.max_range = (double)max_range;
     p->lidar.n_beams = n_beams;
@@ -2232,10 +2190,8 @@ int t2d_lidar_scan_all(t2d_pool* p, float* out_dev, void* hip_stream) {
     int rc;
     if ((rc = lidar_fits(p))) return rc;
     if (!out_dev && !p->d_lidar_all) {   // first use of the pool's own buffer (or the first after a new beam count)
-        const size_t bytes = (size_t)p->v.n_env * p->v.A * p->lidar.n_beams * sizeof(float);
         T2D_HIP(p, hipSetDevice(p->device));
-        T2D_HIP(p, hipMalloc(&p->d_lidar_all, bytes));
-        p->lidar_all_bytes = bytes;
+        T2D_HIP(p, p->d_lidar_all.alloc((size_t)p->v.n_env * p->v.A * p->lidar.n_beams));
     }
     touch(p, s);
     if ((rc = record_event(p, 8, s, true))) return rc;
@@ -2249,7 +2205,7 @@ int t2d_lidar_all_buffer(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
     if (!p->d_lidar_all)
         return fail(p, T2D_ERR_STATE, "a t2d_lidar_scan_all with a NULL destination must precede t2d_lidar_all_buffer");
     *dev_ptr = p->d_lidar_all;
-    *nbytes = p->lidar_all_bytes;
+    *nbytes = p->d_lidar_all.bytes();
     return T2D_OK;
 }
 
@@ -2289,10 +2245,7 @@ int t2d_rs_config(t2d_pool* p, const t2d_rs_params* cfg, const float* vehicle_ba
     }
     int rc;
     if ((rc = dev_replace(p, &p->d_rs_beam_tab, tab.data(), tab.size()))) return rc;
-    if (!p->d_rs_plan) {
-        T2D_HIP(p, hipMalloc((void**)&p->d_rs_plan, (size_t)p->v.n_env * sizeof(t2d_rs_plan_record)));
-        T2D_HIP(p, hipMemset(p->d_rs_plan, 0, (size_t)p->v.n_env * sizeof(t2d_rs_plan_record)));
-    }
+    if (!p->d_rs_plan) T2D_HIP(p, p->d_rs_plan.alloc_zeroed((size_t)p->v.n_env));
     p->rs.cfg = *cfg;
     p->rs.lidar_range = p->lidar.max_range;
     p->rs.beam_tab = p->d_rs_beam_tab;
@@ -2363,9 +2316,11 @@ int t2d_rs_follow_config(t2d_pool* p, const t2d_rs_follow_params* cfg) {
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
     const size_t E = (size_t)p->v.n_env;
-    if (!p->rs_follow.f64) T2D_HIP(p, hipMalloc((void**)&p->rs_follow.f64, (size_t)t2d::kRfF64Rows * E * sizeof(double)));
-    if (!p->rs_follow.i32) T2D_HIP(p, hipMalloc((void**)&p->rs_follow.i32, (size_t)t2d::kRfI32Rows * E * sizeof(int32_t)));
-    if (!p->d_rs_follow_rec) T2D_HIP(p, hipMalloc((void**)&p->d_rs_follow_rec, E * sizeof(t2d_rs_follow_record)));
+    if (!p->d_rs_follow_f64) T2D_HIP(p, p->d_rs_follow_f64.alloc((size_t)t2d::kRfF64Rows * E));
+    if (!p->d_rs_follow_i32) T2D_HIP(p, p->d_rs_follow_i32.alloc((size_t)t2d::kRfI32Rows * E));
+    if (!p->d_rs_follow_rec) T2D_HIP(p, p->d_rs_follow_rec.alloc(E));
+    p->rs_follow.f64 = p->d_rs_follow_f64;
+    p->rs_follow.i32 = p->d_rs_follow_i32;
     int rc;
     if ((rc = rs_follow_clear(p))) return rc;
     p->rs_follow.cfg = *cfg;
@@ -2475,12 +2430,12 @@ int t2d_verify_state(t2d_pool* p, const float* x_dev, const float* y_dev, const 
 struct t2d_traj {
     t2d_pool* pool;
     int device, N, capacity;
-    float* buf = nullptr;   // [T2D_TRAJ_COLS][capacity][N]
+    t2d::DevBuf<float> buf;   // [T2D_TRAJ_COLS][capacity][N]
     // the frame -> slot map and intervals of t2d_verify_states, staged through pinned host memory; `meta_done` follows the last
     // launch that read them, so the next call does not overwrite them under a running kernel
     int32_t meta_cap = 0;
-    void* meta_host = nullptr;
-    void* meta_dev = nullptr;
+    t2d::PinBuf<> meta_host;
+    t2d::DevBuf<> meta_dev;
     hipEvent_t meta_done = nullptr;
     bool meta_pending = false;
     int n_bound = 0;   // pools that replay this trajectory (t2d_replay_bind)
@@ -2490,6 +2445,14 @@ namespace {
 size_t traj_meta_bytes(int n) { return (size_t)n * sizeof(double) + (size_t)n * sizeof(int32_t); }
 bool traj_slot_ok(const t2d_traj* t, int32_t slot) { return slot >= 0 && slot < t->capacity; }
 }  // namespace
+
+// a pool that goes lets go of the trajectories it replays / takes its routes from
+static void unbind_trajectories(t2d_pool* p) {
+    for (t2d_traj** t : {&p->replay_src, &p->route_src}) {
+        if (*t) (*t)->n_bound--;
+        *t = nullptr;
+    }
+}
 
 int t2d_traj_create(t2d_pool* p, int32_t capacity, t2d_traj** out) {
     if (!p || !out) return p ? fail(p, T2D_ERR_INVALID, "t2d_traj_create: null output") : T2D_ERR_INVALID;
@@ -2502,12 +2465,9 @@ int t2d_traj_create(t2d_pool* p, int32_t capacity, t2d_traj** out) {
     t->N = p->v.N;
     t->capacity = capacity;
     const size_t bytes = (size_t)T2D_TRAJ_COLS * capacity * t->N * sizeof(float);
-    if (hipMalloc((void**)&t->buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    if (t->buf.alloc(bytes / sizeof(float)) != hipSuccess)
         return fail(p, T2D_ERR_NOMEM, "t2d_traj_create: " + std::to_string(bytes) + " bytes of device memory");
-    }
     if (hipEventCreateWithFlags(&t->meta_done, hipEventDisableTiming) != hipSuccess) {
-        (void)hipFree(t->buf);
         return fail(p, T2D_ERR_HIP, "t2d_traj_create: hipEventCreateWithFlags failed");
     }
     *out = t.release();
@@ -2523,9 +2483,6 @@ int t2d_traj_destroy(t2d_traj* t) {
     (void)hipSetDevice(t->device);
     (void)quiesce(t->pool);   // records, copies and verify launches on the pool's streams
     if (t->meta_pending) (void)hipEventSynchronize(t->meta_done);
-    if (t->buf) (void)hipFree(t->buf);
-    if (t->meta_dev) (void)hipFree(t->meta_dev);
-    if (t->meta_host) (void)hipHostFree(t->meta_host);
     if (t->meta_done) (void)hipEventDestroy(t->meta_done);
     delete t;
     return T2D_OK;
@@ -2622,22 +2579,21 @@ int t2d_verify_states(t2d_traj* t, int32_t n_frames, const int32_t* slot_host, c
     if (n_frames > t->meta_cap) {
         int cap = std::max(64, t->meta_cap);
         while (cap < n_frames) cap *= 2;
-        if (t->meta_dev) T2D_HIP(p, hipFree(t->meta_dev));
-        if (t->meta_host) T2D_HIP(p, hipHostFree(t->meta_host));
-        t->meta_dev = t->meta_host = nullptr;
         t->meta_cap = 0;
-        T2D_HIP(p, hipMalloc(&t->meta_dev, traj_meta_bytes(cap)));
-        T2D_HIP(p, hipHostMalloc(&t->meta_host, traj_meta_bytes(cap), hipHostMallocDefault));
+        T2D_HIP(p, t->meta_dev.reset());
+        T2D_HIP(p, t->meta_host.reset());
+        T2D_HIP(p, t->meta_dev.alloc(traj_meta_bytes(cap)));
+        T2D_HIP(p, t->meta_host.alloc(traj_meta_bytes(cap), hipHostMallocDefault));
         t->meta_cap = cap;
     }
     // [intervals: n doubles][slots: n int32] -- one copy
-    memcpy(t->meta_host, interval_ms_host, (size_t)n_frames * sizeof(double));
-    memcpy((char*)t->meta_host + (size_t)n_frames * sizeof(double), slot_host, (size_t)n_frames * sizeof(int32_t));
+    memcpy(t->meta_host.get(), interval_ms_host, (size_t)n_frames * sizeof(double));
+    memcpy((char*)t->meta_host.get() + (size_t)n_frames * sizeof(double), slot_host, (size_t)n_frames * sizeof(int32_t));
     const hipStream_t s = (hipStream_t)hip_stream;
     touch(p, s);
     T2D_HIP(p, hipMemcpyAsync(t->meta_dev, t->meta_host, traj_meta_bytes(n_frames), hipMemcpyHostToDevice, s));
-    const double* iv_dev = (const double*)t->meta_dev;
-    const int32_t* slot_dev = (const int32_t*)((const char*)t->meta_dev + (size_t)n_frames * sizeof(double));
+    const double* iv_dev = (const double*)t->meta_dev.get();
+    const int32_t* slot_dev = (const int32_t*)((const char*)t->meta_dev.get() + (size_t)n_frames * sizeof(double));
     T2D_HIP(p, t2d::launch_verify_states(p->v, t->buf, t->capacity, slot_dev, iv_dev, n_frames, stable, valid_dev, s));
     T2D_HIP(p, hipEventRecord(t->meta_done, s));
     t->meta_pending = true;
@@ -2648,8 +2604,7 @@ int t2d_verify_states(t2d_traj* t, int32_t n_frames, const int32_t* slot_host, c
 static void replay_release(t2d_pool* p) {
     if (p->replay_src) p->replay_src->n_bound--;
     p->replay_src = nullptr;
-    if (p->d_replay_meta) (void)hipFree(p->d_replay_meta);
-    p->d_replay_meta = nullptr;
+    p->d_replay_meta = {};
     p->replay = t2d::ReplaySpec{};
 }
 
@@ -2709,22 +2664,18 @@ int t2d_replay_bind(t2d_pool* p, const t2d_traj* src, int32_t n_slots, int32_t t
                                                 std::to_string(m_first[j]) + ", " + std::to_string(m_last[j]) + "], leaves [0, " +
                                                 std::to_string(n_slots) + ")");
     }
-    int32_t* d_meta = nullptr;
-    if (hipMalloc((void**)&d_meta, meta.size() * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
+    t2d::DevBuf<int32_t> d_meta;
+    if (d_meta.alloc(meta.size()) != hipSuccess)
         return fail(p, T2D_ERR_NOMEM, "t2d_replay_bind: " + std::to_string(meta.size() * sizeof(int32_t)) + " bytes of device memory");
-    }
     hipError_t he = quiesce(p);   // (a step that still reads the previous binding)
     if (he == hipSuccess) he = hipMemcpy(d_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipFree(d_meta);
-        return fail(p, T2D_ERR_HIP, std::string("t2d_replay_bind: ") + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, std::string("t2d_replay_bind: ") + hipGetErrorString(he));
     replay_release(p);   // nothing can fail from here on: the new binding replaces the old one whole
-    p->d_replay_meta = d_meta;
+    p->d_replay_meta = std::move(d_meta);
     p->replay_src = const_cast<t2d_traj*>(src);
     p->replay_src->n_bound++;
-    p->replay = t2d::ReplaySpec{src->buf, d_meta, d_meta + e4, d_meta + 2 * e4, d_meta + 2 * e4 + n4, 0u,
+    const int32_t* m = p->d_replay_meta;
+    p->replay = t2d::ReplaySpec{src->buf, m, m + e4, m + 2 * e4, m + 2 * e4 + n4, 0u,
                                 src->capacity, N_src, n_slots, t0_ms, period_ms};
     return T2D_OK;
 }
@@ -2743,8 +2694,7 @@ int t2d_replay_apply(t2d_pool* p, void* hip_stream) {
 static void route_release(t2d_pool* p) {
     if (p->route_src) p->route_src->n_bound--;
     p->route_src = nullptr;
-    if (p->d_route_geo) (void)hipFree(p->d_route_geo);
-    p->d_route_geo = nullptr;
+    p->d_route_geo = {};
     p->route = t2d::RouteView{};
     p->route_limit.clear();
 }
@@ -2770,28 +2720,21 @@ int route_assignment(t2d_pool* p, const char* who, const int32_t* route_of, cons
 // the pool's assignment arrays (allocated once), filled after the pool's work
 int route_assignment_upload(t2d_pool* p, const std::vector<int32_t>* ro, const std::vector<float>* th) {
     const size_t N = (size_t)p->v.N;
-    if (!p->d_route_of) T2D_HIP(p, hipMalloc((void**)&p->d_route_of, N * sizeof(int32_t)));
-    if (!p->d_route_thr) T2D_HIP(p, hipMalloc((void**)&p->d_route_thr, N * sizeof(float)));
+    if (!p->d_route_of) T2D_HIP(p, p->d_route_of.alloc(N));
+    if (!p->d_route_thr) T2D_HIP(p, p->d_route_thr.alloc(N));
     if (ro) T2D_HIP(p, hipMemcpy(p->d_route_of, ro->data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
     if (th) T2D_HIP(p, hipMemcpy(p->d_route_thr, th->data(), N * sizeof(float), hipMemcpyHostToDevice));
     return T2D_OK;
 }
 
 // a new geometry blob of 4-byte words on the device, filled after the pool's work; the caller commits it
-int route_blob(t2d_pool* p, const char* who, const std::vector<uint32_t>& words, void** out) {
-    void* d = nullptr;
+int route_blob(t2d_pool* p, const char* who, const std::vector<uint32_t>& words, t2d::DevBuf<>& d) {
     const size_t bytes = std::max<size_t>(words.size(), 1) * sizeof(uint32_t);
-    if (hipMalloc(&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    if (d.alloc(bytes) != hipSuccess)
         return fail(p, T2D_ERR_NOMEM, std::string(who) + ": " + std::to_string(bytes) + " bytes of device memory");
-    }
     hipError_t he = quiesce(p);   // (an evaluation that still reads the previous routes)
     if (he == hipSuccess && !words.empty()) he = hipMemcpy(d, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return fail(p, T2D_ERR_HIP, std::string(who) + ": " + hipGetErrorString(he));
-    }
-    *out = d;
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, std::string(who) + ": " + hipGetErrorString(he));
     return T2D_OK;
 }
 }  // namespace
@@ -2849,14 +2792,12 @@ int t2d_set_routes(t2d_pool* p, int32_t n_sets, const int32_t* set_route_offsets
     for (int e = 0; e < E; ++e) wi[e] = set_of_env ? set_of_env[e] : 0;
     memcpy(wi + E, set_route_offsets, (size_t)(n_sets + 1) * sizeof(int32_t));
     memcpy(wi + E + n_sets + 1, route_vert_offsets, (size_t)(n_route + 1) * sizeof(int32_t));
-    void* d = nullptr;
-    if ((rc = route_blob(p, "t2d_set_routes", w, &d))) return rc;
-    if ((rc = route_assignment_upload(p, &ro, &th))) {
-        (void)hipFree(d);
-        return rc;
-    }
+    t2d::DevBuf<> blob;
+    if ((rc = route_blob(p, "t2d_set_routes", w, blob))) return rc;
+    if ((rc = route_assignment_upload(p, &ro, &th))) return rc;
     route_release(p);   // nothing can fail from here on: the new routes replace the old ones whole
-    p->d_route_geo = d;
+    p->d_route_geo = std::move(blob);
+    const void* d = p->d_route_geo;
     p->route_limit = std::move(limit);
     t2d::RouteView& rv = p->route;
     rv.kind = 1;
@@ -2922,14 +2863,12 @@ int t2d_set_routes_from_traj(t2d_pool* p, const t2d_traj* src, int32_t n_slots, 
     std::vector<float> th;
     int rc;
     if ((rc = route_assignment(p, "t2d_set_routes_from_traj", route_of, threshold, limit, true, ro, th))) return rc;
-    void* d = nullptr;
-    if ((rc = route_blob(p, "t2d_set_routes_from_traj", w, &d))) return rc;
-    if ((rc = route_assignment_upload(p, &ro, &th))) {
-        (void)hipFree(d);
-        return rc;
-    }
+    t2d::DevBuf<> blob;
+    if ((rc = route_blob(p, "t2d_set_routes_from_traj", w, blob))) return rc;
+    if ((rc = route_assignment_upload(p, &ro, &th))) return rc;
     route_release(p);   // nothing can fail from here on
-    p->d_route_geo = d;
+    p->d_route_geo = std::move(blob);
+    const void* d = p->d_route_geo;
     p->route_limit = std::move(limit);
     p->route_src = const_cast<t2d_traj*>(src);
     p->route_src->n_bound++;
@@ -2962,13 +2901,12 @@ int t2d_off_route(t2d_pool* p, float* dist_out_dev, uint8_t* off_out_dev, void* 
     hipStream_t s = (hipStream_t)hip_stream;
     T2D_HIP(p, hipSetDevice(p->device));
     if ((!dist_out_dev || !off_out_dev) && !p->d_route_dist) {   // first use of the pool's own buffers
-        T2D_HIP(p, hipMalloc((void**)&p->d_route_dist, (size_t)p->v.N * sizeof(float)));
-        if (hipMalloc((void**)&p->d_route_off, (size_t)p->v.N) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(p->d_route_dist);
-            p->d_route_dist = nullptr;
-            return fail(p, T2D_ERR_NOMEM, "t2d_off_route: the pool's own result buffers");
-        }
+        t2d::DevBuf<float> dist;
+        t2d::DevBuf<uint8_t> off;
+        T2D_HIP(p, dist.alloc((size_t)p->v.N));
+        if (off.alloc((size_t)p->v.N) != hipSuccess) return fail(p, T2D_ERR_NOMEM, "t2d_off_route: the pool's own result buffers");
+        p->d_route_dist = std::move(dist);
+        p->d_route_off = std::move(off);
     }
     touch(p, s);
     if (p->route_src && p->route_src->pool != p) touch(p->route_src->pool, s);   // (the source pool's set-up calls wait for readers of its buffer)
@@ -2992,8 +2930,7 @@ int t2d_off_route_buffers(t2d_pool* p, void** dist_dev, void** off_dev, size_t* 
 
 // ---- racing tile progress (kernel: t2d_track.hip) ----------------------------------------------------------------------------
 static void track_release(t2d_pool* p) {
-    if (p->d_track) (void)hipFree(p->d_track);
-    p->d_track = nullptr;
+    p->d_track = {};
     p->track = t2d::TrackView{};
     p->track_n_tile.clear();
     p->trackgen = t2d::TrackGenView{};
@@ -3018,6 +2955,20 @@ struct TrackLayout {
         bytes = o;
     }
 };
+// the view's pointers into the installed allocation `d` (which the pool's d_track owns)
+void track_view_borrow(t2d::TrackView& tv, char* d, const TrackLayout& lay) {
+    tv.tiles = (const float*)(d + lay.tiles);
+    tv.set_start = (const int32_t*)(d + lay.set_start);
+    tv.n_tile = (const int32_t*)(d + lay.n_tile);
+    tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
+    tv.visiting = (int32_t*)(d + lay.visiting);
+    tv.num_visited = (int32_t*)(d + lay.num_visited);
+    tv.mask = (uint32_t*)(d + lay.mask);
+    tv.status = (uint8_t*)(d + lay.status);
+    tv.reward = (float*)(d + lay.reward);
+    tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
+    tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+}
 
 // the progress state of the selected envs <- (tile_visiting, mask) (null: tile 0, only tile 0 visited), in `buf` (a host image
 // of the allocation); their status goes back to NORMAL, their reward to 0, and the start copy follows
@@ -3123,33 +3074,19 @@ int t2d_set_tracks(t2d_pool* p, int32_t n_sets, const int32_t* set_tile_offsets,
     for (int s = 0; s < n_sets; ++s) ((int32_t*)(img.data() + lay.n_tile))[s] = set_tile_offsets[s + 1] - set_tile_offsets[s];
     for (int e = 0; e < E; ++e) ((int32_t*)(img.data() + lay.set_of_env))[e] = set_of_env ? set_of_env[e] : 0;
     track_assign_host(img.data(), lay, E, nullptr, nullptr, nullptr);
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, lay.bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    t2d::DevBuf<> blob;
+    if (blob.alloc(lay.bytes) != hipSuccess)
         return fail(p, T2D_ERR_NOMEM, "t2d_set_tracks: " + std::to_string(lay.bytes) + " bytes of device memory");
-    }
+    char* const d = (char*)blob.get();
     hipError_t he = quiesce(p);   // (a progress launch that still reads the previous tracks)
     if (he == hipSuccess) he = hipMemcpy(d, img.data(), lay.bytes, hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return fail(p, T2D_ERR_HIP, std::string("t2d_set_tracks: ") + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, std::string("t2d_set_tracks: ") + hipGetErrorString(he));
     track_release(p);   // nothing can fail from here on
-    p->d_track = d;
+    p->d_track = std::move(blob);
     p->track_n_tile = std::move(n_of_env);
     t2d::TrackView& tv = p->track;
     tv.installed = 1; tv.ego_index = ego_index; tv.rule = rule; tv.max_advance = max_advance; tv.check_off_road = check_off_road != 0;
-    tv.tiles = (const float*)(d + lay.tiles);
-    tv.set_start = (const int32_t*)(d + lay.set_start);
-    tv.n_tile = (const int32_t*)(d + lay.n_tile);
-    tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
-    tv.visiting = (int32_t*)(d + lay.visiting);
-    tv.num_visited = (int32_t*)(d + lay.num_visited);
-    tv.mask = (uint32_t*)(d + lay.mask);
-    tv.status = (uint8_t*)(d + lay.status);
-    tv.reward = (float*)(d + lay.reward);
-    tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
-    tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+    track_view_borrow(tv, d, lay);
     return T2D_OK;
 }
 
@@ -3192,11 +3129,9 @@ int t2d_set_tracks_generated(t2d_pool* p, int32_t n_sets, uint64_t seed, int64_t
     for (int s = 0; s <= n_sets; ++s) ((int32_t*)(img.data() + tail.set_start))[s] = s * T2D_MAX_TRACK_TILES;
     memcpy(img.data() + tail.set_of_env, soe.data(), (size_t)E * sizeof(int32_t));
     track_assign_host(img.data(), tail, E, nullptr, nullptr, nullptr);
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, lay.bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(p, T2D_ERR_NOMEM, who + std::to_string(lay.bytes) + " bytes of device memory");
-    }
+    t2d::DevBuf<> blob;
+    if (blob.alloc(lay.bytes) != hipSuccess) return fail(p, T2D_ERR_NOMEM, who + std::to_string(lay.bytes) + " bytes of device memory");
+    char* const d = (char*)blob.get();
     t2d::TrackGenView g{};
     g.seed = seed; g.first_track = first_track; g.track_stride = track_stride; g.car_length = car_length;
     g.tiles = (float*)(d + lay.tiles); g.n_tile = (int32_t*)(d + lay.n_tile); g.n_checkpoint = (int32_t*)(d + lay.g_ncp);
@@ -3214,25 +3149,17 @@ int t2d_set_tracks_generated(t2d_pool* p, int32_t n_sets, uint64_t seed, int64_t
     if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
     if (he == hipSuccess) he = hipMemcpy(flags.data(), g.flags, (size_t)n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(n_of_set.data(), g.n_tile, (size_t)n_sets * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
     for (int s = 0; s < n_sets; ++s)
-        if (flags[s] || n_of_set[s] < 3) {
-            (void)hipFree(d);
+        if (flags[s] || n_of_set[s] < 3)
             return fail(p, T2D_ERR_GEOMETRY, who + "track " + std::to_string(s) + " (stream " + std::to_string((long long)(first_track + s)) + ") came back flagged (" +
                                                  (flags[s] & T2D_TRACKGEN_CAPPED ? "no attempt succeeded" : "more tiles than T2D_MAX_TRACK_TILES") + "): nothing was installed");
-        }
     // the envs' boundary, the ego's state and snapshot, from the tracks just made (nothing of them crosses to the host)
     he = t2d::launch_track_install(p->v, g, (const int32_t*)(d + lay.set_of_env), nullptr);
     if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
-    if (he != hipSuccess) {
-        (void)hipFree(d);
-        return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, who + hipGetErrorString(he));
     track_release(p);   // nothing can fail from here on
-    p->d_track = d;
+    p->d_track = std::move(blob);
     p->track_n_tile.resize(E);
     for (int e = 0; e < E; ++e) p->track_n_tile[e] = n_of_set[soe[e]];
     p->trackgen = g;
@@ -3240,17 +3167,7 @@ int t2d_set_tracks_generated(t2d_pool* p, int32_t n_sets, uint64_t seed, int64_t
     p->trackgen_regen = regenerate != 0;
     t2d::TrackView& tv = p->track;
     tv.installed = 1; tv.ego_index = ego_index; tv.rule = rule; tv.max_advance = max_advance; tv.check_off_road = 0;
-    tv.tiles = (const float*)(d + lay.tiles);
-    tv.set_start = (const int32_t*)(d + lay.set_start);
-    tv.n_tile = (const int32_t*)(d + lay.n_tile);
-    tv.set_of_env = (const int32_t*)(d + lay.set_of_env);
-    tv.visiting = (int32_t*)(d + lay.visiting);
-    tv.num_visited = (int32_t*)(d + lay.num_visited);
-    tv.mask = (uint32_t*)(d + lay.mask);
-    tv.status = (uint8_t*)(d + lay.status);
-    tv.reward = (float*)(d + lay.reward);
-    tv.start_visiting = (const int32_t*)(d + lay.start_visiting);
-    tv.start_mask = (const uint32_t*)(d + lay.start_mask);
+    track_view_borrow(tv, d, lay);
     return T2D_OK;
 }
 
@@ -3332,10 +3249,9 @@ int t2d_track_buffers(t2d_pool* p, void** tile_visiting_dev, void** num_visited_
 
 // ---- BEV camera (kernel: t2d_camera.hip) ---------------------------------------------------------------------------------------
 static void camera_release(t2d_pool* p) {
-    for (void* b : {(void*)p->d_cam_class, (void*)p->d_cam_rgb, p->d_cam_geo})
-        if (b) (void)hipFree(b);
-    p->d_cam_class = p->d_cam_rgb = nullptr;
-    p->d_cam_geo = nullptr;
+    p->d_cam_class = {};
+    p->d_cam_rgb = {};
+    p->d_cam_geo = {};
     p->camera = t2d::CameraView{};
     p->cam_geo_gen = -1;
     p->cam_type_default = true;
@@ -3364,7 +3280,7 @@ int camera_refresh_geo(t2d_pool* p) {
         off[k][1] = take(g.ring_vert_off.size() * 4);
         off[k][2] = take(g.ring_xy.size() * 4 + 4);
     }
-    char* d = nullptr;
+    t2d::DevBuf<> blob;
     if (total) {
         std::vector<char> img(total);
         for (int k = 0; k < 2; ++k) {
@@ -3374,21 +3290,16 @@ int camera_refresh_geo(t2d_pool* p) {
             memcpy(img.data() + off[k][1], g.ring_vert_off.data(), g.ring_vert_off.size() * 4);
             if (!g.ring_xy.empty()) memcpy(img.data() + off[k][2], g.ring_xy.data(), g.ring_xy.size() * 4);
         }
-        if (hipMalloc((void**)&d, total) != hipSuccess) {
-            (void)hipGetLastError();
+        if (blob.alloc(total) != hipSuccess)
             return fail(p, T2D_ERR_NOMEM, "t2d_camera_render: " + std::to_string(total) + " bytes of device memory for the rings");
-        }
         hipError_t he = quiesce(p);   // (a render that still reads the previous copy)
-        if (he == hipSuccess) he = hipMemcpy(d, img.data(), total, hipMemcpyHostToDevice);
-        if (he != hipSuccess) {
-            (void)hipFree(d);
-            return fail(p, T2D_ERR_HIP, std::string("t2d_camera_render: ") + hipGetErrorString(he));
-        }
+        if (he == hipSuccess) he = hipMemcpy(blob, img.data(), total, hipMemcpyHostToDevice);
+        if (he != hipSuccess) return fail(p, T2D_ERR_HIP, std::string("t2d_camera_render: ") + hipGetErrorString(he));
     } else {
         T2D_HIP(p, quiesce(p));
     }
-    if (p->d_cam_geo) (void)hipFree(p->d_cam_geo);
-    p->d_cam_geo = d;
+    p->d_cam_geo = std::move(blob);
+    const char* d = (const char*)p->d_cam_geo.get();
     for (int k = 0; k < 2; ++k) {
         p->camera.env_poly_off[k] = have[k] ? (const int32_t*)(d + off[k][0]) : nullptr;
         p->camera.poly_vert_off[k] = have[k] ? (const int32_t*)(d + off[k][1]) : nullptr;
@@ -3422,30 +3333,17 @@ int t2d_camera_config(t2d_pool* p, int32_t width, int32_t height, float left, fl
     const size_t px = (size_t)width * height, blocks = (size_t)((width + 63) / 64) * ((height + 15) / 16);
     if (px * p->v.n_env * 3 > ((size_t)1 << 36) || blocks * p->v.n_env > 0x7fffffffull)
         return fail(p, T2D_ERR_INVALID, "t2d_camera_config: images too large for this pool");
-    uint8_t *dc = nullptr, *dr = nullptr;
-    if (fmt & T2D_CAMERA_FORMAT_CLASS)
-        if (hipMalloc((void**)&dc, px * p->v.n_env) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(px * p->v.n_env) + " bytes of device memory");
-        }
-    if (fmt & T2D_CAMERA_FORMAT_RGB)
-        if (hipMalloc((void**)&dr, 3 * px * p->v.n_env) != hipSuccess) {
-            (void)hipGetLastError();
-            if (dc) (void)hipFree(dc);
-            return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(3 * px * p->v.n_env) + " bytes of device memory");
-        }
+    t2d::DevBuf<uint8_t> dc, dr;
+    if ((fmt & T2D_CAMERA_FORMAT_CLASS) && dc.alloc(px * p->v.n_env) != hipSuccess)
+        return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(px * p->v.n_env) + " bytes of device memory");
+    if ((fmt & T2D_CAMERA_FORMAT_RGB) && dr.alloc(3 * px * p->v.n_env) != hipSuccess)
+        return fail(p, T2D_ERR_NOMEM, "t2d_camera_config: " + std::to_string(3 * px * p->v.n_env) + " bytes of device memory");
     const hipError_t he = quiesce(p);   // (a render into the previous images)
-    if (he != hipSuccess) {
-        if (dc) (void)hipFree(dc);
-        if (dr) (void)hipFree(dr);
-        return fail(p, T2D_ERR_HIP, std::string("t2d_camera_config: ") + hipGetErrorString(he));
-    }
+    if (he != hipSuccess) return fail(p, T2D_ERR_HIP, std::string("t2d_camera_config: ") + hipGetErrorString(he));
     t2d::CameraView& cv = p->camera;
     const bool fresh = !cv.configured;
-    if (p->d_cam_class) (void)hipFree(p->d_cam_class);
-    if (p->d_cam_rgb) (void)hipFree(p->d_cam_rgb);
-    p->d_cam_class = dc;
-    p->d_cam_rgb = dr;
+    p->d_cam_class = std::move(dc);
+    p->d_cam_rgb = std::move(dr);
     // the window: _calculate_bounds, then auto_scale widens the short side about the centre (matplotlib_renderer.py:137-232),
     // here as offsets from the sensor
     double x0 = -(double)left, x1 = (double)right, y0 = -(double)back, y1 = (double)front;

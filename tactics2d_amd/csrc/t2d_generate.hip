@@ -636,8 +636,9 @@ extern "C" int t2d_generate_parking(int32_t device_id, uint64_t seed, int64_t fi
         off[k] = total;
         total += (sizes[k] + 255) & ~(size_t)255;
     }
-    char* dev = nullptr;
-    if (hipMalloc(&dev, total) != hipSuccess) return T2D_ERR_HIP;
+    DevBuf<char> buf;
+    if (buf.alloc(total) != hipSuccess) return T2D_ERR_HIP;
+    char* const dev = buf;
     SceneView sv{};
     sv.seed = seed; sv.first_env = first_env; sv.env_stride = 0;
     sv.type_proportion = type_proportion; sv.len = vehicle_length; sv.wid = vehicle_width;
@@ -648,6 +649,5 @@ extern "C" int t2d_generate_parking(int32_t device_id, uint64_t seed, int64_t fi
         rc = T2D_ERR_HIP;
     for (int k = 0; k < 8 && rc == T2D_OK; ++k)
         if (hipMemcpy(host[k], dev + off[k], sizes[k], hipMemcpyDeviceToHost) != hipSuccess) rc = T2D_ERR_HIP;
-    (void)hipFree(dev);
     return rc;
 }

@@ -96,11 +96,6 @@ void widths(int fn, int& na, int& nb, int& nout) {
     }
 }
 
-struct DevBuf {   // (freed on every way out)
-    double* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 }  // namespace probe
 }  // namespace t2d
@@ -109,7 +104,6 @@ struct DevBuf {   // (freed on every way out)
 
 extern "C" int t2d_debug_geom(int32_t device_id, int32_t fn, int64_t n, const double* a_host, const double* b_host, double* out_host) {
     using t2d::host::fail;
-    using t2d::probe::DevBuf;
     int na, nb, nout;
     t2d::probe::widths(fn, na, nb, nout);
     if (!nout) return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_geom: fn is not one of T2D_GEOM_*");
@@ -120,17 +114,17 @@ extern "C" int t2d_debug_geom(int32_t device_id, int32_t fn, int64_t n, const do
     if (device_id < 0 || device_id >= n_dev) return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_geom: no such device");
     T2D_HIP(nullptr, hipSetDevice(device_id));
     const size_t bytes = (size_t)n * sizeof(double);
-    DevBuf a, b, out;
-    T2D_HIP(nullptr, hipMalloc((void**)&a.p, bytes * na));
-    T2D_HIP(nullptr, hipMemcpy(a.p, a_host, bytes * na, hipMemcpyHostToDevice));
+    t2d::DevBuf<double> a, b, out;   // (freed on every way out)
+    T2D_HIP(nullptr, a.alloc((size_t)n * na));
+    T2D_HIP(nullptr, hipMemcpy(a, a_host, bytes * na, hipMemcpyHostToDevice));
     if (nb) {
-        T2D_HIP(nullptr, hipMalloc((void**)&b.p, bytes * nb));
-        T2D_HIP(nullptr, hipMemcpy(b.p, b_host, bytes * nb, hipMemcpyHostToDevice));
+        T2D_HIP(nullptr, b.alloc((size_t)n * nb));
+        T2D_HIP(nullptr, hipMemcpy(b, b_host, bytes * nb, hipMemcpyHostToDevice));
     }
-    T2D_HIP(nullptr, hipMalloc((void**)&out.p, bytes * nout));
-    T2D_HIP(nullptr, hipMemset(out.p, 0xff, bytes * nout));   // (a NaN with a payload no function returns: an unwritten element shows)
-    T2D_HIP(nullptr, t2d::probe::launch(fn, n, a.p, b.p, out.p));
+    T2D_HIP(nullptr, out.alloc((size_t)n * nout));
+    T2D_HIP(nullptr, hipMemset(out, 0xff, bytes * nout));   // (a NaN with a payload no function returns: an unwritten element shows)
+    T2D_HIP(nullptr, t2d::probe::launch(fn, n, a, b, out));
     T2D_HIP(nullptr, hipDeviceSynchronize());
-    T2D_HIP(nullptr, hipMemcpy(out_host, out.p, bytes * nout, hipMemcpyDeviceToHost));
+    T2D_HIP(nullptr, hipMemcpy(out_host, out, bytes * nout, hipMemcpyDeviceToHost));
     return T2D_OK;
 }

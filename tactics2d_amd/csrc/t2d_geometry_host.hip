@@ -436,15 +436,8 @@ int build_map_grid(t2d_pool* p) {
         if ((rc = dev_replace(p, &p->d_grid_bnd, bd.data(), bd.size()))) return rc;
         mg.bnd = p->d_grid_bnd;
     }
-    if (!p->d_map_flags) {
-        T2D_HIP(p, hipMalloc((void**)&p->d_map_flags, sizeof(uint32_t) * (size_t)p->v.N));
-        T2D_HIP(p, hipMemset(p->d_map_flags, 0, sizeof(uint32_t) * (size_t)p->v.N));
-    }
-    if (!p->d_grid_seg) {
-        const size_t bytes = t2d::map_segment_bytes(p->v.N);
-        T2D_HIP(p, hipMalloc(&p->d_grid_seg, bytes));
-        T2D_HIP(p, hipMemset(p->d_grid_seg, 0, bytes));
-    }
+    if (!p->d_map_flags) T2D_HIP(p, p->d_map_flags.alloc_zeroed((size_t)p->v.N));
+    if (!p->d_grid_seg) T2D_HIP(p, p->d_grid_seg.alloc_zeroed(t2d::map_segment_bytes(p->v.N)));
     p->mapgrid = mg;
     p->grid_tier = true;
     p->v.map_flags = p->d_map_flags;

@@ -20,19 +20,15 @@ const std::string& create_error();
             return ::t2d::host::fail(p, T2D_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// replace a device buffer by a copy of n host elements (n == 0: free it)
+// replace a device buffer by a copy of n host elements (n == 0: free it); the old block goes first (lower peak)
 template <class T>
-int dev_replace(t2d_pool* p, T** dst, const T* src, size_t n) {
-    if (*dst) {
-        T2D_HIP(p, hipFree(*dst));
-        *dst = nullptr;
-    }
+int dev_replace(t2d_pool* p, DevBuf<T>* dst, const T* src, size_t n) {
+    T2D_HIP(p, dst->reset());
     if (n == 0) return T2D_OK;
-    T2D_HIP(p, hipMalloc((void**)dst, n * sizeof(T)));
-    T2D_HIP(p, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    T2D_HIP(p, dst->alloc(n));
+    T2D_HIP(p, hipMemcpy(dst->get(), src, n * sizeof(T), hipMemcpyHostToDevice));
     return T2D_OK;
 }
-
 
 // ---- geometry preparation (t2d_geometry_host.hip) -----------------------------------------------------------------------------
 double area2(const std::vector<double>& P);

@@ -125,11 +125,6 @@ int n_outputs(int fn) {
 bool two_inputs(int fn) { return fn == T2D_MATH_SINCOS_STEER_AND || fn == T2D_MATH_ATAN2 || fn == T2D_MATH_POW; }
 bool has_table_variant(int fn) { return fn >= T2D_MATH_SINCOS && fn <= T2D_MATH_ATAN2; }
 
-struct DevBuf {   // (freed on every way out)
-    double* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 extern "C" int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int64_t n, const double* a_host, const double* b_host,
@@ -148,19 +143,19 @@ extern "C" int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int6
     if (device_id < 0 || device_id >= n_dev) return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_math: no such device");
     T2D_HIP(nullptr, hipSetDevice(device_id));
     const size_t bytes = (size_t)n * sizeof(double);
-    DevBuf a, b, out;
-    T2D_HIP(nullptr, hipMalloc((void**)&a.p, bytes));
-    T2D_HIP(nullptr, hipMemcpy(a.p, a_host, bytes, hipMemcpyHostToDevice));
+    t2d::DevBuf<double> a, b, out;   // (freed on every way out)
+    T2D_HIP(nullptr, a.alloc((size_t)n));
+    T2D_HIP(nullptr, hipMemcpy(a, a_host, bytes, hipMemcpyHostToDevice));
     if (two_inputs(fn)) {
-        T2D_HIP(nullptr, hipMalloc((void**)&b.p, bytes));
-        T2D_HIP(nullptr, hipMemcpy(b.p, b_host, bytes, hipMemcpyHostToDevice));
+        T2D_HIP(nullptr, b.alloc((size_t)n));
+        T2D_HIP(nullptr, hipMemcpy(b, b_host, bytes, hipMemcpyHostToDevice));
     }
-    T2D_HIP(nullptr, hipMalloc((void**)&out.p, bytes * nout));
-    T2D_HIP(nullptr, hipMemset(out.p, 0xff, bytes * nout));   // (a NaN with a payload no function returns: an unwritten element shows)
-    T2D_HIP(nullptr, table ? t2d::probe::math_probe_launch_table(fn, n, a.p, b.p, out.p)
-                           : t2d::probe::math_probe_launch_literal(fn, n, a.p, b.p, out.p));
+    T2D_HIP(nullptr, out.alloc((size_t)n * nout));
+    T2D_HIP(nullptr, hipMemset(out, 0xff, bytes * nout));   // (a NaN with a payload no function returns: an unwritten element shows)
+    T2D_HIP(nullptr, table ? t2d::probe::math_probe_launch_table(fn, n, a, b, out)
+                           : t2d::probe::math_probe_launch_literal(fn, n, a, b, out));
     T2D_HIP(nullptr, hipDeviceSynchronize());
-    T2D_HIP(nullptr, hipMemcpy(out_host, out.p, bytes * nout, hipMemcpyDeviceToHost));
+    T2D_HIP(nullptr, hipMemcpy(out_host, out, bytes * nout, hipMemcpyDeviceToHost));
     return T2D_OK;
 }
 #endif

@@ -1,6 +1,7 @@
 // t2d_pool.h -- internal layout of a participant pool (host + device views).
 //
-// Data layout in HBM (all allocations hipMalloc'ed once in t2d_create, 256-B aligned):
+// Data layout in HBM (the field arrays are allocated once in t2d_create, every other buffer by the call that configures its
+// subsystem; hipMalloc aligns all of them to 256 B):
 //   per participant, N = n_env * max_agents, env-major (idx = env * A + agent), one
 //   contiguous array per field (Struct-of-Arrays) so a wave64 touching 64 consecutive
 //   participants issues one 256-B coalesced transaction per field:
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../include/t2d.h"
+#include "t2d_devbuf.h"
 
 namespace t2d {
 
@@ -363,22 +365,24 @@ struct t2d_pool {
     t2d_status_config status_cfg{};
     std::string err;
     double host_params[T2D_MAX_TYPES][T2D_PARAM_COLS]{};
-    // owned device buffers (freed in t2d_destroy)
-    void* field_ptr[T2D_F_COUNT]{};
+    // Ownership: every DevBuf / PinBuf member below owns its block and frees it when the pool is deleted (or when a setter
+    // resets / replaces it); the view structs next to them hold plain pointers borrowed from these owners.
+    t2d::DevBuf<> field_buf[T2D_F_COUNT];
+    void* field_ptr[T2D_F_COUNT]{};   // t2d_get_field's lookup table: field_buf[f].get()
     size_t field_bytes[T2D_F_COUNT]{};
-    double* d_params = nullptr;
-    uint32_t* d_geo = nullptr;
+    t2d::DevBuf<double> d_params;
+    t2d::DevBuf<uint32_t> d_geo;
     // the HBM grid tier of maps too large for the LDS record (rebuild_geo): device copies of the parts + the grid
     bool grid_tier = false;
     t2d::MapGridView mapgrid{};
-    t2d::MapGridEnv* d_grid_env = nullptr;
-    int32_t* d_grid_cell_start = nullptr;
-    t2d::MapItem* d_grid_items = nullptr;
-    uint32_t* d_map_flags = nullptr;
-    void* d_grid_seg = nullptr;   // t2d_mapgrid.hip: one segment per sixteen participants (poses, verdict bits, the queue of pairs to decide)
-    double* d_grid_bnd = nullptr;
-    float* d_boundary = nullptr;
-    uint8_t* d_boundary_valid = nullptr;
+    t2d::DevBuf<t2d::MapGridEnv> d_grid_env;
+    t2d::DevBuf<int32_t> d_grid_cell_start;
+    t2d::DevBuf<t2d::MapItem> d_grid_items;
+    t2d::DevBuf<uint32_t> d_map_flags;
+    t2d::DevBuf<> d_grid_seg;   // t2d_mapgrid.hip: one segment per sixteen participants (poses, verdict bits, the queue of pairs to decide)
+    t2d::DevBuf<double> d_grid_bnd;
+    t2d::DevBuf<float> d_boundary;
+    t2d::DevBuf<uint8_t> d_boundary_valid;
     // host copies of the CCW-normalised CSR geometry, kind 0 static / 1 lanes
     struct HostGeo {
         bool present = false;
@@ -397,40 +401,38 @@ struct t2d_pool {
         // lanes only: per env kSafeRects rectangles inside the union of its lanes (build_safe_rects), 4 floats each
         std::vector<float> safe;
     } hgeo[2];
-    double *d_target_xy = nullptr, *d_target_c = nullptr, *d_last_pose = nullptr, *d_max_iou = nullptr,
-           *d_min_dist = nullptr, *d_snap_min_dist = nullptr;
-    uint8_t* d_last_valid = nullptr;
+    t2d::DevBuf<double> d_target_xy, d_target_c, d_last_pose, d_max_iou, d_min_dist, d_snap_min_dist;
+    t2d::DevBuf<uint8_t> d_last_valid;
     bool have_target = false;
     // lidar (row f2)
     bool lidar_on = false;
     bool lidar_regular = true;   // the configured beams are linspace(0, 2 pi, n_beams, endpoint=False) to 1e-9 (t2d_rs_config needs that)
     t2d::LidarView lidar{};
-    int32_t *d_lidar_env_off = nullptr, *d_lidar_next = nullptr;
-    uint8_t* d_lidar_meta = nullptr;
-    float* d_lidar_xy = nullptr;
-    float* d_lidar_all = nullptr;    // [n_env][max_agents][n_beams]: the pool's own destination of t2d_lidar_scan_all (first use)
-    size_t lidar_all_bytes = 0;
-    double *d_beam_sin = nullptr, *d_beam_cos = nullptr;
-    double* d_time_penalty = nullptr;
+    t2d::DevBuf<int32_t> d_lidar_env_off;
+    t2d::DevBuf<uint8_t> d_lidar_meta;
+    t2d::DevBuf<float> d_lidar_xy;
+    t2d::DevBuf<float> d_lidar_all;   // [n_env][max_agents][n_beams]: the pool's own destination of t2d_lidar_scan_all (first use)
+    t2d::DevBuf<double> d_beam_sin;
+    t2d::DevBuf<double> d_time_penalty;
     bool has_drift = false;   // a T2D_MODEL_DRIFT row is in the parameter table
     // replayed participants (t2d_replay_bind): rows of model T2D_MODEL_REPLAY, the bound source and the device arrays of the binding
     uint32_t replay_types = 0;         // bit t: row t of the parameter table has model T2D_MODEL_REPLAY
     struct t2d_traj* replay_src = nullptr;   // null: no binding
     t2d::ReplaySpec replay{};
-    int32_t* d_replay_meta = nullptr;
+    t2d::DevBuf<int32_t> d_replay_meta;
     // off-route detector (t2d_set_routes / t2d_set_routes_from_traj): the installed routes, the assignment arrays and the pool's
     // own result buffers (first NULL-destination t2d_off_route)
     t2d::RouteView route{};
     struct t2d_traj* route_src = nullptr;   // trace routes: the bound trajectory
-    void* d_route_geo = nullptr;            // sets: verts | set_of_env | set_route_start | route_vert_off; traces: src_env | first | last
-    int32_t* d_route_of = nullptr;
-    float* d_route_thr = nullptr;
-    float* d_route_dist = nullptr;
-    uint8_t* d_route_off = nullptr;
+    t2d::DevBuf<> d_route_geo;           // sets: verts | set_of_env | set_route_start | route_vert_off; traces: src_env | first | last
+    t2d::DevBuf<int32_t> d_route_of;
+    t2d::DevBuf<float> d_route_thr;
+    t2d::DevBuf<float> d_route_dist;
+    t2d::DevBuf<uint8_t> d_route_off;
     std::vector<int32_t> route_limit;       // [E] exclusive upper bound of route_of in env e (routes of its set / max_agents)
     // racing tile progress (t2d_set_tracks): one allocation behind every pointer of the view; n_tile of each env's track
     t2d::TrackView track{};
-    void* d_track = nullptr;
+    t2d::DevBuf<> d_track;
     std::vector<int32_t> track_n_tile;      // [E]
     t2d::TrackGenView trackgen{};           // generated tracks (t2d_set_tracks_generated); tiles == nullptr: host-uploaded ones
     int trackgen_sets = 0;
@@ -440,37 +442,37 @@ struct t2d_pool {
     // BEV camera (t2d_camera_config): the view, the library's own images, the device copy of the rings (one allocation) and
     // the geometry generation it was made of (geo_gen counts every change of the host rings / the scene mode)
     t2d::CameraView camera{};
-    uint8_t *d_cam_class = nullptr, *d_cam_rgb = nullptr;
-    void* d_cam_geo = nullptr;
+    t2d::DevBuf<uint8_t> d_cam_class, d_cam_rgb;
+    t2d::DevBuf<> d_cam_geo;
     long long geo_gen = 0, cam_geo_gen = -1;
     bool cam_type_default = true;   // class_of_type follows the parameter table's shapes
-    float* d_snap_omega[2]{};
+    t2d::DevBuf<float> d_snap_omega[2];
     // IDM agents (row f3)
     bool idm_on = false;
     t2d::IdmView idm{};
-    double* d_idm_rows = nullptr;
-    uint8_t* d_idm_ctrl = nullptr;
-    float* d_snap[6]{};      // x, y, heading, speed, vx, vy at episode start
-    uint32_t* d_snap_ids = nullptr;
-    uint32_t* d_wgmap = nullptr;   // step-launch placement (t2d_debug_set_step_placement)
+    t2d::DevBuf<double> d_idm_rows;
+    t2d::DevBuf<uint8_t> d_idm_ctrl;
+    t2d::DevBuf<float> d_snap[6];     // x, y, heading, speed, vx, vy at episode start
+    t2d::DevBuf<uint32_t> d_snap_ids;
+    t2d::DevBuf<uint32_t> d_wgmap;   // step-launch placement (t2d_debug_set_step_placement)
     bool have_snapshot = false;
     bool auto_reset = false;
     // generated parking scenes (row f4): capacity-layout geometry owned by the device
     bool scene_mode = false, scene_regen = false;
     t2d::SceneView scene{};
-    void* d_scene_arrays = nullptr;   // one allocation behind scene.live / scene.staged / scene.episode
+    t2d::DevBuf<> d_scene_arrays;   // one allocation behind scene.live / scene.staged / scene.episode
     hipStream_t scene_stream = nullptr;   // staged scenes are refilled here, off the step's stream
     hipEvent_t ev_scene_commit = nullptr, ev_scene_refill = nullptr;
     bool scene_refill_pending = false;
     bool scene_commit_failed = false;
     bool scene_committed_in_step = false;   // the last step launch was the ego kernel with the commit in its epilogue
-    t2d::SceneView* d_scene_view = nullptr;
+    t2d::DevBuf<t2d::SceneView> d_scene_view;
     bool scene_commit_used = false;   // a commit launch since the last host synchronisation (its sticky error word is read then)
-    int32_t* d_lidar_cnt = nullptr;
+    t2d::DevBuf<int32_t> d_lidar_cnt;
     long long step_count = 0;  // t2d_step calls so far (selects the record ring slot)
     int derived_interval = -1; // the interval_ms column T2D_P_SUBSTEPS of the device table was derived for (-1: none yet)
     // chained multi-step launches (t2d_step_n): per-workgroup step counters + one error word behind them
-    unsigned long long* d_chain = nullptr;   // chain_slots words, then the error word
+    t2d::DevBuf<unsigned long long> d_chain;   // chain_slots words, then the error word
     int chain_slots = 0;
     uint32_t chain_count = 0;      // what every counter holds once the launches enqueued so far have run
     bool chain_steps = true;       // t2d_set_step_chaining(pool, 0, *): t2d_step_n falls back to one launch per step
@@ -487,7 +489,7 @@ struct t2d_pool {
     int chain_err_code = 0;
     bool chain_rolled_back = false;
     long long chain_rollback_step = 0;
-    uint32_t* d_ckpt = nullptr;
+    t2d::DevBuf<uint32_t> d_ckpt;
     bool ckpt_armed = false;       // every multi-step launch since the last quiesce was a CHAIN launch with a checkpoint
     uint32_t chain_sig = 0;        // shape (workgroups, split) of the last CHAIN launch whose counters d_chain holds; 0 = none
     uint32_t chain_fault = 0;      // t2d_debug_chain_fault
@@ -514,24 +516,27 @@ struct t2d_pool {
     // the Gym-API host frame (t2d_frame_config / t2d_step_host)
     uint32_t frame_sections = 0;
     t2d_frame_layout frame_layout{};
-    char* d_frame = nullptr;          // device frame (copy mode)
-    char* h_frame[T2D_MAX_HOST_FRAMES]{};   // pinned (and mapped) host frames
+    t2d::DevBuf<char> d_frame;        // device frame (copy mode)
+    t2d::PinBuf<char> h_frame[T2D_MAX_HOST_FRAMES];   // pinned (and mapped) host frames
     int n_host_frames = 0, frame_turn = 0;
-    float* h_actions = nullptr;       // pinned (and mapped) staging of the host actions, [N][2]
-    float* d_actions = nullptr;       // device copy of them (copy mode)
+    t2d::PinBuf<float> h_actions;       // pinned (and mapped) staging of the host actions, [N][2]
+    t2d::DevBuf<float> d_actions;       // device copy of them (copy mode)
     bool act_in_frame = false;        // v.act0 / v.act1 point into d_actions / the mapped h_actions (set by t2d_step_host)
     int64_t act_extent = 0;       // elements readable behind each bound action pointer (t2d_set_action_extent; 0 = not declared)
-    double* d_target_heading = nullptr;
+    t2d::DevBuf<double> d_target_heading;
     // Reeds-Shepp planner (t2d_rs_config): the view, its beam table and the pool's own plan records
     bool rs_on = false;
     t2d::RsPlanView rs{};
-    double* d_rs_beam_tab = nullptr;
-    t2d_rs_plan_record* d_rs_plan = nullptr;
+    t2d::DevBuf<double> d_rs_beam_tab;
+    t2d::DevBuf<t2d_rs_plan_record> d_rs_plan;
     // Reeds-Shepp path follower (t2d_rs_follow_config): the view, its state tables and the pool's own records
     bool rs_follow_on = false;
     t2d::RsFollowView rs_follow{};
-    t2d_rs_follow_record* d_rs_follow_rec = nullptr;
+    t2d::DevBuf<double> d_rs_follow_f64;     // what rs_follow.f64 / .i32 borrow
+    t2d::DevBuf<int32_t> d_rs_follow_i32;
+    t2d::DevBuf<t2d_rs_follow_record> d_rs_follow_rec;
     // profiling
+    t2d::DevBuf<unsigned long long> d_dbg;   // what v.dbg borrows (-DT2D_TIMING builds)
     bool profiling = false;
     static constexpr int kMaxProfSteps = 4096;
     hipEvent_t* prof_events = nullptr;  // 2 events per recorded launch
@@ -580,7 +585,7 @@ hipError_t launch_rs_follow(const PoolView& v, const RsFollowView& fv, const t2d
 hipError_t launch_rs_follow_reset(const PoolView& v, const RsFollowView& fv, const uint8_t* mask, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
-hipError_t launch_restore(const PoolView& v, float* const* snap, const uint32_t* snap_ids, int mode,
+hipError_t launch_restore(const PoolView& v, const float* const* snap, const uint32_t* snap_ids, int mode,
                           hipStream_t s);
 hipError_t launch_spin(long long ticks_100mhz, hipStream_t s);
 size_t map_segment_bytes(int n_participants);   // the walk -> decisions hand-over buffer of launch_map_events

@@ -39,6 +39,7 @@ DEBUG_SYMBOLS = {
     "t2d_debug_last_step_kernel": (C.c_char_p, []),
     "t2d_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "t2d_debug_geom": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
+    "t2d_debug_memory": (C.c_int, [C.POINTER(C.c_int64)]),
 }
 
 _debug_lib = None
@@ -88,6 +89,13 @@ def delay_gather(p, microseconds):
     """t2d_debug_delay_gather: one idle wave holds the pool's gather stream for that long"""
     _need(p)
     p._ck(p._lib.t2d_debug_delay_gather(p._h, int(microseconds)))
+
+
+def memory():
+    """t2d_debug_memory: (device bytes, device blocks, pinned bytes, pinned blocks) this library holds right now"""
+    out = (C.c_int64 * 4)()
+    assert lib().t2d_debug_memory(out) == 0
+    return tuple(out)
 
 
 def last_step_kernel():

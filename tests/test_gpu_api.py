@@ -252,9 +252,11 @@ def test_bound_action_memory_is_read_only_and_uploads_end_a_binding():
     sp = S.parking(16)
     p = ParticipantPool(sp.n_env, sp.A); sp.load(p)
     p.lidar_config(360, 20.0, False)
-    ptr = p.field_ptr(L.F_LIDAR)[0]
+    p.lidar_scan_all()                                         # (into the pool's own all-participants buffer: allocated here)
+    ptr, ptr_all = p.field_ptr(L.F_LIDAR)[0], p.lidar_all_buffer()
     p.lidar_config(360, 20.0, False)
     assert p.field_ptr(L.F_LIDAR)[0] == ptr
+    assert p.lidar_all_buffer() == ptr_all
     p.lidar_config(180, 20.0, False)
     assert p.field_ptr(L.F_LIDAR)[1] == 16 * 180 * 4
     p.close()
