@@ -1035,6 +1035,113 @@ int t2d_rs_follow(t2d_pool* pool, const t2d_rs_plan_record* plan_dev, const floa
 int t2d_rs_follow_reset(t2d_pool* pool, const uint8_t* mask_dev, void* hip_stream);
 int t2d_rs_follow_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
 
+/* Lane-keeping scripted traffic: the reference's PIDController (controller/pid_controller.py:15-470) for every controlled
+ * participant of every env in ONE launch in front of the step launch.  The reference leaves cross_track_error, target_heading
+ * and target_speed to its caller and ships no caller; here the caller is the build: the error is MEASURED against the
+ * participant's installed route (t2d_set_routes).  The action rows it writes reach the step through t2d_bind_actions_strided,
+ * as t2d_rs_follow's do; no stepping call launches the kernel, and a PID-controlled participant is not an IDM-controlled one.
+ *
+ * The law (the reference's, operation by operation in fp64; one rounding per operation):
+ *   _compute_pid(error, state, kp, ki, kd, limits)   :159-234
+ *       p = kp * error; raw = (error - prev_error) / dt (0.0 unless dt > 0); derivative = alpha * raw + (1 - alpha) *
+ *       prev_derivative; out = p + kd * derivative; with limits: out beyond one of them is set to it and counts as saturated;
+ *       integral += error * dt, or integral *= 0.99 when saturated; out += ki * integral; with limits: np.clip(out, min, max).
+ *       New state: (integral, error, derivative).
+ *   lateral (lat_mode != 0)   :333-375   error = the wrapped heading error atan2(sin(e), cos(e)), e = target_heading - heading
+ *       (lat_mode 1; target_heading takes precedence over cross_track_error) or the cross-track error (lat_mode 2);
+ *       _compute_pid WITHOUT limits (so anti-windup never acts on this side); lat_mode 2: steering = out * (2.0 / wheel_base),
+ *       and with wheel_base <= 0 the steering is 0.0 although the lateral state has been updated already (the reference catches
+ *       its own ValueError; in its "lateral" mode it re-raises -- here that participant's steering is 0.0 too and
+ *       T2D_PID_BAD_WHEEL_BASE is raised); steering = np.clip(steering, -max_steering, max_steering).  lat_mode 0: steering 0.0.
+ *   longitudinal, after the lateral side   :378-404   lon_mode 0: acceleration 0.0 (control_mode "lateral"); 1: _compute_pid on
+ *       target_speed - speed with limits (min_accel, max_accel), clipped again; 2: the IDM law of t2d_set_idm row idm_row[i] with
+ *       the leader rule of t2d_idm_actions (same operations, same bits); 3: the caller's acceleration (act_in) passed through.
+ *   ("combined" = lat_mode 1 or 2 with lon_mode 1; "lateral" = lon_mode 0; "longitudinal" = lat_mode 0 with lon_mode 1.)
+ *
+ * The measurement (BUILD-DEFINED; tests/pid_ref.py restates it in numpy).  Position = the participant's centre (x, y), as in
+ * t2d_off_route.  Over the segments A -> B of the participant's route in vertex order, zero-length segments skipped:
+ * u = B - A, w = P - A, L2 = u.u, t = w.u; d2 = |w|^2 if t <= 0, |P - B|^2 if t >= L2, else (wx uy - wy ux)^2 / L2 -- the
+ * arithmetic of t2d_off_route -- and the first strict minimum wins.  d = sqrt(d2min) (the bits of t2d_off_route's distance
+ * before its fp32 cast); c = wx uy - wy ux of the winning segment; cross_track_error = +d if c > 0, -d if c < 0, else 0.0
+ * (positive: the route lies to the LEFT of the vehicle along the direction of travel, so positive steering closes it);
+ * target_heading = atan2(uy, ux) of the winning segment (the library's own atan2).  T2D_PID_ROUTE_END is raised, and nothing
+ * else changes, when the winning segment is the route's last non-degenerate one and t >= L2 there (the nearest point is the
+ * route's last vertex).  route_of = -1, or a route of zero-length segments only, is NO ROUTE: the reference's combined-mode
+ * fallback -- steering 0.0, lateral state untouched -- with T2D_PID_NO_ROUTE.  A non-finite x / y / heading / speed (or
+ * target_speed under lon_mode 1), or a non-finite steering or acceleration: the state stays as it was, the caller's row goes
+ * through bit for bit and T2D_PID_NONFINITE is raised.  Inactive or uncontrolled participants: the caller's row, bit for bit.
+ * Episode end (t2d_rs_follow's rule): an env whose status left by the last step says terminated or truncated has the state of
+ * all its participants cleared (controller.reset()) at the start of the call, T2D_PID_RESET.
+ *
+ *   t2d_set_pid      ctrl_rows: host [n_ctrl][row_stride >= T2D_PID_COLS] fp64, 1 <= n_ctrl <= 254, validated as the
+ *                    constructor validates (:87-102: dt <= 0, max_steering <= 0, max_accel <= 0, min_accel >= 0, max_accel <=
+ *                    min_accel, alpha <= 0 or > 1 are refused; lat_mode in 0..2, lon_mode in 0..3).  wheel_base NaN = lf + lr of
+ *                    the participant's type row.  ctrl_id u8[N] (T2D_PID_NONE: uncontrolled), target_speed f32[N] (NULL: zeros),
+ *                    idm_row i32[N] (NULL: row 0; read under lon_mode 2 only).  T2D_ERR_INVALID for a participant that is IDM-
+ *                    controlled as well (t2d_set_idm refuses the same afterwards) and for an idm_row outside the installed rows;
+ *                    T2D_ERR_STATE for lon_mode 2 without installed IDM rows.  A refused call changes nothing.  Clears the state
+ *                    of every participant.  n_ctrl = 0 uninstalls.
+ *   t2d_pid_actions  one launch, asynchronous on hip_stream.  act_in_dev / act_out_dev: f32 [N][2] rows (steering, accel), may be
+ *                    the same memory; act_in_dev is never written, NULL = zeros.  Controlled rows receive the fp32 rounding of the
+ *                    fp64 action.  record_dev: t2d_pid_record [N] (8-byte aligned) or NULL = the pool's own.  T2D_ERR_STATE
+ *                    before t2d_set_pid or t2d_reset, when no route set is installed although a row has lat_mode != 0, when trace
+ *                    routes are the installed kind, and when a row has lon_mode 2 and the IDM rows it was installed against are
+ *                    gone; T2D_ERR_INVALID without act_out_dev.  kernel_id T2D_PROFILE_PID in t2d_profile_read.
+ *   t2d_pid_reset    controller.reset() for the envs whose mask byte (device memory) is non-zero, NULL = all; asynchronous.  A
+ *                    t2d_reset without a mask does the same for every env.
+ *   t2d_pid_state    the six fp64 state words of every participant, host array [N][6] in the order of T2D_PID_S_*: write = 0
+ *                    reads them (after the pool's work), write != 0 replaces them.
+ *   t2d_pid_buffers  pointer and size in bytes of the pool's own records.                                                    */
+enum {
+    T2D_PID_DT = 0,
+    T2D_PID_KP_LAT = 1,
+    T2D_PID_KI_LAT = 2,
+    T2D_PID_KD_LAT = 3,
+    T2D_PID_MAX_STEERING = 4,
+    T2D_PID_KP_LON = 5,
+    T2D_PID_KI_LON = 6,
+    T2D_PID_KD_LON = 7,
+    T2D_PID_MAX_ACCEL = 8,
+    T2D_PID_MIN_ACCEL = 9,
+    T2D_PID_ALPHA = 10,      /* derivative_filter_alpha */
+    T2D_PID_LAT_MODE = 11,   /* build column: 0 none, 1 target_heading, 2 cross_track_error */
+    T2D_PID_LON_MODE = 12,   /* build column: 0 acceleration 0.0, 1 PID on target_speed, 2 IDM law, 3 caller's acceleration */
+    T2D_PID_WHEEL_BASE = 13, /* build column: the wheel_base kwarg; NaN = lf + lr of the type row */
+    T2D_PID_COLS = 14
+};
+enum {
+    T2D_PID_S_LAT_INTEGRAL = 0,
+    T2D_PID_S_LAT_PREV_ERROR = 1,
+    T2D_PID_S_LAT_PREV_DERIVATIVE = 2,
+    T2D_PID_S_LON_INTEGRAL = 3,
+    T2D_PID_S_LON_PREV_ERROR = 4,
+    T2D_PID_S_LON_PREV_DERIVATIVE = 5,
+    T2D_PID_STATE_WORDS = 6
+};
+#define T2D_PID_NONE 255
+#define T2D_PID_ROUTE_END 1u    /* the nearest point of the route is its last vertex */
+#define T2D_PID_NONFINITE 2u    /* non-finite input or result: state kept, the caller's row passed through */
+#define T2D_PID_RESET 4u        /* the episode ended in the last step: controller.reset() */
+#define T2D_PID_NO_ROUTE 8u     /* lat_mode != 0 without a route: steering 0.0, lateral state untouched */
+#define T2D_PID_BAD_WHEEL_BASE 16u /* cross-track mode with wheel_base <= 0: lateral state updated, steering 0.0 */
+#define T2D_PID_SATURATED 32u   /* the longitudinal PID saturated without its integral term (leaky integration) */
+#define T2D_PROFILE_PID 15
+typedef struct t2d_pid_record {     /* 48 bytes */
+    double cross_track;             /* the measured cross_track_error (m), NaN without a measurement */
+    double lat_error;               /* what the lateral PID saw (lat_mode 1: the wrapped heading error), NaN when it did not run */
+    int32_t segment;                /* index of the winning segment within the route, -1 without a measurement */
+    int32_t leader;                 /* lon_mode 2: agent index of the chosen leader, else -1 */
+    uint32_t events;                /* T2D_PID_* of this call */
+    uint32_t reserved;              /* 0 */
+    double action[2];               /* the applied (steering, accel) in fp64, NaN when the caller's row went through */
+} t2d_pid_record;
+int t2d_set_pid(t2d_pool* pool, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
+                const float* target_speed, const int32_t* idm_row);
+int t2d_pid_actions(t2d_pool* pool, const float* act_in_dev, float* act_out_dev, t2d_pid_record* record_dev, void* hip_stream);
+int t2d_pid_reset(t2d_pool* pool, const uint8_t* env_mask_dev, void* hip_stream);
+int t2d_pid_state(t2d_pool* pool, double* state_host, int32_t write);
+int t2d_pid_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
+
 /* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
  * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
  *
@@ -1186,7 +1293,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * kernel_id: 0 = integrate, 1 = collide(+status), 2 = fused step, 3 = lidar, 4 = idm, 5 = drift, 6 = scene regeneration,
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
- * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow).  */
+ * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
+ * 15 = lane-keeping PID controllers (t2d_pid_actions).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

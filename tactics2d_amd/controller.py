@@ -1,4 +1,4 @@
-"""Host-side mirror of the reference's IDM controller for the batched device path (scope row f3).
+"""Host-side mirrors of the reference's IDM and PID controllers for the batched device path (scope row f3).
 
 Reference: `tactics2d.controller.IDMController` (controller/idm_controller.py:15-157): same
 constructor arguments and defaults, `configure(**kwargs)` with the same AttributeError, and `step`
@@ -85,3 +85,233 @@ def install(pool, controllers, ctrl_id):
     """controllers: sequence of IDMController; ctrl_id[n]: index into it or layout.IDM_NONE."""
     rows = np.stack([c.row() for c in controllers]) if len(controllers) else None
     pool.set_idm(rows, ctrl_id)
+
+
+# ---------------------------------------------------------------------------------------------------- PID (lane keeping)
+_PID_PARAMS = ("dt", "kp_lat", "ki_lat", "kd_lat", "max_steering", "kp_lon", "ki_lon", "kd_lon", "max_accel", "min_accel")
+_PID_MODES = ("combined", "lateral", "longitudinal")
+# update_driving_style: parameter -> (value at style -1, value at style +1), pid_controller.py:120-124
+_PID_STYLE = {"kp_lat": (1.0, 2.0), "kp_lon": (1.5, 2.5), "max_steering": (0.4, 0.6), "max_accel": (2.5, 3.5), "min_accel": (-4.0, -6.0)}
+_LATERAL = {"cross_track": L.PID_LAT_CROSS_TRACK, "heading": L.PID_LAT_HEADING}
+_LONGITUDINAL = {"pid": L.PID_LON_SPEED, "idm": L.PID_LON_IDM, "caller": L.PID_LON_CALLER}
+
+
+def _pid_check(dt=None, control_mode=None, max_steering=None, max_accel=None, min_accel=None, derivative_filter_alpha=None):
+    """the constructor's refusals (pid_controller.py:82-102), comparison by comparison; None = not given"""
+    if control_mode is not None and control_mode not in _PID_MODES:
+        raise ValueError(f"control_mode: one of {_PID_MODES} expected, not {control_mode!r}")
+    if dt is not None and dt <= 0:
+        raise ValueError(f"dt = {dt}: a positive time step expected")
+    if max_steering is not None and max_steering <= 0:
+        raise ValueError(f"max_steering = {max_steering}: a positive angle expected")
+    if max_accel is not None and max_accel <= 0:
+        raise ValueError(f"max_accel = {max_accel}: a positive acceleration expected")
+    if min_accel is not None and min_accel >= 0:
+        raise ValueError(f"min_accel = {min_accel}: a negative acceleration (a deceleration) expected")
+    if max_accel is not None and min_accel is not None and max_accel <= min_accel:
+        raise ValueError(f"max_accel = {max_accel} does not exceed min_accel = {min_accel}")
+    if derivative_filter_alpha is not None and (derivative_filter_alpha <= 0 or derivative_filter_alpha > 1):
+        raise ValueError(f"derivative_filter_alpha = {derivative_filter_alpha} outside (0, 1]")
+
+
+def pid_term(error, state, kp, ki, kd, dt, alpha, limits=None):
+    """`PIDController._compute_pid` (pid_controller.py:159-234) on float64 scalars, one rounding per operation: returns
+    (output, (integral, prev_error, prev_derivative), saturated).  state = (integral, prev_error, prev_derivative)."""
+    f = np.float64
+    error, (integral, prev_error, prev_der) = f(error), (f(v) for v in state)
+    kp, ki, kd, dt, alpha = f(kp), f(ki), f(kd), f(dt), f(alpha)
+    with np.errstate(all="ignore"):
+        raw = (error - prev_error) / dt if dt > 0 else f(0.0)
+        der = alpha * raw + (f(1.0) - alpha) * prev_der
+        out = kp * error + kd * der
+        saturated = False
+        if limits is not None:
+            lo, hi = f(limits[0]), f(limits[1])
+            if out > hi:
+                saturated, out = True, hi
+            elif out < lo:
+                saturated, out = True, lo
+        integral = integral * f(0.99) if saturated else integral + error * dt
+        out = out + ki * integral
+        if limits is not None:
+            out = np.clip(out, lo, hi)
+    return f(out), (f(integral), error, f(der)), saturated
+
+
+class PIDController:
+    """`tactics2d.controller.PIDController` (controller/pid_controller.py:15-470): the same constructor arguments, defaults and
+    refusals, `step`, `reset`, `configure` and `update_driving_style`.  One object is one parameter set of the device path
+    (`row()`, `install_pid`); its own `step` evaluates the restated law in numpy on the host, one participant at a time, with
+    the reference's calling convention (the caller supplies target_heading / cross_track_error / target_speed / wheel_base).
+
+    Build columns of the device row (include/t2d.h, t2d_set_pid): `lateral` = "cross_track" or "heading" says which error the
+    kernel measures against the installed route when the control mode has a lateral side; `longitudinal` = "pid" (the
+    reference's), "idm" (the IDM law with the leader rule of t2d_idm_actions) or "caller" (the acceleration of the caller's
+    row); `wheel_base` = the kwarg of `step` (None: lf + lr of the participant's type)."""
+
+    def __init__(self, dt=0.05, control_mode="combined", kp_lat=1.5, ki_lat=0.2, kd_lat=0.5, max_steering=0.5, kp_lon=2.0,
+                 ki_lon=0.3, kd_lon=0.4, max_accel=3.0, min_accel=-5.0, derivative_filter_alpha=0.1, lateral="cross_track",
+                 longitudinal="pid", wheel_base=None):
+        _pid_check(dt, control_mode, max_steering, max_accel, min_accel, derivative_filter_alpha)
+        if lateral not in _LATERAL or longitudinal not in _LONGITUDINAL:
+            raise ValueError(f"lateral: one of {sorted(_LATERAL)}, longitudinal: one of {sorted(_LONGITUDINAL)}")
+        self.dt, self.control_mode = dt, control_mode
+        self.kp_lat, self.ki_lat, self.kd_lat, self.max_steering = kp_lat, ki_lat, kd_lat, max_steering
+        self.kp_lon, self.ki_lon, self.kd_lon, self.max_accel, self.min_accel = kp_lon, ki_lon, kd_lon, max_accel, min_accel
+        self._derivative_filter_alpha = derivative_filter_alpha
+        self.lateral, self.longitudinal, self.wheel_base = lateral, longitudinal, wheel_base
+        self.reset()
+
+    def reset(self):
+        self._lat = (np.float64(0.0),) * 3   # integral, prev_error, prev_derivative
+        self._lon = (np.float64(0.0),) * 3
+
+    @property
+    def state(self):
+        """the six state words in the order of t2d_pid_state"""
+        return np.array(self._lat + self._lon, np.float64)
+
+    @state.setter
+    def state(self, words):
+        w = [np.float64(v) for v in words]
+        self._lat, self._lon = tuple(w[:3]), tuple(w[3:6])
+
+    def update_driving_style(self, style_id):
+        """pid_controller.py:136-157: kp_lat, kp_lon, max_steering, max_accel and min_accel by the reference's interpolator --
+        linear between style -1 and +1, the end values beyond (controller_base.py:69-91).  Re-install on the pool afterwards."""
+        if not isinstance(style_id, (int, float)):
+            raise TypeError("style_id: an int or a float expected")
+        s = np.float64(style_id)
+        for name, (left, right) in _PID_STYLE.items():
+            left, right = np.float64(left), np.float64(right)
+            if s < -1.0:
+                v = left
+            elif s > 1.0:
+                v = right
+            else:   # (slope * (x - x_left) + y_left: the order of scipy's linear interp1d)
+                v = (right - left) / np.float64(2.0) * (s - np.float64(-1.0)) + left
+            setattr(self, name, float(v))
+
+    def configure(self, **kwargs):
+        """pid_controller.py:420-470: every value is checked before any is applied; re-install on the pool afterwards."""
+        names = set(_PID_PARAMS) | {"control_mode", "derivative_filter_alpha"}
+        for key in kwargs:
+            if key not in names:
+                raise AttributeError(f"PIDController has no parameter '{key}'")
+        _pid_check(**{k: kwargs[k] for k in ("dt", "control_mode", "max_steering", "max_accel", "min_accel",
+                                              "derivative_filter_alpha") if k in kwargs})
+        for key, value in kwargs.items():
+            setattr(self, "_derivative_filter_alpha" if key == "derivative_filter_alpha" else key, value)
+
+    def modes(self):
+        """(lat_mode, lon_mode) of the device row"""
+        lat = _LATERAL[self.lateral] if self.control_mode in ("combined", "lateral") else L.PID_LAT_NONE
+        lon = _LONGITUDINAL[self.longitudinal] if self.control_mode in ("combined", "longitudinal") else L.PID_LON_ZERO
+        return lat, lon
+
+    def row(self):
+        r = np.zeros(L.PID_COLS)
+        for k, name in enumerate(_PID_PARAMS):
+            r[k] = float(getattr(self, name))
+        r[L.PID_ALPHA] = float(self._derivative_filter_alpha)
+        r[L.PID_LAT_MODE], r[L.PID_LON_MODE] = self.modes()
+        r[L.PID_WHEEL_BASE] = np.nan if self.wheel_base is None else float(self.wheel_base)
+        return r
+
+    def step(self, ego_state, **kwargs):
+        """`PIDController.step(ego_state, **kwargs)` (:309-406) for one participant on the host: (steering, acceleration)."""
+        num = (int, float)
+        steering = acceleration = 0.0
+        if self.control_mode in ("combined", "lateral"):
+            try:
+                if "target_heading" in kwargs:
+                    if not isinstance(kwargs["target_heading"], num):
+                        raise TypeError("target_heading: a number expected")
+                    e = np.float64(kwargs["target_heading"]) - np.float64(ego_state.heading)
+                    err = np.float64(np.arctan2(np.sin(e), np.cos(e)))
+                elif "cross_track_error" in kwargs:
+                    if not isinstance(kwargs["cross_track_error"], num):
+                        raise TypeError("cross_track_error: a number expected")
+                    err = np.float64(kwargs["cross_track_error"])
+                else:
+                    raise ValueError("the lateral side needs target_heading or cross_track_error")
+                out, self._lat, _ = pid_term(err, self._lat, self.kp_lat, self.ki_lat, self.kd_lat, self.dt,
+                                             self._derivative_filter_alpha)
+                if "cross_track_error" in kwargs:
+                    wb = kwargs.get("wheel_base", 2.637)
+                    if wb <= 0:
+                        raise ValueError(f"wheel_base = {wb}: a positive length expected")
+                    out = out * (np.float64(2.0) / np.float64(wb))
+                steering = np.clip(out, -np.float64(self.max_steering), np.float64(self.max_steering))
+            except (ValueError, TypeError):
+                if self.control_mode == "lateral":
+                    raise
+                steering = 0.0
+        if self.control_mode in ("combined", "longitudinal"):
+            try:
+                if "target_speed" not in kwargs:
+                    raise ValueError("the longitudinal side needs target_speed")
+                if not isinstance(kwargs["target_speed"], num):
+                    raise TypeError("target_speed: a number expected")
+                speed = ego_state.speed if ego_state.speed is not None else 0.0
+                lim = (self.min_accel, self.max_accel)
+                out, self._lon, _ = pid_term(np.float64(kwargs["target_speed"]) - np.float64(speed), self._lon, self.kp_lon,
+                                             self.ki_lon, self.kd_lon, self.dt, self._derivative_filter_alpha, lim)
+                acceleration = np.clip(out, np.float64(lim[0]), np.float64(lim[1]))
+            except (ValueError, TypeError):
+                if self.control_mode == "longitudinal":
+                    raise
+                acceleration = 0.0
+        return steering, acceleration
+
+
+def install_pid(pool, controllers, ctrl_id, target_speed=0.0, idm=None):
+    """controllers: sequence of PIDController; ctrl_id[n]: index into it or layout.PID_NONE; target_speed[n] (a scalar
+    broadcasts); idm[n]: for participants whose controller has longitudinal="idm", the row of the IDM parameter sets installed
+    with `install` / pool.set_idm (None: row 0).  An empty sequence uninstalls."""
+    rows = np.stack([c.row() for c in controllers]) if len(controllers) else None
+    pool.set_pid(rows, ctrl_id, target_speed, idm)
+
+
+PID_EVENTS = ("route_end", "nonfinite", "reset", "no_route", "bad_wheel_base", "saturated")   # bit k: layout.PID_*
+
+
+class LaneKeeper:
+    """The controllers installed on `pool` (install_pid) in a step_torch-style loop: follow() writes the action rows to step
+    with -- bind them with pool.bind_actions(rows + 4 bytes, rows, stride=2) -- and returns zero-copy torch views of the
+    records (ParticipantPool.pid_records) beside them."""
+
+    def __init__(self, pool):
+        self.pool = pool
+        self._rec = self._views = self._act = None
+
+    def follow(self, actions=None, out=None, stream=None):
+        """actions: float32 CUDA tensor [n, 2] (steering, accel), the rows of whoever else acts (None: zeros), never written
+        unless it is also `out`; out: float32 [n, 2] tensor for the rows to step (None: a buffer of the keeper's own).
+        Asynchronous on `stream`.  Returns dict(action_rows, cross_track, lat_error, segment, leader, events, action), valid until
+        the next follow()."""
+        import torch
+        pool = self.pool
+        dev = torch.device("cuda", pool.device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        for t in (actions, out):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n, 2) or not t.is_contiguous()):
+                raise ValueError(f"action rows must be a contiguous float32 [{pool.n}, 2] tensor")
+        if self._rec is None:
+            self._rec = torch.zeros((pool.n, L.PID_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
+            self._views = pool.pid_records(self._rec.data_ptr(), owner=self._rec)
+            self._act = torch.zeros((pool.n, 2), dtype=torch.float32, device=dev)
+        rows = self._act if out is None else out
+        pool.pid_actions(None if actions is None else actions.data_ptr(), rows.data_ptr(), self._rec.data_ptr(), st.cuda_stream)
+        return dict(self._views, action_rows=rows)
+
+    def reset(self, mask=None, stream=None):
+        """controller.reset() for the envs where `mask` (a uint8 / bool CUDA tensor [n_env]) is non-zero; None: every env"""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.pool.device_id))
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+            if tuple(mask.shape) != (self.pool.n_env,):
+                raise ValueError(f"mask must have {self.pool.n_env} elements")
+            self._mask = mask   # (kept alive until the launch has run)
+        self.pool.pid_reset(None if mask is None else mask.data_ptr(), st.cuda_stream)

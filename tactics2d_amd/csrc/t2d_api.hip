@@ -870,6 +870,10 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
     // (an armed auto-reset may put the snapshot's ids back into any env from the next step on)
     p->types_used = types_used | (p->auto_reset ? p->snap_types : 0u);
     p->have_reset = true;
+    if (!partial && p->pid_on) {   // new episodes everywhere: controller.reset()
+        const int rc = t2d_pid_reset(p, nullptr, nullptr);
+        if (rc != T2D_OK) return rc;
+    }
     if (!partial && p->rs_follow_on) return t2d_rs_follow_reset(p, nullptr, nullptr);   // new episodes everywhere: agent.reset()
     return T2D_OK;
 }
@@ -2392,6 +2396,10 @@ int t2d_set_idm(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t ro
         if (ctrl_id[i] != T2D_IDM_NONE && ctrl_id[i] >= n_ctrl)
             return fail(p, T2D_ERR_INVALID, "t2d_set_idm: ctrl_id[" + std::to_string(i) + "] = " +
                                                 std::to_string((int)ctrl_id[i]) + " out of range");
+    if (p->pid_on)   // (a PID-controlled participant is not an IDM-controlled one: t2d_set_pid)
+        for (int i = 0; i < p->v.N; ++i)
+            if (ctrl_id[i] != T2D_IDM_NONE && p->pid_ctrl_host[i] != T2D_PID_NONE)
+                return fail(p, T2D_ERR_INVALID, "t2d_set_idm: participant " + std::to_string(i) + " is PID-controlled (t2d_set_pid)");
     int rc;
     if ((rc = dev_replace(p, &p->d_idm_rows, rows.data(), rows.size()))) return rc;
     if ((rc = dev_replace(p, &p->d_idm_ctrl, ctrl_id, (size_t)p->v.N))) return rc;
@@ -2410,6 +2418,167 @@ int t2d_idm_actions(t2d_pool* p, const int32_t* forced_leader_dev, void* hip_str
     if (!p->idm_on) return fail(p, T2D_ERR_STATE, "t2d_set_idm must precede t2d_idm_actions");
     if (!p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_idm_actions");
     return idm_impl(p, (hipStream_t)hip_stream, forced_leader_dev);
+}
+
+// ---- lane-keeping PID controllers (kernel: t2d_pid.hip) --------------------------------------------------------------------
+int t2d_set_pid(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
+                const float* target_speed, const int32_t* idm_row) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (n_ctrl == 0) {
+        T2D_HIP(p, quiesce(p));
+        p->pid_on = false;
+        p->pid = t2d::PidView{};
+        p->pid_ctrl_host.clear();
+        p->pid_any_lat = false;
+        p->pid_idm_rows_needed = 0;
+        return T2D_OK;
+    }
+    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= T2D_PID_NONE || row_stride < T2D_PID_COLS)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_pid: need 1..254 parameter sets of >= 14 columns and a controller id per participant");
+    const int N = p->v.N;
+    std::vector<double> rows((size_t)n_ctrl * T2D_PID_COLS);
+    std::vector<int> lon_of(n_ctrl);
+    bool any_lat = false;
+    for (int c = 0; c < n_ctrl; ++c) {
+        const double* r = ctrl_rows + (size_t)c * row_stride;
+        for (int k = 0; k < T2D_PID_COLS; ++k) rows[(size_t)c * T2D_PID_COLS + k] = r[k];
+        const std::string row = " (row " + std::to_string(c) + ")";
+        // pid_controller.py:87-102, comparison by comparison
+        if (r[T2D_PID_DT] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: dt must be positive" + row);
+        if (r[T2D_PID_MAX_STEERING] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_steering must be positive" + row);
+        if (r[T2D_PID_MAX_ACCEL] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_accel must be positive" + row);
+        if (r[T2D_PID_MIN_ACCEL] >= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: min_accel must be negative (deceleration)" + row);
+        if (r[T2D_PID_MAX_ACCEL] <= r[T2D_PID_MIN_ACCEL])
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_accel must be greater than min_accel" + row);
+        if (r[T2D_PID_ALPHA] <= 0 || r[T2D_PID_ALPHA] > 1)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: derivative_filter_alpha must be in range (0, 1]" + row);
+        const double lat = r[T2D_PID_LAT_MODE], lon = r[T2D_PID_LON_MODE];
+        if (!(lat == 0.0 || lat == 1.0 || lat == 2.0) || !(lon == 0.0 || lon == 1.0 || lon == 2.0 || lon == 3.0))
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: lat_mode must be 0, 1 or 2 and lon_mode 0, 1, 2 or 3" + row);
+        lon_of[c] = (int)lon;
+        any_lat = any_lat || lat != 0.0;
+    }
+    T2D_HIP(p, quiesce(p));
+    std::vector<uint8_t> idm_ctrl;
+    if (p->idm_on) {
+        idm_ctrl.resize(N);
+        T2D_HIP(p, hipMemcpy(idm_ctrl.data(), p->d_idm_ctrl, (size_t)N, hipMemcpyDeviceToHost));
+    }
+    std::vector<float> ts(N, 0.f);
+    std::vector<int32_t> irow(N, 0);
+    int idm_needed = 0;
+    for (int i = 0; i < N; ++i) {
+        if (target_speed) ts[i] = target_speed[i];
+        if (ctrl_id[i] == T2D_PID_NONE) continue;
+        if (ctrl_id[i] >= n_ctrl)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: ctrl_id[" + std::to_string(i) + "] = " + std::to_string((int)ctrl_id[i]) +
+                                                " out of range");
+        if (p->idm_on && idm_ctrl[i] != T2D_IDM_NONE)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: participant " + std::to_string(i) + " is IDM-controlled (t2d_set_idm)");
+        if (lon_of[ctrl_id[i]] == 2) {
+            if (!p->idm_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid: lon_mode 2 needs the parameter sets of t2d_set_idm");
+            irow[i] = idm_row ? idm_row[i] : 0;
+            if (irow[i] < 0 || irow[i] >= p->idm.n_ctrl)
+                return fail(p, T2D_ERR_INVALID, "t2d_set_pid: idm_row[" + std::to_string(i) + "] = " + std::to_string(irow[i]) +
+                                                    " outside the installed IDM rows");
+            idm_needed = std::max(idm_needed, irow[i] + 1);
+        }
+    }
+    // everything new first, the installed controllers go only when nothing can fail any more
+    t2d::DevBuf<double> d_rows, d_state;
+    t2d::DevBuf<uint8_t> d_ctrl;
+    t2d::DevBuf<float> d_ts;
+    t2d::DevBuf<int32_t> d_irow;
+    t2d::DevBuf<t2d_pid_record> d_rec;
+    int rc;
+    if ((rc = dev_replace(p, &d_rows, rows.data(), rows.size()))) return rc;
+    if ((rc = dev_replace(p, &d_ctrl, ctrl_id, (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &d_ts, ts.data(), (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &d_irow, irow.data(), (size_t)N))) return rc;
+    T2D_HIP(p, d_state.alloc_zeroed((size_t)T2D_PID_STATE_WORDS * N));
+    T2D_HIP(p, d_rec.alloc_zeroed((size_t)N));
+    p->d_pid_rows = std::move(d_rows);
+    p->d_pid_ctrl = std::move(d_ctrl);
+    p->d_pid_target = std::move(d_ts);
+    p->d_pid_idm_row = std::move(d_irow);
+    p->d_pid_state = std::move(d_state);
+    p->d_pid_rec = std::move(d_rec);
+    p->pid_ctrl_host.assign(ctrl_id, ctrl_id + N);
+    p->pid_any_lat = any_lat;
+    p->pid_idm_rows_needed = idm_needed;
+    t2d::PidView& cv = p->pid;
+    cv = t2d::PidView{};
+    cv.rows = p->d_pid_rows;
+    cv.ctrl_id = p->d_pid_ctrl;
+    cv.target_speed = p->d_pid_target;
+    cv.idm_row = p->d_pid_idm_row;
+    cv.state = p->d_pid_state;
+    cv.n_ctrl = n_ctrl;
+    cv.stage_xy = idm_needed > 0;
+    p->pid_on = true;
+    return T2D_OK;
+}
+
+int t2d_pid_actions(t2d_pool* p, const float* act_in_dev, float* act_out_dev, t2d_pid_record* record_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_actions");
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_pid_actions");
+    if (p->route.kind == 2)
+        return fail(p, T2D_ERR_STATE, "t2d_pid_actions follows route sets (t2d_set_routes); trace routes are the installed kind");
+    if (p->pid_any_lat && p->route.kind != 1)
+        return fail(p, T2D_ERR_STATE, "t2d_pid_actions: a row has lat_mode != 0 and no route set is installed (t2d_set_routes)");
+    if (p->pid_idm_rows_needed > 0 && (!p->idm_on || p->idm.n_ctrl < p->pid_idm_rows_needed))
+        return fail(p, T2D_ERR_STATE, "t2d_pid_actions: the IDM parameter sets lon_mode 2 was installed against are gone (t2d_set_idm)");
+    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, "t2d_pid_actions: act_out_dev is required");
+    if (reinterpret_cast<uintptr_t>(record_dev) & 7u) return fail(p, T2D_ERR_INVALID, "t2d_pid_actions: record_dev must be 8-byte aligned");
+    t2d::PidView cv = p->pid;
+    cv.idm_rows = p->idm_on ? p->d_idm_rows.get() : nullptr;
+    cv.n_idm = p->idm_on ? p->idm.n_ctrl : 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc;
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_PID, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_pid(p->v, cv, p->route, act_in_dev, act_out_dev, record_dev ? record_dev : p->d_pid_rec.get(), s));
+    return record_event(p, T2D_PROFILE_PID, s, false);
+}
+
+int t2d_pid_reset(t2d_pool* p, const uint8_t* env_mask_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_reset");
+    hipStream_t s = (hipStream_t)hip_stream;
+    touch(p, s);
+    T2D_HIP(p, t2d::launch_pid_reset(p->v, p->pid, env_mask_dev, s));
+    return T2D_OK;
+}
+
+int t2d_pid_state(t2d_pool* p, double* state_host, int32_t write) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!state_host) return fail(p, T2D_ERR_INVALID, "t2d_pid_state: null array");
+    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_state");
+    T2D_HIP(p, hipSetDevice(p->device));
+    T2D_HIP(p, quiesce(p));
+    const size_t N = (size_t)p->v.N;
+    std::vector<double> soa((size_t)T2D_PID_STATE_WORDS * N);   // the device's layout: [word][participant]
+    if (write) {
+        for (size_t i = 0; i < N; ++i)
+            for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) soa[w * N + i] = state_host[i * T2D_PID_STATE_WORDS + w];
+        T2D_HIP(p, hipMemcpy(p->d_pid_state, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        T2D_HIP(p, hipMemcpy(soa.data(), p->d_pid_state, soa.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < N; ++i)
+            for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) state_host[i * T2D_PID_STATE_WORDS + w] = soa[w * N + i];
+    }
+    return T2D_OK;
+}
+
+int t2d_pid_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_buffers");
+    *records_dev = p->d_pid_rec;
+    *nbytes = (size_t)p->v.N * sizeof(t2d_pid_record);
+    return T2D_OK;
 }
 
 int t2d_verify_state(t2d_pool* p, const float* x_dev, const float* y_dev, const float* heading_dev,

@@ -345,6 +345,19 @@ struct RsFollowView {
     int32_t ego_index;
 };
 
+// Lane-keeping PID controllers (t2d_pid.hip): parameter sets, the per-participant assignment and the controllers' state,
+// struct-of-arrays -- word w of participant i is state[w * N + i] -- so a wave's loads and stores of one word coalesce.
+struct PidView {
+    const double* rows;          // [n_ctrl][T2D_PID_COLS]
+    const uint8_t* ctrl_id;      // [N] index into rows, T2D_PID_NONE = the caller's row goes through
+    const float* target_speed;   // [N]
+    const int32_t* idm_row;      // [N] row of idm_rows (lon_mode 2)
+    double* state;               // [T2D_PID_STATE_WORDS][N]
+    const double* idm_rows;      // [n_idm][T2D_IDM_COLS] the installed IDM parameter sets, or null
+    int32_t n_ctrl, n_idm;
+    int32_t stage_xy;            // some row has lon_mode 2: the env's (x, y, speed) go through LDS for the leader rule
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -535,6 +548,18 @@ struct t2d_pool {
     t2d::DevBuf<double> d_rs_follow_f64;     // what rs_follow.f64 / .i32 borrow
     t2d::DevBuf<int32_t> d_rs_follow_i32;
     t2d::DevBuf<t2d_rs_follow_record> d_rs_follow_rec;
+    // lane-keeping PID controllers (t2d_set_pid): the view, what it borrows, the pool's own records and the host's copy of the
+    // assignment (t2d_set_idm checks new IDM assignments against it)
+    bool pid_on = false;
+    t2d::PidView pid{};
+    t2d::DevBuf<double> d_pid_rows, d_pid_state;
+    t2d::DevBuf<uint8_t> d_pid_ctrl;
+    t2d::DevBuf<float> d_pid_target;
+    t2d::DevBuf<int32_t> d_pid_idm_row;
+    t2d::DevBuf<t2d_pid_record> d_pid_rec;
+    std::vector<uint8_t> pid_ctrl_host;
+    bool pid_any_lat = false;        // some installed row has lat_mode != 0: a call needs route sets
+    int pid_idm_rows_needed = 0;     // lon_mode 2: 1 + the largest idm_row in use (0: no such participant)
     // profiling
     t2d::DevBuf<unsigned long long> d_dbg;   // what v.dbg borrows (-DT2D_TIMING builds)
     bool profiling = false;
@@ -583,6 +608,11 @@ hipError_t launch_rs_plan(const PoolView& v, const RsPlanView& rv, const float* 
 hipError_t launch_rs_follow(const PoolView& v, const RsFollowView& fv, const t2d_rs_plan_record* plan, const float* act_in,
                             float* act_out, t2d_rs_follow_record* out, hipStream_t s);
 hipError_t launch_rs_follow_reset(const PoolView& v, const RsFollowView& fv, const uint8_t* mask, hipStream_t s);
+// lane-keeping PID controllers (t2d_pid.hip): one action row and one record per participant; controller.reset() for the masked
+// envs (null: all)
+hipError_t launch_pid(const PoolView& v, const PidView& cv, const RouteView& rv, const float* act_in, float* act_out,
+                      t2d_pid_record* out, hipStream_t s);
+hipError_t launch_pid_reset(const PoolView& v, const PidView& cv, const uint8_t* mask, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, const float* const* snap, const uint32_t* snap_ids, int mode,

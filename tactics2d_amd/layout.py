@@ -71,6 +71,18 @@ IDM_LANE_HALF_WIDTH, IDM_HORIZON = 6, 7
 IDM_COLS = 8
 IDM_NONE = 255
 IDM_LEADER_FREE, IDM_LEADER_SEARCH = -1, -2
+# lane-keeping PID controllers (t2d_set_pid / t2d_pid_actions): parameter-row columns, state words, event bits, the record's
+# size in bytes, the kernel id
+PID_DT, PID_KP_LAT, PID_KI_LAT, PID_KD_LAT, PID_MAX_STEERING, PID_KP_LON, PID_KI_LON, PID_KD_LON = range(8)
+PID_MAX_ACCEL, PID_MIN_ACCEL, PID_ALPHA, PID_LAT_MODE, PID_LON_MODE, PID_WHEEL_BASE = range(8, 14)
+PID_COLS = 14
+PID_LAT_NONE, PID_LAT_HEADING, PID_LAT_CROSS_TRACK = 0, 1, 2     # values of the lat_mode column
+PID_LON_ZERO, PID_LON_SPEED, PID_LON_IDM, PID_LON_CALLER = 0, 1, 2, 3   # values of the lon_mode column
+PID_STATE_WORDS = 6   # lat integral, prev_error, prev_derivative, then the same three of the longitudinal side
+PID_NONE = 255
+PID_ROUTE_END, PID_NONFINITE, PID_RESET, PID_NO_ROUTE, PID_BAD_WHEEL_BASE, PID_SATURATED = 1, 2, 4, 8, 16, 32
+PID_RECORD_BYTES = 48
+PROFILE_PID = 15
 # host-frame sections (t2d_frame_config)
 FRAME_LIDAR, FRAME_TARGET, FRAME_ZEROCOPY = 1, 2, 4
 # device-resident trajectories (t2d_traj_*): column order of a slot

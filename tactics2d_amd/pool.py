@@ -314,6 +314,58 @@ class ParticipantPool:
         """IDMController.step for every controlled participant (also runs inside step()/integrate())."""
         self._ck(self._lib.t2d_idm_actions(self._h, forced_leader_ptr, stream))
 
+    # ---------------------------------------------------------------- lane-keeping PID controllers
+    def set_pid(self, ctrl_rows, ctrl_id=None, target_speed=None, idm_row=None):
+        """Install PID controllers (t2d_set_pid): ctrl_rows [n_ctrl, 14] (layout.PID_*; controller.PIDController.row()), ctrl_id
+        uint8 [n] (PID_NONE = the caller's row goes through), target_speed float32 [n] (a scalar broadcasts; None: zeros),
+        idm_row int32 [n] (rows of set_idm for lon_mode 2; None: row 0).  ctrl_rows=None uninstalls."""
+        if ctrl_rows is None:
+            self._ck(self._lib.t2d_set_pid(self._h, None, 0, 0, None, None, None))
+            return
+        rows = np.ascontiguousarray(ctrl_rows, np.float64)
+        if rows.ndim != 2:
+            raise ValueError("ctrl_rows must be 2-D [n_ctrl, >= 14]")
+        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
+        ts = None if target_speed is None else _arr(np.broadcast_to(np.asarray(target_speed, np.float32).reshape(-1)
+                                                    if np.ndim(target_speed) else np.float32(target_speed), (self.n,)),
+                                                    np.float32, self.n, "target_speed")
+        ir = _arr(idm_row, np.int32, self.n, "idm_row")
+        self._ck(self._lib.t2d_set_pid(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid), _p(ts), _p(ir)))
+
+    def pid_actions(self, act_in_ptr, act_out_ptr, record_ptr=None, stream=None):
+        """t2d_pid_actions: one launch; float32 [n, 2] (steering, accel) rows from act_in_ptr (None: zeros) to act_out_ptr (may
+        be the same memory), records to record_ptr (None: the pool's own, pid_records())."""
+        self._ck(self._lib.t2d_pid_actions(self._h, act_in_ptr, act_out_ptr, record_ptr, stream))
+
+    def pid_reset(self, mask_ptr=None, stream=None):
+        """t2d_pid_reset: controller.reset() for the envs whose byte at mask_ptr (device memory) is non-zero; None: all"""
+        self._ck(self._lib.t2d_pid_reset(self._h, mask_ptr, stream))
+
+    def pid_state(self, state=None):
+        """t2d_pid_state: the controllers' state float64 [n, 6] (lat integral, prev_error, prev_derivative, then the longitudinal
+        three).  state None: read (after the pool's work); else: replace it."""
+        if state is None:
+            out = np.empty((self.n, L.PID_STATE_WORDS), np.float64)
+            self._ck(self._lib.t2d_pid_state(self._h, _p(out), 0))
+            return out
+        st = _arr(state, np.float64, self.n * L.PID_STATE_WORDS, "state")
+        self._ck(self._lib.t2d_pid_state(self._h, _p(st), 1))
+
+    def pid_records(self, ptr=None, owner=None):
+        """Zero-copy torch views of t2d_pid_record [n] at `ptr` (None: the pool's own records): cross_track, lat_error float64
+        [n]; segment, leader, events int32 [n]; action float64 [n, 2] (NaN: the caller's row went through)."""
+        import torch
+        if ptr is None:
+            p_, nb = C.c_void_p(), C.c_size_t()
+            self._ck(self._lib.t2d_pid_buffers(self._h, C.byref(p_), C.byref(nb)))
+            ptr = p_.value
+        dev, n = f"cuda:{self.device_id}", self.n
+        keep = owner if owner is not None else self
+        i32 = torch.as_tensor(_DevArray(ptr, (n, L.PID_RECORD_BYTES // 4), "<i4", keep), device=dev)
+        f64 = torch.as_tensor(_DevArray(ptr, (n, L.PID_RECORD_BYTES // 8), "<f8", keep), device=dev)
+        return dict(cross_track=f64[:, 0], lat_error=f64[:, 1], segment=i32[:, 4], leader=i32[:, 5], events=i32[:, 6],
+                    action=f64[:, 4:6])
+
     def verify_state_ptr(self, x_ptr, y_ptr, heading_ptr, speed_ptr, interval_ms, valid_ptr, stream=None):
         """verify_state of device-resident candidate columns against the pool's current state."""
         self._ck(self._lib.t2d_verify_state(self._h, x_ptr, y_ptr, heading_ptr, speed_ptr, int(interval_ms),
