@@ -1078,7 +1078,8 @@ int t2d_rs_follow_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
  *                    min_accel, alpha <= 0 or > 1 are refused; lat_mode in 0..2, lon_mode in 0..3).  wheel_base NaN = lf + lr of
  *                    the participant's type row.  ctrl_id u8[N] (T2D_PID_NONE: uncontrolled), target_speed f32[N] (NULL: zeros),
  *                    idm_row i32[N] (NULL: row 0; read under lon_mode 2 only).  T2D_ERR_INVALID for a participant that is IDM-
- *                    controlled as well (t2d_set_idm refuses the same afterwards) and for an idm_row outside the installed rows;
+ *                    controlled as well (t2d_set_idm refuses the same afterwards), for one that is pursuit-controlled
+ *                    (t2d_set_pursuit; t2d_set_idm refuses that too) and for an idm_row outside the installed rows;
  *                    T2D_ERR_STATE for lon_mode 2 without installed IDM rows.  A refused call changes nothing.  Clears the state
  *                    of every participant.  n_ctrl = 0 uninstalls.
  *   t2d_pid_actions  one launch, asynchronous on hip_stream.  act_in_dev / act_out_dev: f32 [N][2] rows (steering, accel), may be
@@ -1141,6 +1142,109 @@ int t2d_pid_actions(t2d_pool* pool, const float* act_in_dev, float* act_out_dev,
 int t2d_pid_reset(t2d_pool* pool, const uint8_t* env_mask_dev, void* hip_stream);
 int t2d_pid_state(t2d_pool* pool, double* state_host, int32_t write);
 int t2d_pid_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
+
+/* Path-following scripted traffic: the reference's PurePursuitController (controller/pure_pursuit_controller.py:16-98) and
+ * AccelerationController (controller/acceleration_controller.py:14-145; cruise and adaptive cruise, ACC) for every controlled
+ * participant of every env in ONE launch in front of the step launch.  Both are stateless: there is no _reset, no _state and no
+ * episode-end rule.  The rows written reach the step through t2d_bind_actions_strided, as t2d_pid_actions' do; no stepping
+ * call launches the kernel; a participant has ONE of the IDM, PID and pursuit controllers.
+ *
+ * The law (the reference's, operation by operation in fp64; one rounding per operation; np.clip = two selects):
+ *   cruise   :73-93    accel = (target_speed - speed) / kp   -- it DIVIDES by kp --;  accel = clip(accel, accel_last -
+ *       accel_change_rate * delta_t, accel_last + accel_change_rate * delta_t); accel = clip(accel, min_accel, max_accel).
+ *       accel_last = ego_state.accel = T2D_F_APPLIED0 of the participant, which is 0.0 after a reset (the reference's State
+ *       holds None there and its arithmetic raises).
+ *       NOT the reference's State.accel property as it stands: that returns the NORM of the acceleration vector (accel *
+ *       cos(heading), accel * sin(heading)) and is never negative, although both laws clip around it and down to min_accel < 0.
+ *       Here accel_last and front.accel are the signed scalars the pool stores, and the fixture that pins the laws
+ *       (tests/golden/make_pursuit.py) overrides that one property to hand the signed scalar out.
+ *   ACC      :95-124   distance_front = hypot(dx, dy) to the leader; distance_target = clip(speed * interval + 5.0, 7.0, 80.0);
+ *       relative_target_speed = (distance_target - distance_front) / kp; relative_accel = (relative_target_speed -
+ *       (v_front - v)) / kp; accel = front.accel - relative_accel; then the same two clips.  front.accel / front.speed =
+ *       T2D_F_APPLIED0 / T2D_F_SPEED of the leader; the leader is the one t2d_idm_actions' rule finds with this row's
+ *       LANE_HALF_WIDTH and HORIZON (no IDM rows needed).  No leader: cruise, with T2D_PURSUIT_NO_LEADER.
+ *       (speed_factor is set by update_driving_style and never read by the reference; it has no column.)
+ *   pure pursuit  :53-98   pre_aiming_distance = max(speed * interval, min_pre_aiming_distance); pre_aiming_point = the
+ *       waypoints interpolated at that distance; angle = atan2(dy, dx) to it, distance = sqrt(dy * dy + dx * dx);
+ *       steering = atan(2.0 * wheel_base * sin(angle - heading) / distance).  No steering clip.
+ *   sin, atan2 and atan are the library's own deterministic functions, hypot is sqrt(dx * dx + dy * dy).
+ *
+ * The waypoints (BUILD-DEFINED; tests/pursuit_ref.py restates them in numpy).  The reference interpolates from the START of
+ * whatever line string its caller hands over (its source carries a "TODO: set an automatic reference point catcher").  Here
+ * the line string is the rest of the participant's route from its projection onward.  Position = the participant's centre.
+ * The projection is t2d_pid_actions' measurement exactly (same segment arithmetic, first strict minimum, zero-length segments
+ * skipped; the record's cross-track error has the PID record's bits).  On the winning segment A -> B, u = B - A, w = P - A,
+ * t = w.u clamped to [0, L2]: the start point is Q = A + u * (tc / L2).  The walk then covers rem = pre_aiming_distance
+ * forward: per segment, v = (the segment's end) - cur, L = sqrt(vx * vx + vy * vy); if rem <= L and L > 0 the target is
+ * cur + v * (rem / L); otherwise rem -= L, cur = the segment's end, and the walk goes on.  An open route that ends first gives
+ * its last vertex (what shapely's interpolate gives beyond the length) with T2D_PURSUIT_ROUTE_END.  A route whose first and
+ * last vertices are equal bit for bit is CLOSED: the walk continues from its first segment (T2D_PURSUIT_WRAPPED once it visits
+ * one) and visits at most as many segments as the route has, the winning one first: a look-ahead longer than that ends at the
+ * winning segment's start vertex with T2D_PURSUIT_ROUTE_END.  route_of = -1, or a route of zero-length segments only, is NO
+ * ROUTE: steering 0.0 with T2D_PURSUIT_NO_ROUTE.
+ *
+ * Non-finite values.  A non-finite x, y, heading, speed or stored accel, or a non-finite target_speed under lon_mode 0 / 1,
+ * passes the caller's row through bit for bit with T2D_PURSUIT_NONFINITE; so does a non-finite resulting steering or
+ * acceleration (a look-ahead point that coincides with the position while the heading equals the bearing gives 0 / 0; kp = 0
+ * is not refused, as the reference does not refuse it, and the IEEE result decides).  +-inf that the clips or atan make finite
+ * is kept.  Inactive or uncontrolled participants: the caller's row, bit for bit.
+ *
+ *   t2d_set_pursuit      ctrl_rows: host [n_ctrl][row_stride >= T2D_PURSUIT_COLS] fp64, 1 <= n_ctrl <= 254; refused
+ *                        (T2D_ERR_INVALID): min_pre_aiming <= 0 (the constructor's refusal), a non-finite column (wheel_base
+ *                        may be NaN = lf + lr of the participant's type row, horizon may be +inf), lat_mode outside 0..1,
+ *                        lon_mode outside 0..2, a negative or NaN target_speed of a controlled participant (the constructor's
+ *                        refusal; +inf passes and is a non-finite input of the call), a ctrl_id without a row, a participant
+ *                        that is IDM- or PID-controlled (t2d_set_idm and t2d_set_pid refuse the same afterwards).  ctrl_id
+ *                        u8[N] (T2D_PURSUIT_NONE: uncontrolled), target_speed f32[N] (NULL: zeros).  A refused call changes
+ *                        nothing.  n_ctrl = 0 uninstalls and frees the installation's device memory, the pool's own
+ *                        records included.
+ *   t2d_pursuit_actions  one launch, asynchronous on hip_stream.  act_in_dev / act_out_dev: f32 [N][2] rows (steering, accel),
+ *                        may be the same memory; act_in_dev is never written, NULL = zeros.  Controlled rows receive the fp32
+ *                        rounding of the fp64 action.  record_dev: t2d_pursuit_record [N] (8-byte aligned) or NULL = the
+ *                        pool's own.  T2D_ERR_STATE before t2d_set_pursuit or t2d_reset, when a row has lat_mode 1 and no
+ *                        route set is installed, when trace routes are the installed kind, and when a row has lon_mode 0 / 1
+ *                        while t2d_set_outputs has switched T2D_OUT_APPLIED off (accel_last would be stale);
+ *                        T2D_ERR_INVALID without act_out_dev.  kernel_id T2D_PROFILE_PURSUIT in t2d_profile_read.
+ *   t2d_pursuit_buffers  pointer and size in bytes of the pool's own records.                                                */
+enum {
+    T2D_PURSUIT_MIN_PRE_AIMING = 0,    /* PurePursuitController.min_pre_aiming_distance */
+    T2D_PURSUIT_INTERVAL_LAT = 1,      /* PurePursuitController.interval */
+    T2D_PURSUIT_KP = 2,                /* AccelerationController.kp (a divisor) */
+    T2D_PURSUIT_ACCEL_CHANGE_RATE = 3,
+    T2D_PURSUIT_MAX_ACCEL = 4,
+    T2D_PURSUIT_MIN_ACCEL = 5,
+    T2D_PURSUIT_INTERVAL_LON = 6,      /* AccelerationController.interval */
+    T2D_PURSUIT_DELTA_T = 7,
+    T2D_PURSUIT_LAT_MODE = 8,          /* build column: 0 steering 0.0 (AccelerationController.step), 1 pure pursuit */
+    T2D_PURSUIT_LON_MODE = 9,          /* build column: 0 cruise, 1 ACC behind the leader (cruise without one), 2 caller's accel */
+    T2D_PURSUIT_WHEEL_BASE = 10,       /* build column: the wheel_base argument; NaN = lf + lr of the type row */
+    T2D_PURSUIT_LANE_HALF_WIDTH = 11,  /* build columns: the leader rule's corridor and horizon (t2d_set_idm's) */
+    T2D_PURSUIT_HORIZON = 12,
+    T2D_PURSUIT_COLS = 13
+};
+#define T2D_PURSUIT_NONE 255
+#define T2D_PURSUIT_ROUTE_END 1u   /* the walk ran out of route: the target is where it stopped */
+#define T2D_PURSUIT_NONFINITE 2u   /* non-finite input or result: the caller's row passed through */
+#define T2D_PURSUIT_WRAPPED 4u     /* the walk went over the seam of a closed route */
+#define T2D_PURSUIT_NO_ROUTE 8u    /* lat_mode 1 without a route: steering 0.0 */
+#define T2D_PURSUIT_NO_LEADER 16u  /* lon_mode 1 without a leader: cruise */
+#define T2D_PROFILE_PURSUIT 16
+typedef struct t2d_pursuit_record { /* 72 bytes */
+    double point[2];                /* the look-ahead point (x, y), NaN without a walk */
+    double pre_aiming_distance;     /* max(speed * interval, min_pre_aiming_distance), NaN when lat_mode 1 did not run */
+    double distance;                /* from the position to the look-ahead point, NaN without a walk */
+    double cross_track;             /* signed cross-track error of the projection (the PID record's bits), NaN without one */
+    int32_t segment;                /* the projection's segment within the route, -1 without one */
+    int32_t target_segment;         /* the segment the look-ahead point lies on, -1 without a walk */
+    int32_t leader;                 /* lon_mode 1: agent index of the chosen leader, else -1 */
+    uint32_t events;                /* T2D_PURSUIT_* of this call */
+    double action[2];               /* the applied (steering, accel) in fp64, NaN when the caller's row went through */
+} t2d_pursuit_record;
+int t2d_set_pursuit(t2d_pool* pool, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
+                    const float* target_speed);
+int t2d_pursuit_actions(t2d_pool* pool, const float* act_in_dev, float* act_out_dev, t2d_pursuit_record* record_dev,
+                        void* hip_stream);
+int t2d_pursuit_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
 
 /* BEV camera -- the top-down semantic image both reference envs declare as their observation (Box(0, 255, (200, 200, 3),
  * uint8), envs/racing.py:102, envs/parking.py:130), for every env in ONE launch behind the step launch.
@@ -1294,7 +1398,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
  * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
- * 15 = lane-keeping PID controllers (t2d_pid_actions).  */
+ * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -108,6 +108,9 @@ SYMBOLS = {
     "t2d_pid_reset": (C.c_int, [_vp, _vp, _vp]),
     "t2d_pid_state": (C.c_int, [_vp, _vp, C.c_int32]),
     "t2d_pid_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "t2d_set_pursuit": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "t2d_pursuit_actions": (C.c_int, [_vp] * 5),
+    "t2d_pursuit_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "t2d_verify_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "t2d_traj_create": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp)]),
     "t2d_traj_destroy": (C.c_int, [_vp]),

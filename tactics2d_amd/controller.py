@@ -1,4 +1,4 @@
-"""Host-side mirrors of the reference's IDM and PID controllers for the batched device path (scope row f3).
+"""Host-side mirrors of the reference's IDM, PID, pure-pursuit and acceleration controllers for the batched device path (scope row f3).
 
 Reference: `tactics2d.controller.IDMController` (controller/idm_controller.py:15-157): same
 constructor arguments and defaults, `configure(**kwargs)` with the same AttributeError, and `step`
@@ -315,3 +315,240 @@ class LaneKeeper:
                 raise ValueError(f"mask must have {self.pool.n_env} elements")
             self._mask = mask   # (kept alive until the launch has run)
         self.pool.pid_reset(None if mask is None else mask.data_ptr(), st.cuda_stream)
+
+
+# ---------------------------------------------------------------------------------------------------- pure pursuit, cruise / ACC
+_PURSUIT_LON = {"cruise": L.PURSUIT_LON_CRUISE, "acc": L.PURSUIT_LON_ACC, "caller": L.PURSUIT_LON_CALLER}
+# update_driving_style: parameter -> (value at style -1, value at style +1), acceleration_controller.py:50-55
+_ACCEL_STYLE = {"kp": (4.5, 2.5), "speed_factor": (0.8, 1.2), "accel_change_rate": (3.0, 6.0), "max_accel": (1.5, 2.5),
+                "min_accel": (-3.0, -5.0), "interval": (3.5, 1.5)}
+
+
+def _style_value(style_id, left, right):
+    """the reference's style interpolator (controller_base.py:69-91): linear between style -1 and +1, the end values beyond"""
+    s, left, right = np.float64(style_id), np.float64(left), np.float64(right)
+    if s < -1.0:
+        return float(left)
+    if s > 1.0:
+        return float(right)
+    return float((right - left) / np.float64(2.0) * (s - np.float64(-1.0)) + left)   # (the order of scipy's linear interp1d)
+
+
+def _configure(obj, kwargs):
+    """ControllerBase.configure (controller_base.py:52-67)"""
+    for key, value in kwargs.items():
+        if hasattr(obj, key):
+            setattr(obj, key, value)
+        else:
+            raise AttributeError(f"Controller {type(obj).__name__} has no parameter '{key}'")
+
+
+def interpolate(line, distance):
+    """The point `distance` along a polyline from its START, float64 (x, y): what `LineString.interpolate` is asked for by the
+    reference (pure_pursuit_controller.py:94), computed as the device's walk computes it (include/t2d.h) -- per segment
+    L = sqrt(vx * vx + vy * vy), the target is cur + v * (distance_left / L) on the first segment with distance_left <= L and
+    L > 0, the last vertex beyond the line's end.  `line`: anything traffic.as_polyline accepts."""
+    from .traffic import as_polyline
+    pts = as_polyline(line).astype(np.float64)
+    rem = np.float64(distance)
+    cur = pts[0]
+    with np.errstate(all="ignore"):
+        for k in range(1, len(pts)):
+            v = pts[k] - cur
+            seg = np.sqrt(v[0] * v[0] + v[1] * v[1])
+            if rem <= seg and seg > 0.0:
+                return cur + v * (rem / seg)
+            rem = rem - seg
+            cur = pts[k]
+    return cur
+
+
+class AccelerationController:
+    """`tactics2d.controller.AccelerationController` (controller/acceleration_controller.py:14-145): the same constructor,
+    attributes, class defaults and refusals, `update_driving_style`, `configure` and `step` (cruise, or adaptive cruise behind
+    `front_state`); `step` evaluates the law in numpy on the host.  One object is one parameter set of the device path (`row()`,
+    `install_pursuit`).  `lane_half_width` and `horizon` are the build's leader rule for longitudinal="acc" (t2d_set_idm's)."""
+    kp = 3.5
+    speed_factor = 1.0   # set by update_driving_style and never read, as in the reference
+    accel_change_rate = 3.0
+    max_accel = 1.5
+    min_accel = -4.0
+    interval = 2.0
+    delta_t = 0.05
+    lane_half_width = 1.875
+    horizon = np.inf
+    DEFAULT_SAFETY_DISTANCE = 5.0
+    MIN_TARGET_DISTANCE = 7.0
+    MAX_TARGET_DISTANCE = 80.0
+
+    def __init__(self, target_speed=5.0):
+        if target_speed < 0:
+            raise ValueError("target_speed must be non-negative")
+        self.target_speed = target_speed
+
+    def update_driving_style(self, style_id):
+        if not isinstance(style_id, (int, float)):
+            raise TypeError("style_id must be int or float")
+        for name, (left, right) in _ACCEL_STYLE.items():
+            setattr(self, name, _style_value(style_id, left, right))
+
+    def configure(self, **kwargs):
+        _configure(self, kwargs)
+
+    def _clips(self, accel, accel_last):
+        f = np.float64
+        step = f(self.accel_change_rate) * f(self.delta_t)
+        accel = np.clip(accel, f(accel_last) - step, f(accel_last) + step)
+        return np.clip(accel, f(self.min_accel), f(self.max_accel))
+
+    def _cruise_control(self, ego_state):
+        f = np.float64
+        with np.errstate(all="ignore"):
+            return self._clips((f(self.target_speed) - f(ego_state.speed)) / f(self.kp), ego_state.accel)
+
+    def _adaptive_cruise_control(self, ego_state, front_state):
+        f = np.float64
+        with np.errstate(all="ignore"):
+            distance_front = np.hypot(f(ego_state.x) - f(front_state.x), f(ego_state.y) - f(front_state.y))
+            distance_target = np.clip(f(ego_state.speed) * f(self.interval) + f(self.DEFAULT_SAFETY_DISTANCE),
+                                      f(self.MIN_TARGET_DISTANCE), f(self.MAX_TARGET_DISTANCE))
+            relative_speed = f(front_state.speed) - f(ego_state.speed)
+            relative_target_speed = (distance_target - distance_front) / f(self.kp)
+            relative_accel = (relative_target_speed - relative_speed) / f(self.kp)
+            return self._clips(f(front_state.accel) - relative_accel, ego_state.accel)
+
+    def step(self, ego_state, **kwargs):
+        """(0.0, acceleration): adaptive cruise behind kwargs["front_state"] when given, cruise otherwise (:126-145).  The
+        reference raises TypeError for a front_state that is no `State`; this package has no State class, so the refusal is for
+        whatever lacks a state's x, y, speed and accel."""
+        front_state = kwargs.get("front_state")
+        if front_state is not None:
+            if not all(hasattr(front_state, k) for k in ("x", "y", "speed", "accel")):
+                raise TypeError("front_state must be a state with x, y, speed and accel")
+            return 0.0, self._adaptive_cruise_control(ego_state, front_state)
+        return 0.0, self._cruise_control(ego_state)
+
+    def row(self, longitudinal="cruise"):
+        r = np.zeros(L.PURSUIT_COLS)
+        r[L.PURSUIT_MIN_PRE_AIMING], r[L.PURSUIT_INTERVAL_LAT] = 10.0, 1.0   # (unread with lat_mode 0)
+        self._fill(r, longitudinal)
+        r[L.PURSUIT_WHEEL_BASE] = np.nan
+        return r
+
+    def _fill(self, r, longitudinal):
+        if longitudinal not in _PURSUIT_LON:
+            raise ValueError(f"longitudinal: one of {sorted(_PURSUIT_LON)}")
+        for col, name in ((L.PURSUIT_KP, "kp"), (L.PURSUIT_ACCEL_CHANGE_RATE, "accel_change_rate"), (L.PURSUIT_MAX_ACCEL, "max_accel"),
+                          (L.PURSUIT_MIN_ACCEL, "min_accel"), (L.PURSUIT_INTERVAL_LON, "interval"), (L.PURSUIT_DELTA_T, "delta_t"),
+                          (L.PURSUIT_LANE_HALF_WIDTH, "lane_half_width"), (L.PURSUIT_HORIZON, "horizon")):
+            r[col] = float(getattr(self, name))
+        r[L.PURSUIT_LON_MODE] = _PURSUIT_LON[longitudinal]
+
+
+class PurePursuitController:
+    """`tactics2d.controller.PurePursuitController` (controller/pure_pursuit_controller.py:16-98): the same constructor, class
+    default, refusals, `update_driving_style` (forwarded to its longitudinal AccelerationController), `configure` and `step`.
+    The host `step` interpolates the look-ahead point from the START of `waypoints`, as the reference does (there is no shapely:
+    `interpolate` above); the device path walks from the participant's projection onto its installed route (include/t2d.h).
+    `wheel_base` (None: lf + lr of the participant's type) is the build column of the device row."""
+    interval = 1.0
+    wheel_base = None
+
+    def __init__(self, min_pre_aiming_distance=10.0, target_speed=5.0):
+        if min_pre_aiming_distance <= 0:
+            raise ValueError("min_pre_aiming_distance must be positive")
+        if target_speed < 0:
+            raise ValueError("target_speed must be non-negative")
+        self.min_pre_aiming_distance = min_pre_aiming_distance
+        self._longitudinal_control = AccelerationController(target_speed)
+
+    @property
+    def target_speed(self):
+        return self._longitudinal_control.target_speed
+
+    def update_driving_style(self, style_id):
+        if not isinstance(style_id, (int, float)):
+            raise TypeError("style_id must be int or float")
+        self._longitudinal_control.update_driving_style(style_id)
+        self.interval = _style_value(style_id, 2.0, 1.0)
+
+    def configure(self, **kwargs):
+        _configure(self, kwargs)
+
+    def _lateral_control(self, ego_state, pre_aiming_point, wheel_base):
+        """pre_aiming_point: (x, y) or an object with .x / .y"""
+        f = np.float64
+        px, py = (pre_aiming_point.x, pre_aiming_point.y) if hasattr(pre_aiming_point, "x") else pre_aiming_point
+        with np.errstate(all="ignore"):
+            dy, dx = f(py) - f(ego_state.y), f(px) - f(ego_state.x)
+            pre_aiming_angle = np.arctan2(dy, dx)
+            distance = np.linalg.norm((dy, dx))
+            return np.arctan(f(2.0) * f(wheel_base) * np.sin(pre_aiming_angle - f(ego_state.heading)) / distance)
+
+    def pre_aiming_distance(self, speed):
+        return np.max([np.float64(speed) * np.float64(self.interval), np.float64(self.min_pre_aiming_distance)])
+
+    def step(self, ego_state, waypoints, wheel_base=2.637, front_state=None, **kwargs):
+        """(steering, acceleration) (:76-98); waypoints: anything traffic.as_polyline accepts; front_state (the one keyword the
+        reference's **kwargs carries on to the longitudinal controller): adaptive cruise behind it, TypeError if it is no state"""
+        point = interpolate(waypoints, self.pre_aiming_distance(ego_state.speed))
+        _, accel = self._longitudinal_control.step(ego_state, front_state=front_state, **kwargs)
+        return self._lateral_control(ego_state, point, wheel_base), accel
+
+    def row(self, longitudinal="cruise"):
+        r = np.zeros(L.PURSUIT_COLS)
+        r[L.PURSUIT_MIN_PRE_AIMING], r[L.PURSUIT_INTERVAL_LAT] = float(self.min_pre_aiming_distance), float(self.interval)
+        self._longitudinal_control._fill(r, longitudinal)
+        r[L.PURSUIT_LAT_MODE] = L.PURSUIT_LAT_PURE_PURSUIT
+        r[L.PURSUIT_WHEEL_BASE] = np.nan if self.wheel_base is None else float(self.wheel_base)
+        return r
+
+
+def install_pursuit(pool, controllers, ctrl_id, target_speed=None, longitudinal="cruise"):
+    """controllers: sequence of PurePursuitController / AccelerationController; ctrl_id[n]: index into it or layout.PURSUIT_NONE;
+    target_speed[n] (a scalar broadcasts; None: each controller's own target_speed); longitudinal: "cruise", "acc" (adaptive
+    cruise behind the leader of t2d_idm_actions' rule, cruise without one) or "caller" (the acceleration of the caller's row).
+    An empty sequence uninstalls."""
+    if not len(controllers):
+        pool.set_pursuit(None)
+        return
+    rows = np.stack([c.row(longitudinal) for c in controllers])
+    cid = np.asarray(ctrl_id, np.uint8).reshape(-1)
+    if target_speed is None:
+        own = np.float32([c.target_speed for c in controllers] + [0.0])
+        target_speed = own[np.where(cid == L.PURSUIT_NONE, len(controllers), np.minimum(cid, len(controllers)))]
+    pool.set_pursuit(rows, cid, target_speed)
+
+
+PURSUIT_EVENTS = ("route_end", "nonfinite", "wrapped", "no_route", "no_leader")   # bit k: layout.PURSUIT_*
+
+
+class PathFollower:
+    """The controllers installed on `pool` (install_pursuit) in a step_torch-style loop: LaneKeeper's contract without reset()
+    -- the controllers hold no state.  follow() writes the action rows to step with -- bind them with
+    pool.bind_actions(rows + 4 bytes, rows, stride=2) -- and returns zero-copy torch views of the records
+    (ParticipantPool.pursuit_records) beside them."""
+
+    def __init__(self, pool):
+        self.pool = pool
+        self._rec = self._views = self._act = None
+
+    def follow(self, actions=None, out=None, stream=None):
+        """actions: float32 CUDA tensor [n, 2] (steering, accel), the rows of whoever else acts (None: zeros), never written
+        unless it is also `out`; out: float32 [n, 2] tensor for the rows to step (None: a buffer of the follower's own).
+        Asynchronous on `stream`.  Returns dict(action_rows, point, pre_aiming_distance, distance, cross_track, segment,
+        target_segment, leader, events, action), valid until the next follow()."""
+        import torch
+        pool = self.pool
+        dev = torch.device("cuda", pool.device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        for t in (actions, out):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n, 2) or not t.is_contiguous()):
+                raise ValueError(f"action rows must be a contiguous float32 [{pool.n}, 2] tensor")
+        if self._rec is None:
+            self._rec = torch.zeros((pool.n, L.PURSUIT_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
+            self._views = pool.pursuit_records(self._rec.data_ptr(), owner=self._rec)
+            self._act = torch.zeros((pool.n, 2), dtype=torch.float32, device=dev)
+        rows = self._act if out is None else out
+        pool.pursuit_actions(None if actions is None else actions.data_ptr(), rows.data_ptr(), self._rec.data_ptr(), st.cuda_stream)
+        return dict(self._views, action_rows=rows)

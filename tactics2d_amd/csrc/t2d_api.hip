@@ -2400,6 +2400,10 @@ int t2d_set_idm(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t ro
         for (int i = 0; i < p->v.N; ++i)
             if (ctrl_id[i] != T2D_IDM_NONE && p->pid_ctrl_host[i] != T2D_PID_NONE)
                 return fail(p, T2D_ERR_INVALID, "t2d_set_idm: participant " + std::to_string(i) + " is PID-controlled (t2d_set_pid)");
+    if (p->pursuit_on)   // (nor a pursuit-controlled one: t2d_set_pursuit)
+        for (int i = 0; i < p->v.N; ++i)
+            if (ctrl_id[i] != T2D_IDM_NONE && p->pursuit_ctrl_host[i] != T2D_PURSUIT_NONE)
+                return fail(p, T2D_ERR_INVALID, "t2d_set_idm: participant " + std::to_string(i) + " is pursuit-controlled (t2d_set_pursuit)");
     int rc;
     if ((rc = dev_replace(p, &p->d_idm_rows, rows.data(), rows.size()))) return rc;
     if ((rc = dev_replace(p, &p->d_idm_ctrl, ctrl_id, (size_t)p->v.N))) return rc;
@@ -2476,6 +2480,8 @@ int t2d_set_pid(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t ro
                                                 " out of range");
         if (p->idm_on && idm_ctrl[i] != T2D_IDM_NONE)
             return fail(p, T2D_ERR_INVALID, "t2d_set_pid: participant " + std::to_string(i) + " is IDM-controlled (t2d_set_idm)");
+        if (p->pursuit_on && p->pursuit_ctrl_host[i] != T2D_PURSUIT_NONE)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: participant " + std::to_string(i) + " is pursuit-controlled (t2d_set_pursuit)");
         if (lon_of[ctrl_id[i]] == 2) {
             if (!p->idm_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid: lon_mode 2 needs the parameter sets of t2d_set_idm");
             irow[i] = idm_row ? idm_row[i] : 0;
@@ -2578,6 +2584,130 @@ int t2d_pid_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
     if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_buffers");
     *records_dev = p->d_pid_rec;
     *nbytes = (size_t)p->v.N * sizeof(t2d_pid_record);
+    return T2D_OK;
+}
+
+// ---- pure pursuit and cruise / ACC controllers (kernel: t2d_pursuit.hip) ---------------------------------------------------
+int t2d_set_pursuit(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
+                    const float* target_speed) {
+    if (!p) return T2D_ERR_INVALID;
+    T2D_HIP(p, hipSetDevice(p->device));
+    if (n_ctrl == 0) {
+        T2D_HIP(p, quiesce(p));
+        p->pursuit_on = false;
+        p->pursuit = t2d::PursuitView{};
+        p->pursuit_ctrl_host.clear();
+        // (quiesced above: nothing in flight reads them any more)
+        T2D_HIP(p, p->d_pursuit_rows.reset());
+        T2D_HIP(p, p->d_pursuit_ctrl.reset());
+        T2D_HIP(p, p->d_pursuit_target.reset());
+        T2D_HIP(p, p->d_pursuit_rec.reset());
+        p->pursuit_any_lat = p->pursuit_any_last = false;
+        return T2D_OK;
+    }
+    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= T2D_PURSUIT_NONE || row_stride < T2D_PURSUIT_COLS)
+        return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: need 1..254 parameter sets of >= 13 columns and a controller id per participant");
+    const int N = p->v.N;
+    std::vector<double> rows((size_t)n_ctrl * T2D_PURSUIT_COLS);
+    bool any_lat = false, any_acc = false, any_last = false;
+    std::vector<int> lon_of(n_ctrl);
+    for (int c = 0; c < n_ctrl; ++c) {
+        const double* r = ctrl_rows + (size_t)c * row_stride;
+        const std::string row = " (row " + std::to_string(c) + ")";
+        for (int k = 0; k < T2D_PURSUIT_COLS; ++k) {
+            rows[(size_t)c * T2D_PURSUIT_COLS + k] = r[k];
+            const bool may = (k == T2D_PURSUIT_WHEEL_BASE && r[k] != r[k]) || (k == T2D_PURSUIT_HORIZON && r[k] == HUGE_VAL);
+            if (!std::isfinite(r[k]) && !may)
+                return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: column " + std::to_string(k) + " is not finite" + row);
+        }
+        // pure_pursuit_controller.py:31-32
+        if (r[T2D_PURSUIT_MIN_PRE_AIMING] <= 0)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: min_pre_aiming_distance must be positive" + row);
+        const double lat = r[T2D_PURSUIT_LAT_MODE], lon = r[T2D_PURSUIT_LON_MODE];
+        if (!(lat == 0.0 || lat == 1.0) || !(lon == 0.0 || lon == 1.0 || lon == 2.0))
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: lat_mode must be 0 or 1 and lon_mode 0, 1 or 2" + row);
+        lon_of[c] = (int)lon;
+        any_lat = any_lat || lat == 1.0;
+        any_acc = any_acc || lon == 1.0;
+        any_last = any_last || lon != 2.0;
+    }
+    T2D_HIP(p, quiesce(p));
+    std::vector<uint8_t> idm_ctrl;
+    if (p->idm_on) {
+        idm_ctrl.resize(N);
+        T2D_HIP(p, hipMemcpy(idm_ctrl.data(), p->d_idm_ctrl, (size_t)N, hipMemcpyDeviceToHost));
+    }
+    std::vector<float> ts(N, 0.f);
+    for (int i = 0; i < N; ++i) {
+        if (target_speed) ts[i] = target_speed[i];
+        if (ctrl_id[i] == T2D_PURSUIT_NONE) continue;
+        if (ctrl_id[i] >= n_ctrl)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: ctrl_id[" + std::to_string(i) + "] = " +
+                                                std::to_string((int)ctrl_id[i]) + " out of range");
+        // acceleration_controller.py:46-47 (the caller's acceleration needs no target speed)
+        if (lon_of[ctrl_id[i]] != 2 && !(ts[i] >= 0))
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: target_speed[" + std::to_string(i) + "] must be non-negative");
+        if (p->idm_on && idm_ctrl[i] != T2D_IDM_NONE)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: participant " + std::to_string(i) + " is IDM-controlled (t2d_set_idm)");
+        if (p->pid_on && p->pid_ctrl_host[i] != T2D_PID_NONE)
+            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: participant " + std::to_string(i) + " is PID-controlled (t2d_set_pid)");
+    }
+    // everything new first, the installed controllers go only when nothing can fail any more
+    t2d::DevBuf<double> d_rows;
+    t2d::DevBuf<uint8_t> d_ctrl;
+    t2d::DevBuf<float> d_ts;
+    t2d::DevBuf<t2d_pursuit_record> d_rec;
+    int rc;
+    if ((rc = dev_replace(p, &d_rows, rows.data(), rows.size()))) return rc;
+    if ((rc = dev_replace(p, &d_ctrl, ctrl_id, (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &d_ts, ts.data(), (size_t)N))) return rc;
+    T2D_HIP(p, d_rec.alloc_zeroed((size_t)N));
+    p->d_pursuit_rows = std::move(d_rows);
+    p->d_pursuit_ctrl = std::move(d_ctrl);
+    p->d_pursuit_target = std::move(d_ts);
+    p->d_pursuit_rec = std::move(d_rec);
+    p->pursuit_ctrl_host.assign(ctrl_id, ctrl_id + N);
+    p->pursuit_any_lat = any_lat;
+    p->pursuit_any_last = any_last;
+    t2d::PursuitView& cv = p->pursuit;
+    cv = t2d::PursuitView{};
+    cv.rows = p->d_pursuit_rows;
+    cv.ctrl_id = p->d_pursuit_ctrl;
+    cv.target_speed = p->d_pursuit_target;
+    cv.n_ctrl = n_ctrl;
+    cv.stage_xy = any_acc;
+    p->pursuit_on = true;
+    return T2D_OK;
+}
+
+int t2d_pursuit_actions(t2d_pool* p, const float* act_in_dev, float* act_out_dev, t2d_pursuit_record* record_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!p->pursuit_on) return fail(p, T2D_ERR_STATE, "t2d_set_pursuit must precede t2d_pursuit_actions");
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_pursuit_actions");
+    if (p->route.kind == 2)
+        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions follows route sets (t2d_set_routes); trace routes are the installed kind");
+    if (p->pursuit_any_lat && p->route.kind != 1)
+        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions: a row has lat_mode 1 and no route set is installed (t2d_set_routes)");
+    if (p->pursuit_any_last && !(p->v.out_mask & T2D_OUT_APPLIED))
+        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions: cruise / ACC read T2D_F_APPLIED0, which t2d_set_outputs switched off");
+    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, "t2d_pursuit_actions: act_out_dev is required");
+    if (reinterpret_cast<uintptr_t>(record_dev) & 7u)
+        return fail(p, T2D_ERR_INVALID, "t2d_pursuit_actions: record_dev must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc;
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_PURSUIT, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_pursuit(p->v, p->pursuit, p->route, act_in_dev, act_out_dev,
+                                   record_dev ? record_dev : p->d_pursuit_rec.get(), s));
+    return record_event(p, T2D_PROFILE_PURSUIT, s, false);
+}
+
+int t2d_pursuit_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!p->pursuit_on) return fail(p, T2D_ERR_STATE, "t2d_set_pursuit must precede t2d_pursuit_buffers");
+    *records_dev = p->d_pursuit_rec;
+    *nbytes = (size_t)p->v.N * sizeof(t2d_pursuit_record);
     return T2D_OK;
 }
 

@@ -137,41 +137,10 @@ __global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv,
             double cte = 0.0, th = 0.0;
             const int ro = (lat_mode != 0 && rv.kind == 1) ? rv.route_of[i] : -1;
             if (ro >= 0) {
-                int k = lo[ro];
-                const int k0 = k, k1 = lo[ro + 1];
-                float2 A = lv[k];
-                double d2min = __builtin_inf(), wc = 0.0, wux = 0.0, wuy = 0.0;
-                int seg = -1, last_seg = -1;
-                bool wend = false;
-                for (++k; k < k1; ++k) {
-                    const float2 B = lv[k];
-                    // route_seg_d2's operations, with t, L2 and c kept
-                    const double ux = (double)B.x - (double)A.x, uy = (double)B.y - (double)A.y;
-                    const double wx = x - (double)A.x, wy = y - (double)A.y;
-                    A = B;
-                    if (ux == 0.0 && uy == 0.0) continue;   // a zero-length segment is skipped
-                    const double L2 = ux * ux + uy * uy;
-                    const double t = wx * ux + wy * uy;
-                    const double cr = wx * uy - wy * ux;
-                    double d2;
-                    if (t <= 0.0) {
-                        d2 = wx * wx + wy * wy;
-                    } else if (t >= L2) {
-                        const double vx = x - (double)B.x, vy = y - (double)B.y;
-                        d2 = vx * vx + vy * vy;
-                    } else {
-                        d2 = (cr * cr) / L2;
-                    }
-                    last_seg = k - 1 - k0;
-                    if (d2 < d2min) {
-                        d2min = d2;
-                        seg = last_seg;
-                        wc = cr;
-                        wux = ux;
-                        wuy = uy;
-                        wend = t >= L2;
-                    }
-                }
+                const RouteMeasure m = route_measure(lv, lo[ro], lo[ro + 1], x, y);
+                const double d2min = m.d2min, wc = m.c, wux = m.ux, wuy = m.uy;
+                const int seg = m.seg, last_seg = m.last_seg;
+                const bool wend = m.end;
                 if (seg >= 0) {
                     const double d = __builtin_sqrt(d2min);
                     cte = wc > 0.0 ? d : wc < 0.0 ? -d : 0.0;

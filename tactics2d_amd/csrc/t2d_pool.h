@@ -358,6 +358,15 @@ struct PidView {
     int32_t stage_xy;            // some row has lon_mode 2: the env's (x, y, speed) go through LDS for the leader rule
 };
 
+// Pure pursuit and cruise / ACC controllers (t2d_pursuit.hip): parameter sets and the per-participant assignment.  Stateless.
+struct PursuitView {
+    const double* rows;          // [n_ctrl][T2D_PURSUIT_COLS]
+    const uint8_t* ctrl_id;      // [N] index into rows, T2D_PURSUIT_NONE = the caller's row goes through
+    const float* target_speed;   // [N]
+    int32_t n_ctrl;
+    int32_t stage_xy;            // some row has lon_mode 1: the env's (x, y, speed, applied accel) go through LDS for the leader
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -560,6 +569,17 @@ struct t2d_pool {
     std::vector<uint8_t> pid_ctrl_host;
     bool pid_any_lat = false;        // some installed row has lat_mode != 0: a call needs route sets
     int pid_idm_rows_needed = 0;     // lon_mode 2: 1 + the largest idm_row in use (0: no such participant)
+    // pure pursuit and cruise / ACC controllers (t2d_set_pursuit): the view, what it borrows, the pool's own records and the
+    // host's copy of the assignment (t2d_set_idm / t2d_set_pid check new assignments against it)
+    bool pursuit_on = false;
+    t2d::PursuitView pursuit{};
+    t2d::DevBuf<double> d_pursuit_rows;
+    t2d::DevBuf<uint8_t> d_pursuit_ctrl;
+    t2d::DevBuf<float> d_pursuit_target;
+    t2d::DevBuf<t2d_pursuit_record> d_pursuit_rec;
+    std::vector<uint8_t> pursuit_ctrl_host;
+    bool pursuit_any_lat = false;    // some installed row has lat_mode 1: a call needs route sets
+    bool pursuit_any_last = false;   // some installed row has lon_mode 0 / 1: a call reads T2D_F_APPLIED0 (T2D_OUT_APPLIED)
     // profiling
     t2d::DevBuf<unsigned long long> d_dbg;   // what v.dbg borrows (-DT2D_TIMING builds)
     bool profiling = false;
@@ -613,6 +633,9 @@ hipError_t launch_rs_follow_reset(const PoolView& v, const RsFollowView& fv, con
 hipError_t launch_pid(const PoolView& v, const PidView& cv, const RouteView& rv, const float* act_in, float* act_out,
                       t2d_pid_record* out, hipStream_t s);
 hipError_t launch_pid_reset(const PoolView& v, const PidView& cv, const uint8_t* mask, hipStream_t s);
+// pure pursuit and cruise / ACC controllers (t2d_pursuit.hip): one action row and one record per participant
+hipError_t launch_pursuit(const PoolView& v, const PursuitView& cv, const RouteView& rv, const float* act_in, float* act_out,
+                          t2d_pursuit_record* out, hipStream_t s);
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s);
 hipError_t launch_restore(const PoolView& v, const float* const* snap, const uint32_t* snap_ids, int mode,

@@ -83,6 +83,18 @@ PID_NONE = 255
 PID_ROUTE_END, PID_NONFINITE, PID_RESET, PID_NO_ROUTE, PID_BAD_WHEEL_BASE, PID_SATURATED = 1, 2, 4, 8, 16, 32
 PID_RECORD_BYTES = 48
 PROFILE_PID = 15
+# pure pursuit and cruise / ACC controllers (t2d_set_pursuit / t2d_pursuit_actions): parameter-row columns, mode values, event
+# bits, the record's size in bytes, the kernel id
+PURSUIT_MIN_PRE_AIMING, PURSUIT_INTERVAL_LAT, PURSUIT_KP, PURSUIT_ACCEL_CHANGE_RATE, PURSUIT_MAX_ACCEL, PURSUIT_MIN_ACCEL = range(6)
+PURSUIT_INTERVAL_LON, PURSUIT_DELTA_T, PURSUIT_LAT_MODE, PURSUIT_LON_MODE, PURSUIT_WHEEL_BASE = range(6, 11)
+PURSUIT_LANE_HALF_WIDTH, PURSUIT_HORIZON = 11, 12
+PURSUIT_COLS = 13
+PURSUIT_LAT_NONE, PURSUIT_LAT_PURE_PURSUIT = 0, 1                      # values of the lat_mode column
+PURSUIT_LON_CRUISE, PURSUIT_LON_ACC, PURSUIT_LON_CALLER = 0, 1, 2      # values of the lon_mode column
+PURSUIT_NONE = 255
+PURSUIT_ROUTE_END, PURSUIT_NONFINITE, PURSUIT_WRAPPED, PURSUIT_NO_ROUTE, PURSUIT_NO_LEADER = 1, 2, 4, 8, 16
+PURSUIT_RECORD_BYTES = 72
+PROFILE_PURSUIT = 16
 # host-frame sections (t2d_frame_config)
 FRAME_LIDAR, FRAME_TARGET, FRAME_ZEROCOPY = 1, 2, 4
 # device-resident trajectories (t2d_traj_*): column order of a slot

@@ -366,6 +366,45 @@ class ParticipantPool:
         return dict(cross_track=f64[:, 0], lat_error=f64[:, 1], segment=i32[:, 4], leader=i32[:, 5], events=i32[:, 6],
                     action=f64[:, 4:6])
 
+    # ---------------------------------------------------------------- pure pursuit and cruise / ACC controllers
+    def set_pursuit(self, ctrl_rows, ctrl_id=None, target_speed=None):
+        """Install pure-pursuit / acceleration controllers (t2d_set_pursuit): ctrl_rows [n_ctrl, 13] (layout.PURSUIT_*;
+        controller.PurePursuitController.row() / AccelerationController.row()), ctrl_id uint8 [n] (PURSUIT_NONE = the caller's row
+        goes through), target_speed float32 [n] (a scalar broadcasts; None: zeros).  ctrl_rows=None uninstalls."""
+        if ctrl_rows is None:
+            self._ck(self._lib.t2d_set_pursuit(self._h, None, 0, 0, None, None))
+            return
+        rows = np.ascontiguousarray(ctrl_rows, np.float64)
+        if rows.ndim != 2:
+            raise ValueError("ctrl_rows must be 2-D [n_ctrl, >= 13]")
+        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
+        ts = None if target_speed is None else _arr(np.broadcast_to(np.asarray(target_speed, np.float32).reshape(-1)
+                                                    if np.ndim(target_speed) else np.float32(target_speed), (self.n,)),
+                                                    np.float32, self.n, "target_speed")
+        self._ck(self._lib.t2d_set_pursuit(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid), _p(ts)))
+
+    def pursuit_actions(self, act_in_ptr, act_out_ptr, record_ptr=None, stream=None):
+        """t2d_pursuit_actions: one launch; float32 [n, 2] (steering, accel) rows from act_in_ptr (None: zeros) to act_out_ptr
+        (may be the same memory), records to record_ptr (None: the pool's own, pursuit_records())."""
+        self._ck(self._lib.t2d_pursuit_actions(self._h, act_in_ptr, act_out_ptr, record_ptr, stream))
+
+    def pursuit_records(self, ptr=None, owner=None):
+        """Zero-copy torch views of t2d_pursuit_record [n] at `ptr` (None: the pool's own records): point float64 [n, 2];
+        pre_aiming_distance, distance, cross_track float64 [n]; segment, target_segment, leader, events int32 [n]; action
+        float64 [n, 2] (NaN: the caller's row went through).  Views of the pool's own records are valid until the next set_pursuit, which
+        replaces or frees them."""
+        import torch
+        if ptr is None:
+            p_, nb = C.c_void_p(), C.c_size_t()
+            self._ck(self._lib.t2d_pursuit_buffers(self._h, C.byref(p_), C.byref(nb)))
+            ptr = p_.value
+        dev, n = f"cuda:{self.device_id}", self.n
+        keep = owner if owner is not None else self
+        i32 = torch.as_tensor(_DevArray(ptr, (n, L.PURSUIT_RECORD_BYTES // 4), "<i4", keep), device=dev)
+        f64 = torch.as_tensor(_DevArray(ptr, (n, L.PURSUIT_RECORD_BYTES // 8), "<f8", keep), device=dev)
+        return dict(point=f64[:, 0:2], pre_aiming_distance=f64[:, 2], distance=f64[:, 3], cross_track=f64[:, 4],
+                    segment=i32[:, 10], target_segment=i32[:, 11], leader=i32[:, 12], events=i32[:, 13], action=f64[:, 7:9])
+
     def verify_state_ptr(self, x_ptr, y_ptr, heading_ptr, speed_ptr, interval_ms, valid_ptr, stream=None):
         """verify_state of device-resident candidate columns against the pool's current state."""
         self._ck(self._lib.t2d_verify_state(self._h, x_ptr, y_ptr, heading_ptr, speed_ptr, int(interval_ms),
