@@ -44,6 +44,9 @@
  *                            ParticipantBase._verify_trajectory  participant/element/participant_base.py:120-131
  *   t2d_set_routes* /     <- OffRoute.reset / update             traffic/event_detection/off_route.py:24-51
  *   t2d_off_route            Trajectory.get_trace (trace routes)  participant/trajectory/trajectory.py:151-168
+ *   t2d_dubins_paths /    <- Dubins.get_all_path / get_path / get_curve  interpolator/dubins.py:240-331
+ *   t2d_curve_lines /        DubinsPath.get_curve_line :28-104; ReedsSheppPath.get_curve_line  interpolator/reeds_shepp.py:46-139
+ *   t2d_curve_routes         Circle.get_arc  geometry/circle.py:106-139 (the curve written into the routes above)
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -959,6 +962,74 @@ int t2d_rs_config(t2d_pool* pool, const t2d_rs_params* cfg, const float* vehicle
 int t2d_rs_plan(t2d_pool* pool, const float* lidar_dev, t2d_rs_plan_record* out_dev, void* hip_stream);
 int t2d_rs_plan_buffers(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
 
+/* Dubins paths and sampled curve lines on the device -- interpolator/dubins.py (Dubins :107-331, DubinsPath :14-104),
+ * ReedsSheppPath.get_curve_line (interpolator/reeds_shepp.py:46-139) and Circle.get_arc (geometry/circle.py:106-139).
+ *
+ * Dubins.get_all_path (:240-273) returns six slots in a fixed order, LRL, RLR, LSL, RSL, RSR, LSR: None or a DubinsPath with
+ * segments (t, p, q) in units of the radius and length = |segments|.sum() * radius; theta = atan2(dy, dx), d = |delta| / radius,
+ * alpha / beta = mod(heading - theta, 2 pi); a CSC word is None for a negative discriminant, a CCC word for |discriminant| > 1.
+ * get_path (:275-304) keeps the LAST of several equal shortest lengths.  _LRL (:216-231) computes t = mod(-alpha + tmp + p / 2)
+ * where the family's form has -alpha - tmp + p / 2: the curve of slot 0 misses the goal.  lrl_rule 0 keeps it
+ * as written; lrl_rule 1, BUILD-DEFINED, corrects that sign and changes nothing else.
+ *   t2d_dubins_slot_info  the letters of one slot, host only: letters[3] +1 L / -1 R / 0 S.
+ *   t2d_dubins_paths      get_all_path for n independent queries in ONE launch, asynchronous on hip_stream, no pool:
+ *                         start_dev / goal_dev f64 [n][3] (x, y, heading) -> valid_dev u8 [n] (bit s: slot s is a path),
+ *                         segments_dev f64 [n][6][3] (zero for None), length_dev f64 [n][6] (metres, +inf for None),
+ *                         shortest_dev i32 [n][2]: get_path's slot, then the lowest-index shortest one; -1: no slot is a path,
+ *                         which is also the BUILD-DEFINED answer to a query that is not finite.  T2D_ERR_INVALID for
+ *                         radius <= 0 (Dubins.__init__ :126-128 raises ValueError), n < 0, an lrl_rule other than 0 / 1 or a
+ *                         null pointer: nothing is launched.
+ *
+ * A curve line is the point list of get_curve_line: the word walked segment by segment from the start pose.
+ *   arcs       centre = point + r (cos(h +- pi/2), sin(h +- pi/2)), + for L; start angle h + pi/2 for R, h - pi/2 for L; points
+ *              centre + r (cos a_k, sin a_k), a_k = a0 + k ((a0 + delta) - a0), delta = -+step / r, as many as numpy's arange
+ *              gives, ceil((stop - start) / delta) in fp64: the arc's END POINT IS NOT among them; yaw = linspace(h, h_end,
+ *              count), which does reach the end heading.  Clockwise: Dubins: the letter is R; Reeds-Shepp: (R and forward) or
+ *              (L and backward).
+ *   straights  linspace from the point to the end point, end included (the next segment's first point repeats it);
+ *              max(1, ceil(L / step)) points for Dubins, max(2, ceil(L / step)) for Reeds-Shepp.
+ *   tiny       |length| < 1e-15: the single point.  An arc of 0 points is [point] for Dubins; for Reeds-Shepp an arc of fewer
+ *              than 2 points is [point, end_point] with yaw [h, h_end].
+ * One word per curve, 48 bytes: f64 seg[5] (signed lengths in units of the radius; under T2D_CURVE_RS the sign is the
+ * reference's `forward`; under T2D_CURVE_DUBINS |seg| is read, as DubinsPath.get_curve_line does, so a negative length drives
+ * forward), i8 letter[5] (+1 L / -1 R / 0 S), i8 n_seg, 2 bytes of padding.
+ * BUILD-DEFINED: a word of 0 segments (or of more than T2D_RS_MAX_SEGMENTS), or a start or segment that is not finite, gives
+ * count 0 and nothing else written; a curve of more than max_points points writes its first max_points and count holds the
+ * FULL count (saturating at INT32_MAX; a single segment's count at 2^30).
+ *   t2d_curve_lines   n curves in ONE launch, asynchronous on hip_stream, no pool: words_dev [n] (8-byte aligned), start_dev
+ *                     f64 [n][3], rule T2D_CURVE_DUBINS / T2D_CURVE_RS -> xy_dev f64 [n][max_points][2] (16-byte aligned),
+ *                     yaw_dev f64 [n][max_points], count_dev i32 [n], end_dev f64 [n][3] (next_point / next_heading after the
+ *                     last segment).  T2D_ERR_INVALID for radius, step_size or max_points <= 0, n < 0, another rule, a null or
+ *                     misaligned pointer: nothing is launched.
+ *   t2d_curve_routes  the same sampler, curve e for env e, written as fp32 vertices INTO the installed route sets' own device
+ *                     storage: route `route` of env e's set, whose vertex count is the capacity.  count c == 0: the route is
+ *                     left untouched; c <= capacity: vertices k < c are the points, vertices k >= c the curve's END POINT (the
+ *                     route reaches the goal although the arcs omit it; zero-length segments are defined by every consumer);
+ *                     c > capacity: the first `capacity` points.  count_dev i32 [n_env] (may be NULL) = c in every case.
+ *                     t2d_off_route, t2d_pid_actions and t2d_pursuit_actions see the curve in their next launch on the stream.
+ *                     Offsets, assignment and thresholds are untouched.  T2D_ERR_STATE unless route sets are the installed
+ *                     kind, no two envs share a set and every env's set has a route `route`; T2D_ERR_INVALID as above.
+ *                     kernel_id T2D_PROFILE_CURVE_ROUTES in t2d_profile_read.
+ *   t2d_route_vertices  the installed route sets' vertex storage, f32 [n_vertices][2] in the order of t2d_set_routes' verts_xy
+ *                     (what t2d_curve_routes writes into and the three consumers read); valid until the routes are replaced or
+ *                     cleared.  The memory is writable: a caller that writes through it edits the routes the consumers read and
+ *                     orders those writes against their launches itself.  T2D_ERR_STATE unless route sets are the installed kind;
+ *                     T2D_ERR_INVALID for a null output.                                    */
+#define T2D_DUBINS_SLOTS 6
+#define T2D_CURVE_WORD_BYTES 48
+#define T2D_CURVE_DUBINS 0
+#define T2D_CURVE_RS 1
+#define T2D_PROFILE_CURVE_ROUTES 17
+int t2d_dubins_slot_info(int32_t slot, int8_t* letters);
+int t2d_dubins_paths(int32_t device_id, int32_t n, double radius, const double* start_dev, const double* goal_dev, int32_t lrl_rule,
+                     uint8_t* valid_dev, double* segments_dev, double* length_dev, int32_t* shortest_dev, void* hip_stream);
+int t2d_curve_lines(int32_t device_id, int32_t n, const void* words_dev, const double* start_dev, double radius, double step_size,
+                    int32_t rule, int32_t max_points, double* xy_dev, double* yaw_dev, int32_t* count_dev, double* end_dev,
+                    void* hip_stream);
+int t2d_curve_routes(t2d_pool* pool, const void* words_dev, const double* start_dev, double radius, double step_size, int32_t rule,
+                     int32_t route, int32_t* count_dev, void* hip_stream);
+int t2d_route_vertices(t2d_pool* pool, void** verts_dev, size_t* n_vertices);
+
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
  * over the action row of an env while a path is being executed and leaves the policy's row alone otherwise.
@@ -1398,7 +1469,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * 7 = chained steps (t2d_step_n), 8 = lidar of every participant (t2d_lidar_scan_all), 9 = off-route (t2d_off_route),
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
  * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
- * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions).  */
+ * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions),
+ * 17 = curve lines into the route sets (t2d_curve_routes).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

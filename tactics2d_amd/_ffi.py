@@ -139,6 +139,11 @@ SYMBOLS = {
     "t2d_generated_track_buffers": (C.c_int, [_vp] + [C.POINTER(_vp)] * 8 + [C.POINTER(C.c_size_t)]),
     "t2d_rs_slot_info": (C.c_int, [C.c_int32, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "t2d_rs_paths": (C.c_int, [C.c_int32, C.c_int32, C.c_double] + [_vp] * 7),
+    "t2d_dubins_slot_info": (C.c_int, [C.c_int32, _vp]),
+    "t2d_dubins_paths": (C.c_int, [C.c_int32, C.c_int32, C.c_double, _vp, _vp, C.c_int32] + [_vp] * 5),
+    "t2d_curve_lines": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_double, C.c_double, C.c_int32, C.c_int32] + [_vp] * 5),
+    "t2d_curve_routes": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _vp]),
+    "t2d_route_vertices": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "t2d_rs_config": (C.c_int, [_vp, C.POINTER(RSParams), _vp]),
     "t2d_rs_plan": (C.c_int, [_vp, _vp, _vp, _vp]),
     "t2d_rs_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),

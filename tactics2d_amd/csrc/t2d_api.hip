@@ -2996,6 +2996,9 @@ static void route_release(t2d_pool* p) {
     p->d_route_geo = {};
     p->route = t2d::RouteView{};
     p->route_limit.clear();
+    p->route_min_limit = 0;
+    p->route_n_vert = 0;
+    p->route_sets_distinct = false;
 }
 
 namespace {
@@ -3098,6 +3101,17 @@ int t2d_set_routes(t2d_pool* p, int32_t n_sets, const int32_t* set_route_offsets
     p->d_route_geo = std::move(blob);
     const void* d = p->d_route_geo;
     p->route_limit = std::move(limit);
+    p->route_n_vert = n_vert;
+    p->route_min_limit = *std::min_element(p->route_limit.begin(), p->route_limit.end());
+    {   // (what t2d_curve_routes asks of the installed offsets)
+        std::vector<char> used(n_sets, 0);
+        p->route_sets_distinct = true;
+        for (int e = 0; e < E; ++e) {
+            const int s = set_of_env ? set_of_env[e] : 0;
+            if (used[s]) p->route_sets_distinct = false;
+            used[s] = 1;
+        }
+    }
     t2d::RouteView& rv = p->route;
     rv.kind = 1;
     rv.lds_bytes = lds_bytes;
@@ -3214,6 +3228,39 @@ int t2d_off_route(t2d_pool* p, float* dist_out_dev, uint8_t* off_out_dev, void* 
     T2D_HIP(p, t2d::launch_off_route(p->v, p->route, dist_out_dev ? dist_out_dev : p->d_route_dist,
                                      off_out_dev ? off_out_dev : p->d_route_off, s));
     return record_event(p, 9, s, false);
+}
+
+int t2d_curve_routes(t2d_pool* p, const void* words_dev, const double* start_dev, double radius, double step_size, int32_t rule,
+                     int32_t route, int32_t* count_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!words_dev || !start_dev || (reinterpret_cast<uintptr_t>(words_dev) & 7u))
+        return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: null or misaligned words_dev / start_dev");
+    if (!(radius > 0.0) || !std::isfinite(radius) || !(step_size > 0.0) || !std::isfinite(step_size))
+        return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: radius and step_size must be positive and finite");
+    if (rule != T2D_CURVE_DUBINS && rule != T2D_CURVE_RS) return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: rule must be T2D_CURVE_DUBINS or T2D_CURVE_RS");
+    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: route must be >= 0");
+    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_curve_routes writes into route sets: t2d_set_routes must precede it");
+    if (!p->route_sets_distinct)
+        return fail(p, T2D_ERR_STATE, "t2d_curve_routes: two envs share a route set; install one set per env (set_of_env)");
+    if (route >= p->route_min_limit)
+        return fail(p, T2D_ERR_STATE, "t2d_curve_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
+                                          std::to_string(p->route_min_limit) + " routes)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, T2D_PROFILE_CURVE_ROUTES, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_curve_routes(p->v, p->route, words_dev, start_dev, radius, step_size, rule, route, count_dev, s));
+    return record_event(p, T2D_PROFILE_CURVE_ROUTES, s, false);
+}
+
+int t2d_route_vertices(t2d_pool* p, void** verts_dev, size_t* n_vertices) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!verts_dev || !n_vertices) return fail(p, T2D_ERR_INVALID, "null output");
+    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_route_vertices: route sets (t2d_set_routes) are not the installed kind");
+    *verts_dev = const_cast<float*>(p->route.verts);
+    *n_vertices = (size_t)p->route_n_vert;
+    return T2D_OK;
 }
 
 int t2d_off_route_buffers(t2d_pool* p, void** dist_dev, void** off_dev, size_t* n_elements) {

@@ -452,6 +452,9 @@ struct t2d_pool {
     t2d::DevBuf<float> d_route_dist;
     t2d::DevBuf<uint8_t> d_route_off;
     std::vector<int32_t> route_limit;       // [E] exclusive upper bound of route_of in env e (routes of its set / max_agents)
+    int32_t route_n_vert = 0;               // sets: vertices of all sets together (t2d_route_vertices)
+    int32_t route_min_limit = 0;            // sets: the smallest route_limit (t2d_curve_routes: every env's set has route r < this)
+    bool route_sets_distinct = false;       // sets: no two envs use the same set (t2d_curve_routes writes one curve per env)
     // racing tile progress (t2d_set_tracks): one allocation behind every pointer of the view; n_tile of each env's track
     t2d::TrackView track{};
     t2d::DevBuf<> d_track;
@@ -615,6 +618,9 @@ hipError_t launch_verify_states(const PoolView& v, const float* buf, int capacit
 hipError_t launch_replay(const PoolView& v, const ReplaySpec& r, int step_ms, hipStream_t s);
 // off-route detector (t2d_route.hip): distance (f32) and verdict (u8) of every participant against its route
 hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s);
+// curve lines into the route sets (t2d_curve.hip): curve e -> the fp32 vertices of route `route` of env e's set
+hipError_t launch_curve_routes(const PoolView& v, const RouteView& rv, const void* words, const double* start, double radius,
+                               double step, int rule, int route, int32_t* count, hipStream_t s);
 // racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
 hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
 hipError_t launch_trackgen(const TrackGenView& g, int n, int mode, hipStream_t s);

@@ -1,8 +1,10 @@
-"""Reeds-Shepp curves for batches of queries on the device (tactics2d/interpolator/reeds_shepp.py).
+"""Reeds-Shepp and Dubins curves for batches of queries on the device (tactics2d/interpolator/reeds_shepp.py, dubins.py).
 
 `ReedsShepp(radius).get_all_path(...)` is the reference's method of that name for n queries in one launch of
-t2d_rs_paths (include/t2d.h): the 48 slots of the reference's list, in its order, as device tensors.  The point lists of
-ReedsSheppPath.get_curve_line are not provided.  There is no CPU path: without a device the calls raise T2DError.
+t2d_rs_paths (include/t2d.h): the 48 slots of the reference's list, in its order, as device tensors.  `Dubins(radius)` is the
+same for the six Dubins words (t2d_dubins_paths).  `get_curve(...)` of either class samples the shortest path of every query into
+the point list of the reference's get_curve_line (t2d_curve_lines); `curve_lines(...)` is that call for words of the caller's own.
+There is no CPU path: without a device the calls raise T2DError.
 """
 import ctypes as C
 import functools
@@ -69,6 +71,76 @@ class RSPath:
         self.slot, self.segments, self.steer, self.n_seg, self.length = slot, segments, steer, n_seg, length
 
 
+def _stream_of(device_id, stream):
+    """(torch device, torch stream) a call works on: `stream`, or the device's current one"""
+    import torch
+    try:
+        dev = torch.device("cuda", device_id)
+        return dev, stream if stream is not None else torch.cuda.current_stream(dev)
+    except (RuntimeError, AssertionError) as exc:
+        raise _ffi.T2DError(_ffi.ERR_HIP, f"no usable HIP device: {exc}") from None
+
+
+class CurveLines:
+    """What curve_lines / get_curve return: device tensors, one row per curve.  xy float64 [n, max_points, 2] and yaw float64
+    [n, max_points]: the first min(count, max_points) rows of a curve are its points, the rest is not written; count int32 [n]:
+    the curve's FULL point count (0: no curve; > max_points: truncated); end float64 [n, 3]: the pose after the last segment
+    (not written where count is 0); slot int32 [n]: the path each curve was sampled from (get_curve; None for curve_lines)."""
+
+    def __init__(self, xy, yaw, count, end, slot=None):
+        self.xy, self.yaw, self.count, self.end, self.slot = xy, yaw, count, end, slot
+
+
+def pack_words(segments, letters, n_seg):
+    """The word records of t2d_curve_lines (layout.CURVE_WORD_BYTES each) as a float64 device tensor [n, 6], made on the device of
+    `segments`: segments float64 [n, 5] signed lengths in units of the radius, letters int [n, 5] (+1 L, -1 R, 0 S), n_seg int [n]."""
+    import torch
+    n = segments.shape[0]
+    words = torch.zeros((n, L.CURVE_WORD_BYTES // 8), dtype=torch.float64, device=segments.device)
+    words[:, :L.RS_MAX_SEGMENTS] = segments
+    tail = words.view(torch.int8).view(n, L.CURVE_WORD_BYTES)
+    tail[:, 40:40 + L.RS_MAX_SEGMENTS] = letters.to(torch.int8)
+    tail[:, 40 + L.RS_MAX_SEGMENTS] = n_seg.to(torch.int8)
+    return words
+
+
+def curve_lines(words, starts, radius, step_size, rule, max_points, device_id=0, stream=None):
+    """t2d_curve_lines: words float64 CUDA tensor [n, 6] (pack_words), starts float64 CUDA tensor [n, 3] (x, y, heading), rule
+    layout.CURVE_DUBINS / CURVE_RS (or "dubins" / "rs").  One launch, asynchronous on `stream`.  Returns CurveLines."""
+    import torch
+    lib = _ffi.lib()
+    rule = {"dubins": L.CURVE_DUBINS, "rs": L.CURVE_RS}.get(rule, rule)
+    try:
+        dev = torch.device("cuda", device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+    except (RuntimeError, AssertionError) as exc:
+        raise _ffi.T2DError(_ffi.ERR_HIP, f"no usable HIP device: {exc}") from None
+    n = words.shape[0]
+    if words.dtype != torch.float64 or tuple(words.shape) != (n, L.CURVE_WORD_BYTES // 8) or not words.is_contiguous():
+        raise ValueError("words must be a contiguous float64 [n, 6] tensor (pack_words)")
+    if starts.dtype != torch.float64 or tuple(starts.shape) != (n, 3) or not starts.is_contiguous():
+        raise ValueError("starts must be a contiguous float64 [n, 3] tensor")
+    max_points = int(max_points)
+    with torch.cuda.stream(st):
+        rows = max(max_points, 0)
+        xy = torch.empty((n, rows, 2), dtype=torch.float64, device=dev)
+        yaw = torch.empty((n, rows), dtype=torch.float64, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        end = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        _ffi.check(lib.t2d_curve_lines(device_id, n, words.data_ptr(), starts.data_ptr(), float(radius), float(step_size), int(rule),
+                                       max_points, xy.data_ptr(), yaw.data_ptr(), count.data_ptr(), end.data_ptr(), st.cuda_stream),
+                   None, lib)
+    out = CurveLines(xy, yaw, count, end)
+    out._inputs = (words, starts)   # (kept alive with the result)
+    return out
+
+
+def default_max_points(radius, step_size, reach):
+    """A point budget for get_curve: a shortest path between poses at most `reach` metres apart is shorter than reach + 7 pi
+    radius (three arcs of a full turn and a half at the very most), one point per step and two per segment on top."""
+    return int(np.ceil((float(reach) + 7.0 * np.pi * float(radius)) / float(step_size))) + 2 * L.RS_MAX_SEGMENTS
+
+
 class ReedsShepp(metaclass=_SlotTables):
     """ReedsShepp (reeds_shepp.py:142-156) for batches.  WORDS / CURVE_TYPES: the word ("LSL", ...) and the curve type ("CSC",
     ...) of each of the 48 slots; LETTERS / SIGNS / N_SEG the same table as arrays (on the class; read from the library on first
@@ -130,15 +202,157 @@ class ReedsShepp(metaclass=_SlotTables):
             return out
 
     def get_path(self, start_points, start_headings, end_points, end_headings, stream=None):
-        """The shortest path of each query by the reference's rule (get_path :529-558: the last of equal shortest lengths)."""
+        """The shortest path of each query by the reference's rule (get_path :529-558: the last of equal shortest lengths).  The
+        launch and the gather behind it are both enqueued on `stream`."""
         import torch
-        r = self.get_all_path(start_points, start_headings, end_points, end_headings, stream)
-        dev = r.mask.device
-        k = r.shortest.long().clamp(min=0)
-        rows = torch.arange(k.shape[0], device=dev)
-        none = r.shortest < 0
-        letters = torch.as_tensor(_tables()["LETTERS"], device=dev)[k]
-        n_seg = torch.as_tensor(_tables()["N_SEG"], device=dev)[k]
-        zero = none[:, None]
-        return RSPath(r.shortest, r.segments[rows, k].masked_fill(zero, 0.0), letters.masked_fill(zero, 0),
-                      n_seg.masked_fill(none, 0), r.length[rows, k].masked_fill(none, float("inf")))
+        dev, st = _stream_of(self.device_id, stream)
+        with torch.cuda.stream(st):
+            r = self.get_all_path(start_points, start_headings, end_points, end_headings, st)
+            k = r.shortest.long().clamp(min=0)
+            rows = torch.arange(k.shape[0], device=dev)
+            none = r.shortest < 0
+            letters = torch.as_tensor(_tables()["LETTERS"], device=dev)[k]
+            n_seg = torch.as_tensor(_tables()["N_SEG"], device=dev)[k]
+            zero = none[:, None]
+            out = RSPath(r.shortest, r.segments[rows, k].masked_fill(zero, 0.0), letters.masked_fill(zero, 0),
+                         n_seg.masked_fill(none, 0), r.length[rows, k].masked_fill(none, float("inf")))
+        out._inputs = r._inputs
+        return out
+
+    def get_curve(self, start_points, start_headings, end_points, end_headings, step_size=0.01, max_points=None, stream=None):
+        """ReedsShepp.get_curve (:560-585): get_path's choice of every query sampled by ReedsSheppPath.get_curve_line (:46-139) at
+        the reference's default step.  max_points None: default_max_points for poses up to 64 m apart (at the default step some
+        16 000 points, 0.4 MB, per query: pass a budget that fits the scene).  The gather from (segments, slot) to words is torch
+        ops on the device; both launches and those ops are enqueued on `stream`.  Returns CurveLines (count 0 where no slot is a
+        path)."""
+        import torch
+        _, st = _stream_of(self.device_id, stream)
+        if max_points is None:
+            max_points = default_max_points(self.radius, step_size, 64.0)
+        with torch.cuda.stream(st):
+            path = self.get_path(start_points, start_headings, end_points, end_headings, st)
+            words = pack_words(path.segments, path.steer, path.n_seg)
+            out = curve_lines(words, path._inputs[0], self.radius, step_size, L.CURVE_RS, max_points, self.device_id, st)
+        out.slot = path.slot
+        return out
+
+
+def dubins_slot_table(library=None):
+    """letters int8 [6, 3] (+1 L, -1 R, 0 S): the library's own table of the six Dubins words (t2d_dubins_slot_info)"""
+    lib = library if library is not None else _ffi.lib()
+    letters = np.zeros((L.DUBINS_SLOTS, 3), np.int8)
+    for s in range(L.DUBINS_SLOTS):
+        _ffi.check(lib.t2d_dubins_slot_info(s, letters[s].ctypes.data_as(C.c_void_p)), None, lib)
+    return letters
+
+
+@functools.lru_cache(None)
+def _dubins_tables():
+    letters = dubins_slot_table()
+    return dict(LETTERS=letters, WORDS=tuple("".join(_LETTER[int(v)] for v in row) for row in letters))
+
+
+class _DubinsTables(type):
+    """Dubins.WORDS, .LETTERS as class attributes that load the library on first access"""
+    WORDS = property(lambda cls: _dubins_tables()["WORDS"])
+    LETTERS = property(lambda cls: _dubins_tables()["LETTERS"])
+
+
+class DubinsPaths:
+    """What Dubins.get_all_path returns: device tensors, one row per query.
+    valid bool [n, 6]; segments float64 [n, 6, 3] = (t, p, q) of the slot's DubinsPath in units of the radius (zero where the
+    reference's list holds None); length float64 [n, 6] in metres, +inf for None; shortest int32 [n] = get_path's slot (the last
+    of equal shortest lengths); shortest_first int32 [n] = the lowest-index shortest one; -1 where no slot is a path.  mask uint8
+    [n]: bit s = valid[:, s]."""
+
+    def __init__(self, mask, segments, length, shortest, radius):
+        import torch
+        self.mask, self.segments, self.length, self.radius = mask, segments, length, radius
+        self.shortest, self.shortest_first = shortest[:, 0], shortest[:, 1]
+        self.valid = ((mask[:, None].to(torch.int32) >> torch.arange(L.DUBINS_SLOTS, device=mask.device, dtype=torch.int32)) & 1).bool()
+        self.WORDS = Dubins.WORDS
+
+
+class DubinsPath:
+    """What Dubins.get_path returns: per query the chosen slot (-1: none), its segments [n, 3], steer signs [n, 3] (+1 L, -1 R,
+    0 S), n_seg [n] (3, or 0 without a path) and length [n] (+inf without a path), as device tensors."""
+
+    def __init__(self, slot, segments, steer, n_seg, length):
+        self.slot, self.segments, self.steer, self.n_seg, self.length = slot, segments, steer, n_seg, length
+
+
+class Dubins(metaclass=_DubinsTables):
+    """Dubins (dubins.py:107-331) for batches.  WORDS: the word of each of the six slots, LETTERS the same as an array (on the
+    class; read from the library on first access).  lrl: "reference" keeps Dubins._LRL (:216-231) as written -- its curve misses
+    the goal, DESIGN.md 4.18 --, "standard" (build-defined) corrects the sign of its `tmp` term and changes nothing else."""
+
+    LRL_RULES = {"reference": 0, "standard": 1}
+    _poses = ReedsShepp._poses
+
+    def __init__(self, radius, lrl="reference", device_id=0):
+        self.radius = float(radius)
+        if not self.radius > 0:
+            raise ValueError("The minimum turning radius must be positive.")
+        if lrl not in self.LRL_RULES:
+            raise ValueError(f"lrl must be one of {sorted(self.LRL_RULES)}")
+        self.lrl = lrl
+        self.device_id = int(device_id)
+
+    def get_all_path(self, start_points, start_headings, end_points, end_headings, stream=None):
+        """The input conventions of ReedsShepp.get_all_path: points [n, 2] with headings [n] (numpy or torch), or packed float64
+        CUDA tensors [n, 3] with the headings None, read in place.  Asynchronous on `stream`.  Returns DubinsPaths."""
+        import torch
+        lib = _ffi.lib()
+        try:
+            dev = torch.device("cuda", self.device_id)
+            st = stream if stream is not None else torch.cuda.current_stream(dev)
+        except (RuntimeError, AssertionError) as exc:
+            raise _ffi.T2DError(_ffi.ERR_HIP, f"no usable HIP device: {exc}") from None
+        with torch.cuda.stream(st):
+            start, goal = self._poses(start_points, start_headings), self._poses(end_points, end_headings)
+            n = start.shape[0]
+            if goal.shape[0] != n:
+                raise ValueError("start and end must have the same number of queries")
+            mask = torch.empty(n, dtype=torch.uint8, device=dev)
+            seg = torch.empty((n, L.DUBINS_SLOTS, 3), dtype=torch.float64, device=dev)
+            length = torch.empty((n, L.DUBINS_SLOTS), dtype=torch.float64, device=dev)
+            short = torch.empty((n, 2), dtype=torch.int32, device=dev)
+            _ffi.check(lib.t2d_dubins_paths(self.device_id, n, self.radius, start.data_ptr(), goal.data_ptr(),
+                                            self.LRL_RULES[self.lrl], mask.data_ptr(), seg.data_ptr(), length.data_ptr(),
+                                            short.data_ptr(), st.cuda_stream), None, lib)
+            out = DubinsPaths(mask, seg, length, short, self.radius)
+            out._inputs = (start, goal)   # (kept alive with the result)
+            return out
+
+    def get_path(self, start_points, start_headings, end_points, end_headings, stream=None):
+        """The shortest path of each query by the reference's rule (get_path :275-304: the last of equal shortest lengths).  The
+        launch and the gather behind it are both enqueued on `stream`."""
+        import torch
+        dev, st = _stream_of(self.device_id, stream)
+        with torch.cuda.stream(st):
+            r = self.get_all_path(start_points, start_headings, end_points, end_headings, st)
+            k = r.shortest.long().clamp(min=0)
+            rows = torch.arange(k.shape[0], device=dev)
+            none = r.shortest < 0
+            letters = torch.as_tensor(_dubins_tables()["LETTERS"], device=dev)[k]
+            out = DubinsPath(r.shortest, r.segments[rows, k].masked_fill(none[:, None], 0.0), letters.masked_fill(none[:, None], 0),
+                             torch.full_like(r.shortest, 3).masked_fill(none, 0), r.length[rows, k].masked_fill(none, float("inf")))
+        out._inputs = r._inputs
+        return out
+
+    def get_curve(self, start_points, start_headings, end_points, end_headings, step_size=0.1, max_points=None, stream=None):
+        """Dubins.get_curve (:306-331): get_path's choice of every query sampled by DubinsPath.get_curve_line (:28-104) at the
+        reference's default step.  max_points None: default_max_points for poses up to 64 m apart.  The gather from (segments,
+        slot) to words is torch ops on the device; both launches and those ops are enqueued on `stream`.  Returns CurveLines
+        (count 0 where no slot is a path)."""
+        import torch
+        _, st = _stream_of(self.device_id, stream)
+        if max_points is None:
+            max_points = default_max_points(self.radius, step_size, 64.0)
+        with torch.cuda.stream(st):
+            path = self.get_path(start_points, start_headings, end_points, end_headings, st)
+            pad = torch.zeros((path.segments.shape[0], L.RS_MAX_SEGMENTS - 3), dtype=torch.float64, device=path.segments.device)
+            words = pack_words(torch.cat([path.segments, pad], 1), torch.cat([path.steer, pad.to(torch.int8)], 1), path.n_seg)
+            out = curve_lines(words, path._inputs[0], self.radius, step_size, L.CURVE_DUBINS, max_points, self.device_id, st)
+        out.slot = path.slot
+        return out

@@ -60,6 +60,12 @@ RS_SLOTS, RS_MAX_SEGMENTS, RS_MAX_POSES, RS_MAX_BEAMS = 48, 5, 1024, 1024
 RS_NO_TARGET, RS_FAR, RS_FOUND, RS_NONE_FREE, RS_UNCHECKED = range(5)
 RS_RECORD_BYTES = 96
 PROFILE_RS_PLAN = 13         # kernel id of t2d_rs_plan in t2d_profile_read
+# Dubins paths and sampled curve lines (t2d_dubins_paths / t2d_curve_lines / t2d_curve_routes): slots, the word record's size
+# in bytes (f64 seg[5], i8 letter[5], i8 n_seg, 2 bytes of padding), the sampling rules, the kernel id
+DUBINS_SLOTS = 6
+CURVE_WORD_BYTES = 48
+CURVE_DUBINS, CURVE_RS = 0, 1
+PROFILE_CURVE_ROUTES = 17
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_ADOPTED, RS_FOLLOW_POP_REACHED, RS_FOLLOW_POP_RISING, RS_FOLLOW_FINISHED, RS_FOLLOW_RESET, RS_FOLLOW_DROPPED = \

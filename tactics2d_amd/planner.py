@@ -67,6 +67,32 @@ class RSPlanner:
         pool.rs_plan(None if lidar is None else lidar.data_ptr(), self._out.data_ptr(), st.cuda_stream)
         return self._views
 
+    def write_routes(self, route=0, step_size=0.01, plan=None, stream=None):
+        """The current plans as routes (ParticipantPool.curve_routes): the path of every FOUND env, sampled as
+        ReedsSheppPath.get_curve_line samples it (reeds_shepp.py:46-139; step_size: its default) from the ego's rear-axle pose,
+        goes into route `route` of that env's own route set; every other env gives a word of 0 segments, so its route stays.
+        The words are made of the plan records on the device -- steer is the letter, distance / radius the segment --, the start
+        of the state views; nothing crosses to the host.  plan: the dict plan() returned (None: its last one).  Needs
+        pool.set_routes with one set per env, whose route `route` has the capacity in vertices.  Returns the int32 CUDA tensor
+        [n_env] of the curves' point counts (0: no plan, more than the capacity: truncated).  Asynchronous on `stream`."""
+        import torch
+        from .interpolator import pack_words
+        pool = self.pool
+        plan = plan if plan is not None else self._views
+        if plan is None:
+            raise RuntimeError("write_routes needs a plan: call plan() first")
+        dev = torch.device("cuda", pool.device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):
+            found = plan["status"] == L.RS_FOUND
+            radius, shift = float(self.params["radius"]), float(self.params["center_shift"])
+            ego = pool.status_config.ego_index if hasattr(pool, "status_config") else 0
+            cols = [torch.as_tensor(pool.device_array(f), device=dev).view(pool.n_env, pool.max_agents)[:, ego].double()
+                    for f in (L.F_X, L.F_Y, L.F_HEADING)]
+            starts = torch.stack([cols[0] - shift * torch.cos(cols[2]), cols[1] - shift * torch.sin(cols[2]), cols[2]], 1).contiguous()
+            words = pack_words(plan["distance"] / radius, plan["steer"], plan["n_seg"].masked_fill(~found, 0))
+            return pool.curve_routes(words, starts, radius, step_size, L.CURVE_RS, route, stream=st.cuda_stream)
+
 
 FOLLOW_EVENTS = ("adopted", "pop_reached", "pop_rising", "finished", "reset", "dropped")   # bit k: layout.RS_FOLLOW_*
 

@@ -562,6 +562,40 @@ class ParticipantPool:
         off_route_all()).  Asynchronous on `stream`; reads the pool's current state, changes nothing in it."""
         self._ck(self._lib.t2d_off_route(self._h, dist_ptr, off_ptr, stream))
 
+    def curve_routes(self, words, starts, radius, step_size, rule, route=0, count=None, stream=None):
+        """t2d_curve_routes: sample one curve per env (interpolator.pack_words records, float64 CUDA tensor [n_env, 6]; starts float64
+        CUDA tensor [n_env, 3]; rule layout.CURVE_DUBINS / CURVE_RS or "dubins" / "rs") into route `route` of each env's own route
+        set, as fp32 vertices in the installed sets' device storage: the route's vertex count is the capacity, vertices past the
+        curve's points repeat its end point, a word of 0 segments leaves the route as it is.  Needs set_routes with one set per
+        env.  off_route / pid_actions / pursuit_actions see the curve in their next launch on `stream`.  Returns the int32 CUDA
+        tensor [n_env] of the curves' full point counts (`count`, or a new one).  Asynchronous."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        rule = {"dubins": L.CURVE_DUBINS, "rs": L.CURVE_RS}.get(rule, rule)
+        if words.dtype != torch.float64 or tuple(words.shape) != (self.n_env, L.CURVE_WORD_BYTES // 8) or not words.is_contiguous():
+            raise ValueError(f"words must be a contiguous float64 [{self.n_env}, 6] tensor (interpolator.pack_words)")
+        if starts.dtype != torch.float64 or tuple(starts.shape) != (self.n_env, 3) or not starts.is_contiguous():
+            raise ValueError(f"starts must be a contiguous float64 [{self.n_env}, 3] tensor")
+        if count is None:
+            count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
+        elif count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous():
+            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
+        self._ck(self._lib.t2d_curve_routes(self._h, words.data_ptr(), starts.data_ptr(), float(radius), float(step_size), int(rule),
+                                            int(route), count.data_ptr(), st))
+        self._curve_inputs = (words, starts)   # (kept alive until the launch has run)
+        return count
+
+    def route_vertices(self):
+        """Zero-copy torch view float32 [n_vertices, 2] of the installed route sets' vertices on the device (t2d_route_vertices), in
+        the order set_routes flattened them: what curve_routes writes into.  Valid until the routes are replaced or cleared.  The
+        view is writable: writing through it edits the routes off_route / pid_actions / pursuit_actions read, and ordering such
+        writes against their launches is the caller's own business."""
+        import torch
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._ck(self._lib.t2d_route_vertices(self._h, C.byref(ptr), C.byref(n)))
+        return torch.as_tensor(_DevArray(ptr.value, (n.value, 2), "<f4", self), device=f"cuda:{self.device_id}")
+
     def off_route_buffers(self):
         """(distance pointer, verdict pointer, elements) of the pool's own result buffers (after an off_route() into them)."""
         d, o, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
