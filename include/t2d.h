@@ -534,7 +534,9 @@ int t2d_lidar_all_buffer(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
  * arguments of idm_controller.py:33-57 (`configure` :143-157 = calling t2d_set_idm again) plus the two
  * columns of the build-defined leader rule; ctrl_id: host array [n_env * max_agents], index of the
  * participant's parameter set or T2D_IDM_NONE (its action stays whatever the caller supplied).
- * n_ctrl = 0 uninstalls.  t2d_idm_actions = IDMController.step :59-93 for every controlled participant:
+ * A refused call changes nothing in the pool (the three t2d_set_* of the scripted agents share one order: host arguments,
+ * quiesce, the pool's state, new device memory, and only then the exchange).  n_ctrl = 0 uninstalls and frees the installation's
+ * device memory.  t2d_idm_actions = IDMController.step :59-93 for every controlled participant:
  * acceleration (np.clip-ed to [-comfortable_deceleration, max_acceleration]) -> the pool's T2D_F_ACT0, steering
  * 0.0 -> T2D_F_ACT1 (always the pool's own fields: memory bound with t2d_bind_actions is never written; controlled
  * participants are integrated from the pool's fields, the others from the bound memory), leader index ->
@@ -1152,7 +1154,8 @@ int t2d_rs_follow_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
  *                    controlled as well (t2d_set_idm refuses the same afterwards), for one that is pursuit-controlled
  *                    (t2d_set_pursuit; t2d_set_idm refuses that too) and for an idm_row outside the installed rows;
  *                    T2D_ERR_STATE for lon_mode 2 without installed IDM rows.  A refused call changes nothing.  Clears the state
- *                    of every participant.  n_ctrl = 0 uninstalls.
+ *                    of every participant.  n_ctrl = 0 uninstalls and frees the installation's device memory, the pool's own
+ *                    records included.
  *   t2d_pid_actions  one launch, asynchronous on hip_stream.  act_in_dev / act_out_dev: f32 [N][2] rows (steering, accel), may be
  *                    the same memory; act_in_dev is never written, NULL = zeros.  Controlled rows receive the fp32 rounding of the
  *                    fp64 action.  record_dev: t2d_pid_record [N] (8-byte aligned) or NULL = the pool's own.  T2D_ERR_STATE
@@ -1163,7 +1166,8 @@ int t2d_rs_follow_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
  *                    t2d_reset without a mask does the same for every env.
  *   t2d_pid_state    the six fp64 state words of every participant, host array [N][6] in the order of T2D_PID_S_*: write = 0
  *                    reads them (after the pool's work), write != 0 replaces them.
- *   t2d_pid_buffers  pointer and size in bytes of the pool's own records.                                                    */
+ *   t2d_pid_buffers  pointer and size in bytes of the pool's own records, valid until the next t2d_set_pid (which replaces or
+ *                    frees them).                                                                                             */
 enum {
     T2D_PID_DT = 0,
     T2D_PID_KP_LAT = 1,
@@ -1276,7 +1280,8 @@ int t2d_pid_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
  *                        route set is installed, when trace routes are the installed kind, and when a row has lon_mode 0 / 1
  *                        while t2d_set_outputs has switched T2D_OUT_APPLIED off (accel_last would be stale);
  *                        T2D_ERR_INVALID without act_out_dev.  kernel_id T2D_PROFILE_PURSUIT in t2d_profile_read.
- *   t2d_pursuit_buffers  pointer and size in bytes of the pool's own records.                                                */
+ *   t2d_pursuit_buffers  pointer and size in bytes of the pool's own records, valid until the next t2d_set_pursuit (which
+ *                        replaces or frees them).                                                                           */
 enum {
     T2D_PURSUIT_MIN_PRE_AIMING = 0,    /* PurePursuitController.min_pre_aiming_distance */
     T2D_PURSUIT_INTERVAL_LAT = 1,      /* PurePursuitController.interval */

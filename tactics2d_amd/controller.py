@@ -276,45 +276,66 @@ def install_pid(pool, controllers, ctrl_id, target_speed=0.0, idm=None):
 PID_EVENTS = ("route_end", "nonfinite", "reset", "no_route", "bad_wheel_base", "saturated")   # bit k: layout.PID_*
 
 
-class LaneKeeper:
-    """The controllers installed on `pool` (install_pid) in a step_torch-style loop: follow() writes the action rows to step
-    with -- bind them with pool.bind_actions(rows + 4 bytes, rows, stride=2) -- and returns zero-copy torch views of the
-    records (ParticipantPool.pid_records) beside them."""
+class _ActionWriter:
+    """What LaneKeeper, PathFollower and planner.RSFollower share: one launch per call that writes one (steering, accel) row and
+    one record per row of the action tensor, into lazily made buffers of the object's own unless the caller brings the rows.
+    A subclass names its records (their size in bytes, the ParticipantPool method that views them, whether there is one row
+    per participant or per env) and passes its launch to _write / _reset."""
+    _record_bytes = _records = None
+    _n_rows = "n"   # the pool attribute that counts the rows: "n" (participants) or "n_env"
 
     def __init__(self, pool):
         self.pool = pool
         self._rec = self._views = self._act = None
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.pool.device_id))
+
+    def _write(self, launch, actions, out, stream):
+        """launch(act_in_ptr, act_out_ptr, record_ptr, stream handle) -> dict(the record views, action_rows=the rows written)"""
+        import torch
+        n, st = getattr(self.pool, self._n_rows), self._stream(stream)
+        for t in (actions, out):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n, 2) or not t.is_contiguous()):
+                raise ValueError(f"action rows must be a contiguous float32 [{n}, 2] tensor")
+        if self._rec is None:
+            self._rec = torch.zeros((n, self._record_bytes // 8), dtype=torch.float64, device=st.device)
+            self._views = getattr(self.pool, self._records)(self._rec.data_ptr(), owner=self._rec)
+            self._act = torch.zeros((n, 2), dtype=torch.float32, device=st.device)
+        rows = self._act if out is None else out
+        launch(None if actions is None else actions.data_ptr(), rows.data_ptr(), self._rec.data_ptr(), st.cuda_stream)
+        return dict(self._views, action_rows=rows)
+
+    def _reset(self, launch, mask, stream):
+        """launch(mask_ptr, stream handle) with `mask` as uint8 [n_env] (None: every env)"""
+        import torch
+        st = self._stream(stream)
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+            if tuple(mask.shape) != (self.pool.n_env,):
+                raise ValueError(f"mask must have {self.pool.n_env} elements")
+            self._mask = mask   # (kept alive until the launch has run)
+        launch(None if mask is None else mask.data_ptr(), st.cuda_stream)
+
+
+class LaneKeeper(_ActionWriter):
+    """The controllers installed on `pool` (install_pid) in a step_torch-style loop: follow() writes the action rows to step
+    with -- bind them with pool.bind_actions(rows + 4 bytes, rows, stride=2) -- and returns zero-copy torch views of the
+    records (ParticipantPool.pid_records) beside them."""
+
+    _record_bytes, _records = L.PID_RECORD_BYTES, "pid_records"
 
     def follow(self, actions=None, out=None, stream=None):
         """actions: float32 CUDA tensor [n, 2] (steering, accel), the rows of whoever else acts (None: zeros), never written
         unless it is also `out`; out: float32 [n, 2] tensor for the rows to step (None: a buffer of the keeper's own).
         Asynchronous on `stream`.  Returns dict(action_rows, cross_track, lat_error, segment, leader, events, action), valid until
         the next follow()."""
-        import torch
-        pool = self.pool
-        dev = torch.device("cuda", pool.device_id)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        for t in (actions, out):
-            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n, 2) or not t.is_contiguous()):
-                raise ValueError(f"action rows must be a contiguous float32 [{pool.n}, 2] tensor")
-        if self._rec is None:
-            self._rec = torch.zeros((pool.n, L.PID_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
-            self._views = pool.pid_records(self._rec.data_ptr(), owner=self._rec)
-            self._act = torch.zeros((pool.n, 2), dtype=torch.float32, device=dev)
-        rows = self._act if out is None else out
-        pool.pid_actions(None if actions is None else actions.data_ptr(), rows.data_ptr(), self._rec.data_ptr(), st.cuda_stream)
-        return dict(self._views, action_rows=rows)
+        return self._write(self.pool.pid_actions, actions, out, stream)
 
     def reset(self, mask=None, stream=None):
         """controller.reset() for the envs where `mask` (a uint8 / bool CUDA tensor [n_env]) is non-zero; None: every env"""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.pool.device_id))
-        if mask is not None:
-            mask = mask.to(torch.uint8).contiguous()
-            if tuple(mask.shape) != (self.pool.n_env,):
-                raise ValueError(f"mask must have {self.pool.n_env} elements")
-            self._mask = mask   # (kept alive until the launch has run)
-        self.pool.pid_reset(None if mask is None else mask.data_ptr(), st.cuda_stream)
+        self._reset(self.pool.pid_reset, mask, stream)
 
 
 # ---------------------------------------------------------------------------------------------------- pure pursuit, cruise / ACC
@@ -523,32 +544,17 @@ def install_pursuit(pool, controllers, ctrl_id, target_speed=None, longitudinal=
 PURSUIT_EVENTS = ("route_end", "nonfinite", "wrapped", "no_route", "no_leader")   # bit k: layout.PURSUIT_*
 
 
-class PathFollower:
+class PathFollower(_ActionWriter):
     """The controllers installed on `pool` (install_pursuit) in a step_torch-style loop: LaneKeeper's contract without reset()
     -- the controllers hold no state.  follow() writes the action rows to step with -- bind them with
     pool.bind_actions(rows + 4 bytes, rows, stride=2) -- and returns zero-copy torch views of the records
     (ParticipantPool.pursuit_records) beside them."""
 
-    def __init__(self, pool):
-        self.pool = pool
-        self._rec = self._views = self._act = None
+    _record_bytes, _records = L.PURSUIT_RECORD_BYTES, "pursuit_records"
 
     def follow(self, actions=None, out=None, stream=None):
         """actions: float32 CUDA tensor [n, 2] (steering, accel), the rows of whoever else acts (None: zeros), never written
         unless it is also `out`; out: float32 [n, 2] tensor for the rows to step (None: a buffer of the follower's own).
         Asynchronous on `stream`.  Returns dict(action_rows, point, pre_aiming_distance, distance, cross_track, segment,
         target_segment, leader, events, action), valid until the next follow()."""
-        import torch
-        pool = self.pool
-        dev = torch.device("cuda", pool.device_id)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        for t in (actions, out):
-            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n, 2) or not t.is_contiguous()):
-                raise ValueError(f"action rows must be a contiguous float32 [{pool.n}, 2] tensor")
-        if self._rec is None:
-            self._rec = torch.zeros((pool.n, L.PURSUIT_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
-            self._views = pool.pursuit_records(self._rec.data_ptr(), owner=self._rec)
-            self._act = torch.zeros((pool.n, 2), dtype=torch.float32, device=dev)
-        rows = self._act if out is None else out
-        pool.pursuit_actions(None if actions is None else actions.data_ptr(), rows.data_ptr(), self._rec.data_ptr(), st.cuda_stream)
-        return dict(self._views, action_rows=rows)
+        return self._write(self.pool.pursuit_actions, actions, out, stream)

@@ -21,6 +21,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1, ncclInt32 = 2, ncclUint32 = 3 } nccl
 #endif
 
 #include <algorithm>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <new>
@@ -870,7 +871,7 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
     // (an armed auto-reset may put the snapshot's ids back into any env from the next step on)
     p->types_used = types_used | (p->auto_reset ? p->snap_types : 0u);
     p->have_reset = true;
-    if (!partial && p->pid_on) {   // new episodes everywhere: controller.reset()
+    if (!partial && p->pid.on) {   // new episodes everywhere: controller.reset()
         const int rc = t2d_pid_reset(p, nullptr, nullptr);
         if (rc != T2D_OK) return rc;
     }
@@ -882,8 +883,8 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
 // the two apart
 static void refresh_idm_view(t2d_pool* p) {
     const bool bound = p->v.act0 != (const float*)p->field_ptr[T2D_F_ACT0];
-    const bool sel = p->idm_on && bound;
-    p->v.idm_ctrl = sel ? p->d_idm_ctrl : nullptr;
+    const bool sel = p->idm.on && bound;
+    p->v.idm_ctrl = sel ? p->idm.d_ctrl : nullptr;
     p->v.own_act0 = sel ? (const float*)p->field_ptr[T2D_F_ACT0] : nullptr;
     p->v.own_act1 = sel ? (const float*)p->field_ptr[T2D_F_ACT1] : nullptr;
 }
@@ -929,7 +930,7 @@ static int idm_impl(t2d_pool* p, hipStream_t s, const int32_t* forced_leader = n
     int rc;
     touch(p, s);
     if ((rc = record_event(p, 4, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_idm(p->v, p->idm, forced_leader, (float*)p->field_ptr[T2D_F_ACT0],
+    T2D_HIP(p, t2d::launch_idm(p->v, p->idm.view, forced_leader, (float*)p->field_ptr[T2D_F_ACT0],
                                (float*)p->field_ptr[T2D_F_ACT1], s));
     return record_event(p, 4, s, false);
 }
@@ -1028,7 +1029,7 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if ((rc = replay_check(p, interval_ms))) return rc;
     touch(p, s);
     if ((rc = prepare_interval(p, interval_ms, s))) return rc;
-    if (p->idm_on && (rc = idm_impl(p, s))) return rc;
+    if (p->idm.on && (rc = idm_impl(p, s))) return rc;
     if (p->has_drift && (rc = drift_impl(p, interval_ms, s))) return rc;
     if (p->replay_types && (rc = replay_impl(p, interval_ms, s))) return rc;
     if ((rc = record_event(p, 0, s, true))) return rc;
@@ -1058,14 +1059,14 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
 static bool idm_in_step(t2d_pool* p) {
     // (not pools with SingleTrackDrift participants: drift_kernel runs between the controllers and the step launch and reads
     // the accelerations the controllers wrote -- t2d_step's order is IDM, drift, step -- so there idm_kernel stays a launch)
-    return p->idm_on && p->chain_steps && p->fused_step && !p->grid_tier && !side_models(p) && p->v.A >= 2 && p->v.A <= 64 &&
+    return p->idm.on && p->chain_steps && p->fused_step && !p->grid_tier && !side_models(p) && p->v.A >= 2 && p->v.A <= 64 &&
            !(p->status_cfg.check_no_action || p->status_cfg.check_arrival);
 }
 static void fill_idm(t2d::PoolView& v, t2d_pool* p) {
-    v.idm_rows = p->idm.rows;
-    v.idm_ctrl_all = p->idm.ctrl_id;
-    v.idm_leader = p->idm.leader;
-    v.idm_n_ctrl = p->idm.n_ctrl;
+    v.idm_rows = p->idm.view.rows;
+    v.idm_ctrl_all = p->idm.view.ctrl_id;
+    v.idm_leader = p->idm.view.leader;
+    v.idm_n_ctrl = p->idm.view.n_ctrl;
     v.idm_act0_own = (float*)p->field_ptr[T2D_F_ACT0];
     v.idm_act1_own = (float*)p->field_ptr[T2D_F_ACT1];
 }
@@ -1202,7 +1203,7 @@ int t2d_step(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if ((rc = prepare_interval(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     if ((rc = claim_record_slot(p, (hipStream_t)hip_stream))) return rc;
     // (installed IDM controllers: a launch of their own ahead of the step -- or, idm_in_step, the front of the step launch)
-    if (p->idm_on && !idm_in_step(p) && (rc = idm_impl(p, (hipStream_t)hip_stream))) return rc;
+    if (p->idm.on && !idm_in_step(p) && (rc = idm_impl(p, (hipStream_t)hip_stream))) return rc;
     if (p->has_drift && (rc = drift_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     if (p->replay_types && (rc = replay_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     rc = collide_impl(p, true, interval_ms, (hipStream_t)hip_stream, p->integrator_variant);
@@ -1229,7 +1230,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
     const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
     const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;   // per-env history read by the epilogue
     // (the single-ego kernel has a LOOP form of its own, which reads the history with sc1 loads: IoU events are fine there)
-    const bool chain = p->chain_steps && n_steps >= 2 && p->fused_step && !p->grid_tier && (!p->idm_on || idm_in_step(p)) && !side_models(p) &&
+    const bool chain = p->chain_steps && n_steps >= 2 && p->fused_step && !p->grid_tier && (!p->idm.on || idm_in_step(p)) && !side_models(p) &&
                        !p->scene_regen && (ego ? p->chain_loop : !iou);
     const float *a0 = p->v.act0, *a1 = p->v.act1;
     int rc = T2D_OK;
@@ -1250,7 +1251,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         int n = std::min(n_steps - done, (int)T2D_RECORD_RING);
         // the chained form of large pools: chain_depth steps per workgroup (launches of a multiple of it; what is left over
         // at the end of a call goes out one step per workgroup)
-        const int depth = p->chain_loop && !ego && !p->idm_on && p->chain_depth > 1 && n >= p->chain_depth && log2_pad(p->v.A) <= 6
+        const int depth = p->chain_loop && !ego && !p->idm.on && p->chain_depth > 1 && n >= p->chain_depth && log2_pad(p->v.A) <= 6
                               ? p->chain_depth : 1;
         n -= n % depth;
         const int slot0 = (int)(p->step_count % T2D_RECORD_RING);
@@ -1289,7 +1290,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
                 v.split_step = 0;
                 v.chain_real_wgs = loop_wgs;
             }
-            if (p->idm_on) {   // the integrator waves run the controllers (no lane waves then) -- or every workgroup of the chained form
+            if (p->idm.on) {   // the integrator waves run the controllers (no lane waves then) -- or every workgroup of the chained form
                 v.pipe_step = idm_in_pipe(p) ? 1 : 0;
                 if (!v.pipe_step) {
                     v.split_step = 0;
@@ -1297,7 +1298,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
                 }
                 fill_idm(v, p);
             }
-            v.loop_steps = (!v.split_step && loop_ok && !(p->idm_on && !v.pipe_step)) ? n : 0;
+            v.loop_steps = (!v.split_step && loop_ok && !(p->idm.on && !v.pipe_step)) ? n : 0;
         }
         v.record_ring = (uint2*)p->field_ptr[T2D_F_RECORD];
         v.record_slot0 = slot0;
@@ -1357,7 +1358,7 @@ int t2d_step_form(t2d_pool* p, int32_t n_steps) {
     const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;
     if (!p->fused_step || p->grid_tier || side_models(p) || p->scene_regen) return T2D_FORM_UNFUSED;
     const bool chain = p->chain_steps && n_steps >= 2 && (ego ? p->chain_loop : !iou);
-    if (p->idm_on) {
+    if (p->idm.on) {
         if (ego || !idm_in_step(p)) return T2D_FORM_UNFUSED;
         return !chain ? T2D_FORM_STEP : idm_in_pipe(p) ? T2D_FORM_LOOP_PIPE : T2D_FORM_CHAIN;
     }
@@ -2287,13 +2288,19 @@ int t2d_rs_plan(t2d_pool* p, const float* lidar_dev, t2d_rs_plan_record* out_dev
     return record_event(p, T2D_PROFILE_RS_PLAN, s, false);
 }
 
+// the pool's own records of an installed source (the t2d_*_buffers entry points): where they are and how many bytes
+static int own_records(t2d_pool* p, bool on, const char* need, void* records, size_t bytes, void** records_dev, size_t* nbytes) {
+    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
+    if (!on) return fail(p, T2D_ERR_STATE, need);
+    *records_dev = records;
+    *nbytes = bytes;
+    return T2D_OK;
+}
+
 int t2d_rs_plan_buffers(t2d_pool* p, void** dev_ptr, size_t* nbytes) {
     if (!p) return T2D_ERR_INVALID;
-    if (!dev_ptr || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
-    if (!p->rs_on) return fail(p, T2D_ERR_STATE, "t2d_rs_config must precede t2d_rs_plan_buffers");
-    *dev_ptr = p->d_rs_plan;
-    *nbytes = (size_t)p->v.n_env * sizeof(t2d_rs_plan_record);
-    return T2D_OK;
+    return own_records(p, p->rs_on, "t2d_rs_config must precede t2d_rs_plan_buffers", p->d_rs_plan.get(),
+                       (size_t)p->v.n_env * sizeof(t2d_rs_plan_record), dev_ptr, nbytes);
 }
 
 static int rs_follow_clear(t2d_pool* p) {
@@ -2362,206 +2369,208 @@ int t2d_rs_follow_reset(t2d_pool* p, const uint8_t* mask_dev, void* hip_stream) 
 
 int t2d_rs_follow_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
     if (!p) return T2D_ERR_INVALID;
-    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
-    if (!p->rs_follow_on) return fail(p, T2D_ERR_STATE, "t2d_rs_follow_config must precede t2d_rs_follow_buffers");
-    *records_dev = p->d_rs_follow_rec;
-    *nbytes = (size_t)p->v.n_env * sizeof(t2d_rs_follow_record);
+    return own_records(p, p->rs_follow_on, "t2d_rs_follow_config must precede t2d_rs_follow_buffers", p->d_rs_follow_rec.get(),
+                       (size_t)p->v.n_env * sizeof(t2d_rs_follow_record), records_dev, nbytes);
+}
+
+// ---- scripted action sources: IDM (t2d_idm.hip), lane-keeping PID (t2d_pid.hip), pure pursuit and cruise / ACC (t2d_pursuit.hip)
+// One order for the three setters: validate the host arguments, quiesce, check against the pool's state, stage every new device
+// block in locals, move them in and fill the view.  A call that returns an error has changed nothing in the pool.  n_ctrl == 0
+// uninstalls: quiesce, then the family's clear() -- flags, view and host copy gone, device blocks freed.
+namespace {
+
+constexpr int kCtrlNone = 255;
+static_assert(T2D_IDM_NONE == kCtrlNone && T2D_PID_NONE == kCtrlNone && T2D_PURSUIT_NONE == kCtrlNone, "one 'no controller' id");
+
+// The front of a setter: the arguments against the family's column count, the rows copied densely into `rows` with every row
+// put to check_row(c, row) -- an empty string, or what is wrong with it -- and the range of ctrl_id.
+int ctrl_front(t2d_pool* p, const std::string& who, int cols, const double* ctrl_rows, int n_ctrl, int row_stride, const uint8_t* ctrl_id,
+               std::vector<double>& rows, const std::function<std::string(int, const double*)>& check_row) {
+    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= kCtrlNone || row_stride < cols)
+        return fail(p, T2D_ERR_INVALID, who + ": need 1..254 parameter sets of >= " + std::to_string(cols) +
+                                            " columns and a controller id per participant");
+    rows.resize((size_t)n_ctrl * cols);
+    for (int c = 0; c < n_ctrl; ++c) {
+        const double* r = ctrl_rows + (size_t)c * row_stride;
+        std::copy(r, r + cols, rows.begin() + (size_t)c * cols);
+        const std::string wrong = check_row(c, r);
+        if (!wrong.empty()) return fail(p, T2D_ERR_INVALID, who + ": " + wrong + " (row " + std::to_string(c) + ")");
+    }
+    for (int i = 0; i < p->v.N; ++i)
+        if (ctrl_id[i] != kCtrlNone && ctrl_id[i] >= n_ctrl)
+            return fail(p, T2D_ERR_INVALID, who + ": ctrl_id[" + std::to_string(i) + "] = " + std::to_string((int)ctrl_id[i]) +
+                                                " out of range");
     return T2D_OK;
 }
+
+// A participant has one controller: the first participant of `ctrl_id` that another installed family holds refuses the call.
+int one_controller(t2d_pool* p, const std::string& who, const uint8_t* ctrl_id) {
+    const struct {
+        const char *setter, *name;
+        bool on;
+        const std::vector<uint8_t>& held;
+    } families[] = {{"t2d_set_idm", "IDM", p->idm.on, p->idm.ctrl_host},
+                    {"t2d_set_pid", "PID", p->pid.on, p->pid.ctrl_host},
+                    {"t2d_set_pursuit", "pursuit", p->pursuit.on, p->pursuit.ctrl_host}};
+    for (int i = 0; i < p->v.N; ++i)
+        for (const auto& f : families)
+            if (ctrl_id[i] != kCtrlNone && f.on && who != f.setter && f.held[i] != kCtrlNone)
+                return fail(p, T2D_ERR_INVALID, who + ": participant " + std::to_string(i) + " is " + f.name + "-controlled (" +
+                                                    f.setter + ")");
+    return T2D_OK;
+}
+
+// The gate of t2d_pid_actions / t2d_pursuit_actions.  `lat_rows`: how the family words "a row steers" (null: none installed
+// does); `state_wrong`: the family's own complaint about the pool's state, or null.
+int actions_gate(t2d_pool* p, const std::string& who, const char* setter, bool on, const char* lat_rows, const char* state_wrong,
+                 const float* act_out_dev, const void* record_dev) {
+    if (!on) return fail(p, T2D_ERR_STATE, std::string(setter) + " must precede " + who);
+    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede " + who);
+    if (p->route.kind == 2)
+        return fail(p, T2D_ERR_STATE, who + " follows route sets (t2d_set_routes); trace routes are the installed kind");
+    if (lat_rows && p->route.kind != 1)
+        return fail(p, T2D_ERR_STATE, who + ": a row has " + lat_rows + " and no route set is installed (t2d_set_routes)");
+    if (state_wrong) return fail(p, T2D_ERR_STATE, who + ": " + state_wrong);
+    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, who + ": act_out_dev is required");
+    if (reinterpret_cast<uintptr_t>(record_dev) & 7u) return fail(p, T2D_ERR_INVALID, who + ": record_dev must be 8-byte aligned");
+    return T2D_OK;
+}
+
+}  // namespace
 
 int t2d_set_idm(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id) {
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
-    T2D_HIP(p, quiesce(p));
     if (n_ctrl == 0) {
-        p->idm_on = false;
+        T2D_HIP(p, quiesce(p));   // (nothing in flight reads the blocks any more)
+        const hipError_t e = p->idm.clear();
         refresh_idm_view(p);
+        T2D_HIP(p, e);
         return T2D_OK;
     }
-    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= T2D_IDM_NONE || row_stride < T2D_IDM_COLS)
-        return fail(p, T2D_ERR_INVALID, "t2d_set_idm: need 1..254 parameter sets of >= 8 columns and a controller id per participant");
-    std::vector<double> rows((size_t)n_ctrl * T2D_IDM_COLS);
-    for (int c = 0; c < n_ctrl; ++c) {
-        const double* r = ctrl_rows + (size_t)c * row_stride;
-        for (int k = 0; k < T2D_IDM_COLS; ++k) rows[(size_t)c * T2D_IDM_COLS + k] = r[k];
+    const std::string who = "t2d_set_idm";
+    std::vector<double> rows;
+    int rc = ctrl_front(p, who, T2D_IDM_COLS, ctrl_rows, n_ctrl, row_stride, ctrl_id, rows, [](int, const double* r) -> std::string {
         // idm_controller.py divides by sqrt(max_acceleration * comfortable_deceleration) (:121)
-        if (!(r[T2D_IDM_MAX_ACCEL] * r[T2D_IDM_COMF_DECEL] > 0.0))
-            return fail(p, T2D_ERR_INVALID, "t2d_set_idm: max_acceleration * comfortable_deceleration must be positive (row " +
-                                                std::to_string(c) + ")");
-        if (!(r[T2D_IDM_LANE_HALF_WIDTH] >= 0.0) || !(r[T2D_IDM_HORIZON] > 0.0))
-            return fail(p, T2D_ERR_INVALID, "t2d_set_idm: lane_half_width >= 0 and horizon > 0 required (row " +
-                                                std::to_string(c) + ")");
-    }
-    for (int i = 0; i < p->v.N; ++i)
-        if (ctrl_id[i] != T2D_IDM_NONE && ctrl_id[i] >= n_ctrl)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_idm: ctrl_id[" + std::to_string(i) + "] = " +
-                                                std::to_string((int)ctrl_id[i]) + " out of range");
-    if (p->pid_on)   // (a PID-controlled participant is not an IDM-controlled one: t2d_set_pid)
-        for (int i = 0; i < p->v.N; ++i)
-            if (ctrl_id[i] != T2D_IDM_NONE && p->pid_ctrl_host[i] != T2D_PID_NONE)
-                return fail(p, T2D_ERR_INVALID, "t2d_set_idm: participant " + std::to_string(i) + " is PID-controlled (t2d_set_pid)");
-    if (p->pursuit_on)   // (nor a pursuit-controlled one: t2d_set_pursuit)
-        for (int i = 0; i < p->v.N; ++i)
-            if (ctrl_id[i] != T2D_IDM_NONE && p->pursuit_ctrl_host[i] != T2D_PURSUIT_NONE)
-                return fail(p, T2D_ERR_INVALID, "t2d_set_idm: participant " + std::to_string(i) + " is pursuit-controlled (t2d_set_pursuit)");
-    int rc;
-    if ((rc = dev_replace(p, &p->d_idm_rows, rows.data(), rows.size()))) return rc;
-    if ((rc = dev_replace(p, &p->d_idm_ctrl, ctrl_id, (size_t)p->v.N))) return rc;
-    p->idm.rows = p->d_idm_rows;
-    p->idm.ctrl_id = p->d_idm_ctrl;
-    p->idm.leader = (int32_t*)p->field_ptr[T2D_F_LEADER];
-    p->idm.n_ctrl = n_ctrl;
+        if (!(r[T2D_IDM_MAX_ACCEL] * r[T2D_IDM_COMF_DECEL] > 0.0)) return "max_acceleration * comfortable_deceleration must be positive";
+        if (!(r[T2D_IDM_LANE_HALF_WIDTH] >= 0.0) || !(r[T2D_IDM_HORIZON] > 0.0)) return "lane_half_width >= 0 and horizon > 0 required";
+        return "";
+    });
+    if (rc) return rc;
+    T2D_HIP(p, quiesce(p));
+    if ((rc = one_controller(p, who, ctrl_id))) return rc;
+    const size_t N = (size_t)p->v.N;
+    t2d::IdmFamily f;   // the new family whole; the installed one goes when nothing can fail any more
+    if ((rc = dev_replace(p, &f.d_rows, rows.data(), rows.size()))) return rc;
+    if ((rc = dev_replace(p, &f.d_ctrl, ctrl_id, N))) return rc;
     T2D_HIP(p, hipMemset(p->field_ptr[T2D_F_LEADER], 0xff, p->field_bytes[T2D_F_LEADER]));
-    p->idm_on = true;
+    f.ctrl_host.assign(ctrl_id, ctrl_id + N);
+    f.view = t2d::IdmView{f.d_rows, f.d_ctrl, (int32_t*)p->field_ptr[T2D_F_LEADER], n_ctrl};
+    f.on = true;
+    p->idm = std::move(f);
     refresh_idm_view(p);
     return T2D_OK;
 }
 
 int t2d_idm_actions(t2d_pool* p, const int32_t* forced_leader_dev, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
-    if (!p->idm_on) return fail(p, T2D_ERR_STATE, "t2d_set_idm must precede t2d_idm_actions");
+    if (!p->idm.on) return fail(p, T2D_ERR_STATE, "t2d_set_idm must precede t2d_idm_actions");
     if (!p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_idm_actions");
     return idm_impl(p, (hipStream_t)hip_stream, forced_leader_dev);
 }
 
-// ---- lane-keeping PID controllers (kernel: t2d_pid.hip) --------------------------------------------------------------------
 int t2d_set_pid(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
                 const float* target_speed, const int32_t* idm_row) {
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
     if (n_ctrl == 0) {
-        T2D_HIP(p, quiesce(p));
-        p->pid_on = false;
-        p->pid = t2d::PidView{};
-        p->pid_ctrl_host.clear();
-        p->pid_any_lat = false;
-        p->pid_idm_rows_needed = 0;
+        T2D_HIP(p, quiesce(p));   // (nothing in flight reads the blocks any more)
+        T2D_HIP(p, p->pid.clear());
         return T2D_OK;
     }
-    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= T2D_PID_NONE || row_stride < T2D_PID_COLS)
-        return fail(p, T2D_ERR_INVALID, "t2d_set_pid: need 1..254 parameter sets of >= 14 columns and a controller id per participant");
-    const int N = p->v.N;
-    std::vector<double> rows((size_t)n_ctrl * T2D_PID_COLS);
-    std::vector<int> lon_of(n_ctrl);
+    const std::string who = "t2d_set_pid";
+    std::vector<double> rows;
+    std::vector<int> lon_of;
     bool any_lat = false;
-    for (int c = 0; c < n_ctrl; ++c) {
-        const double* r = ctrl_rows + (size_t)c * row_stride;
-        for (int k = 0; k < T2D_PID_COLS; ++k) rows[(size_t)c * T2D_PID_COLS + k] = r[k];
-        const std::string row = " (row " + std::to_string(c) + ")";
+    int rc = ctrl_front(p, who, T2D_PID_COLS, ctrl_rows, n_ctrl, row_stride, ctrl_id, rows, [&](int, const double* r) -> std::string {
         // pid_controller.py:87-102, comparison by comparison
-        if (r[T2D_PID_DT] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: dt must be positive" + row);
-        if (r[T2D_PID_MAX_STEERING] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_steering must be positive" + row);
-        if (r[T2D_PID_MAX_ACCEL] <= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_accel must be positive" + row);
-        if (r[T2D_PID_MIN_ACCEL] >= 0) return fail(p, T2D_ERR_INVALID, "t2d_set_pid: min_accel must be negative (deceleration)" + row);
-        if (r[T2D_PID_MAX_ACCEL] <= r[T2D_PID_MIN_ACCEL])
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: max_accel must be greater than min_accel" + row);
-        if (r[T2D_PID_ALPHA] <= 0 || r[T2D_PID_ALPHA] > 1)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: derivative_filter_alpha must be in range (0, 1]" + row);
+        if (r[T2D_PID_DT] <= 0) return "dt must be positive";
+        if (r[T2D_PID_MAX_STEERING] <= 0) return "max_steering must be positive";
+        if (r[T2D_PID_MAX_ACCEL] <= 0) return "max_accel must be positive";
+        if (r[T2D_PID_MIN_ACCEL] >= 0) return "min_accel must be negative (deceleration)";
+        if (r[T2D_PID_MAX_ACCEL] <= r[T2D_PID_MIN_ACCEL]) return "max_accel must be greater than min_accel";
+        if (r[T2D_PID_ALPHA] <= 0 || r[T2D_PID_ALPHA] > 1) return "derivative_filter_alpha must be in range (0, 1]";
         const double lat = r[T2D_PID_LAT_MODE], lon = r[T2D_PID_LON_MODE];
         if (!(lat == 0.0 || lat == 1.0 || lat == 2.0) || !(lon == 0.0 || lon == 1.0 || lon == 2.0 || lon == 3.0))
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: lat_mode must be 0, 1 or 2 and lon_mode 0, 1, 2 or 3" + row);
-        lon_of[c] = (int)lon;
+            return "lat_mode must be 0, 1 or 2 and lon_mode 0, 1, 2 or 3";
+        lon_of.push_back((int)lon);
         any_lat = any_lat || lat != 0.0;
-    }
+        return "";
+    });
+    if (rc) return rc;
     T2D_HIP(p, quiesce(p));
-    std::vector<uint8_t> idm_ctrl;
-    if (p->idm_on) {
-        idm_ctrl.resize(N);
-        T2D_HIP(p, hipMemcpy(idm_ctrl.data(), p->d_idm_ctrl, (size_t)N, hipMemcpyDeviceToHost));
-    }
+    if ((rc = one_controller(p, who, ctrl_id))) return rc;
+    const int N = p->v.N;
     std::vector<float> ts(N, 0.f);
+    if (target_speed) ts.assign(target_speed, target_speed + N);
     std::vector<int32_t> irow(N, 0);
     int idm_needed = 0;
     for (int i = 0; i < N; ++i) {
-        if (target_speed) ts[i] = target_speed[i];
-        if (ctrl_id[i] == T2D_PID_NONE) continue;
-        if (ctrl_id[i] >= n_ctrl)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: ctrl_id[" + std::to_string(i) + "] = " + std::to_string((int)ctrl_id[i]) +
-                                                " out of range");
-        if (p->idm_on && idm_ctrl[i] != T2D_IDM_NONE)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: participant " + std::to_string(i) + " is IDM-controlled (t2d_set_idm)");
-        if (p->pursuit_on && p->pursuit_ctrl_host[i] != T2D_PURSUIT_NONE)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pid: participant " + std::to_string(i) + " is pursuit-controlled (t2d_set_pursuit)");
-        if (lon_of[ctrl_id[i]] == 2) {
-            if (!p->idm_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid: lon_mode 2 needs the parameter sets of t2d_set_idm");
-            irow[i] = idm_row ? idm_row[i] : 0;
-            if (irow[i] < 0 || irow[i] >= p->idm.n_ctrl)
-                return fail(p, T2D_ERR_INVALID, "t2d_set_pid: idm_row[" + std::to_string(i) + "] = " + std::to_string(irow[i]) +
-                                                    " outside the installed IDM rows");
-            idm_needed = std::max(idm_needed, irow[i] + 1);
-        }
+        if (ctrl_id[i] == kCtrlNone || lon_of[ctrl_id[i]] != 2) continue;
+        if (!p->idm.on) return fail(p, T2D_ERR_STATE, who + ": lon_mode 2 needs the parameter sets of t2d_set_idm");
+        irow[i] = idm_row ? idm_row[i] : 0;
+        if (irow[i] < 0 || irow[i] >= p->idm.view.n_ctrl)
+            return fail(p, T2D_ERR_INVALID, who + ": idm_row[" + std::to_string(i) + "] = " + std::to_string(irow[i]) +
+                                                " outside the installed IDM rows");
+        idm_needed = std::max(idm_needed, irow[i] + 1);
     }
-    // everything new first, the installed controllers go only when nothing can fail any more
-    t2d::DevBuf<double> d_rows, d_state;
-    t2d::DevBuf<uint8_t> d_ctrl;
-    t2d::DevBuf<float> d_ts;
-    t2d::DevBuf<int32_t> d_irow;
-    t2d::DevBuf<t2d_pid_record> d_rec;
-    int rc;
-    if ((rc = dev_replace(p, &d_rows, rows.data(), rows.size()))) return rc;
-    if ((rc = dev_replace(p, &d_ctrl, ctrl_id, (size_t)N))) return rc;
-    if ((rc = dev_replace(p, &d_ts, ts.data(), (size_t)N))) return rc;
-    if ((rc = dev_replace(p, &d_irow, irow.data(), (size_t)N))) return rc;
-    T2D_HIP(p, d_state.alloc_zeroed((size_t)T2D_PID_STATE_WORDS * N));
-    T2D_HIP(p, d_rec.alloc_zeroed((size_t)N));
-    p->d_pid_rows = std::move(d_rows);
-    p->d_pid_ctrl = std::move(d_ctrl);
-    p->d_pid_target = std::move(d_ts);
-    p->d_pid_idm_row = std::move(d_irow);
-    p->d_pid_state = std::move(d_state);
-    p->d_pid_rec = std::move(d_rec);
-    p->pid_ctrl_host.assign(ctrl_id, ctrl_id + N);
-    p->pid_any_lat = any_lat;
-    p->pid_idm_rows_needed = idm_needed;
-    t2d::PidView& cv = p->pid;
-    cv = t2d::PidView{};
-    cv.rows = p->d_pid_rows;
-    cv.ctrl_id = p->d_pid_ctrl;
-    cv.target_speed = p->d_pid_target;
-    cv.idm_row = p->d_pid_idm_row;
-    cv.state = p->d_pid_state;
-    cv.n_ctrl = n_ctrl;
-    cv.stage_xy = idm_needed > 0;
-    p->pid_on = true;
+    t2d::PidFamily f;   // the new family whole; the installed one goes when nothing can fail any more
+    if ((rc = dev_replace(p, &f.d_rows, rows.data(), rows.size()))) return rc;
+    if ((rc = dev_replace(p, &f.d_ctrl, ctrl_id, (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &f.d_target, ts.data(), (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &f.d_idm_row, irow.data(), (size_t)N))) return rc;
+    T2D_HIP(p, f.d_state.alloc_zeroed((size_t)T2D_PID_STATE_WORDS * N));
+    T2D_HIP(p, f.d_rec.alloc_zeroed((size_t)N));
+    f.ctrl_host.assign(ctrl_id, ctrl_id + N);
+    f.any_lat = any_lat;
+    f.idm_rows_needed = idm_needed;
+    // (idm_rows / n_idm: whatever t2d_set_idm has installed when a call is made -- t2d_pid_actions fills them in)
+    f.view = t2d::PidView{f.d_rows, f.d_ctrl, f.d_target, f.d_idm_row, f.d_state, nullptr, n_ctrl, 0, idm_needed > 0};
+    f.on = true;
+    p->pid = std::move(f);
     return T2D_OK;
 }
 
 int t2d_pid_actions(t2d_pool* p, const float* act_in_dev, float* act_out_dev, t2d_pid_record* record_dev, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
-    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_actions");
-    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_pid_actions");
-    if (p->route.kind == 2)
-        return fail(p, T2D_ERR_STATE, "t2d_pid_actions follows route sets (t2d_set_routes); trace routes are the installed kind");
-    if (p->pid_any_lat && p->route.kind != 1)
-        return fail(p, T2D_ERR_STATE, "t2d_pid_actions: a row has lat_mode != 0 and no route set is installed (t2d_set_routes)");
-    if (p->pid_idm_rows_needed > 0 && (!p->idm_on || p->idm.n_ctrl < p->pid_idm_rows_needed))
-        return fail(p, T2D_ERR_STATE, "t2d_pid_actions: the IDM parameter sets lon_mode 2 was installed against are gone (t2d_set_idm)");
-    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, "t2d_pid_actions: act_out_dev is required");
-    if (reinterpret_cast<uintptr_t>(record_dev) & 7u) return fail(p, T2D_ERR_INVALID, "t2d_pid_actions: record_dev must be 8-byte aligned");
-    t2d::PidView cv = p->pid;
-    cv.idm_rows = p->idm_on ? p->d_idm_rows.get() : nullptr;
-    cv.n_idm = p->idm_on ? p->idm.n_ctrl : 0;
+    const bool rows_gone = p->pid.idm_rows_needed > 0 && (!p->idm.on || p->idm.view.n_ctrl < p->pid.idm_rows_needed);
+    int rc = actions_gate(p, "t2d_pid_actions", "t2d_set_pid", p->pid.on, p->pid.any_lat ? "lat_mode != 0" : nullptr,
+                          rows_gone ? "the IDM parameter sets lon_mode 2 was installed against are gone (t2d_set_idm)" : nullptr,
+                          act_out_dev, record_dev);
+    if (rc) return rc;
+    t2d::PidView cv = p->pid.view;
+    cv.idm_rows = p->idm.on ? p->idm.d_rows.get() : nullptr;
+    cv.n_idm = p->idm.on ? p->idm.view.n_ctrl : 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    int rc;
     touch(p, s);
     if ((rc = record_event(p, T2D_PROFILE_PID, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_pid(p->v, cv, p->route, act_in_dev, act_out_dev, record_dev ? record_dev : p->d_pid_rec.get(), s));
+    T2D_HIP(p, t2d::launch_pid(p->v, cv, p->route, act_in_dev, act_out_dev, record_dev ? record_dev : p->pid.d_rec.get(), s));
     return record_event(p, T2D_PROFILE_PID, s, false);
 }
 
 int t2d_pid_reset(t2d_pool* p, const uint8_t* env_mask_dev, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
-    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_reset");
+    if (!p->pid.on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_reset");
     hipStream_t s = (hipStream_t)hip_stream;
     touch(p, s);
-    T2D_HIP(p, t2d::launch_pid_reset(p->v, p->pid, env_mask_dev, s));
+    T2D_HIP(p, t2d::launch_pid_reset(p->v, p->pid.view, env_mask_dev, s));
     return T2D_OK;
 }
 
 int t2d_pid_state(t2d_pool* p, double* state_host, int32_t write) {
     if (!p) return T2D_ERR_INVALID;
     if (!state_host) return fail(p, T2D_ERR_INVALID, "t2d_pid_state: null array");
-    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_state");
+    if (!p->pid.on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_state");
     T2D_HIP(p, hipSetDevice(p->device));
     T2D_HIP(p, quiesce(p));
     const size_t N = (size_t)p->v.N;
@@ -2569,9 +2578,9 @@ int t2d_pid_state(t2d_pool* p, double* state_host, int32_t write) {
     if (write) {
         for (size_t i = 0; i < N; ++i)
             for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) soa[w * N + i] = state_host[i * T2D_PID_STATE_WORDS + w];
-        T2D_HIP(p, hipMemcpy(p->d_pid_state, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice));
+        T2D_HIP(p, hipMemcpy(p->pid.d_state, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice));
     } else {
-        T2D_HIP(p, hipMemcpy(soa.data(), p->d_pid_state, soa.size() * sizeof(double), hipMemcpyDeviceToHost));
+        T2D_HIP(p, hipMemcpy(soa.data(), p->pid.d_state, soa.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < N; ++i)
             for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) state_host[i * T2D_PID_STATE_WORDS + w] = soa[w * N + i];
     }
@@ -2580,135 +2589,80 @@ int t2d_pid_state(t2d_pool* p, double* state_host, int32_t write) {
 
 int t2d_pid_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
     if (!p) return T2D_ERR_INVALID;
-    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
-    if (!p->pid_on) return fail(p, T2D_ERR_STATE, "t2d_set_pid must precede t2d_pid_buffers");
-    *records_dev = p->d_pid_rec;
-    *nbytes = (size_t)p->v.N * sizeof(t2d_pid_record);
-    return T2D_OK;
+    return own_records(p, p->pid.on, "t2d_set_pid must precede t2d_pid_buffers", p->pid.d_rec.get(),
+                       (size_t)p->v.N * sizeof(t2d_pid_record), records_dev, nbytes);
 }
 
-// ---- pure pursuit and cruise / ACC controllers (kernel: t2d_pursuit.hip) ---------------------------------------------------
 int t2d_set_pursuit(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_t row_stride, const uint8_t* ctrl_id,
                     const float* target_speed) {
     if (!p) return T2D_ERR_INVALID;
     T2D_HIP(p, hipSetDevice(p->device));
     if (n_ctrl == 0) {
-        T2D_HIP(p, quiesce(p));
-        p->pursuit_on = false;
-        p->pursuit = t2d::PursuitView{};
-        p->pursuit_ctrl_host.clear();
-        // (quiesced above: nothing in flight reads them any more)
-        T2D_HIP(p, p->d_pursuit_rows.reset());
-        T2D_HIP(p, p->d_pursuit_ctrl.reset());
-        T2D_HIP(p, p->d_pursuit_target.reset());
-        T2D_HIP(p, p->d_pursuit_rec.reset());
-        p->pursuit_any_lat = p->pursuit_any_last = false;
+        T2D_HIP(p, quiesce(p));   // (nothing in flight reads the blocks any more)
+        T2D_HIP(p, p->pursuit.clear());
         return T2D_OK;
     }
-    if (!ctrl_rows || !ctrl_id || n_ctrl < 0 || n_ctrl >= T2D_PURSUIT_NONE || row_stride < T2D_PURSUIT_COLS)
-        return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: need 1..254 parameter sets of >= 13 columns and a controller id per participant");
-    const int N = p->v.N;
-    std::vector<double> rows((size_t)n_ctrl * T2D_PURSUIT_COLS);
+    const std::string who = "t2d_set_pursuit";
+    std::vector<double> rows;
+    std::vector<int> lon_of;
     bool any_lat = false, any_acc = false, any_last = false;
-    std::vector<int> lon_of(n_ctrl);
-    for (int c = 0; c < n_ctrl; ++c) {
-        const double* r = ctrl_rows + (size_t)c * row_stride;
-        const std::string row = " (row " + std::to_string(c) + ")";
+    int rc = ctrl_front(p, who, T2D_PURSUIT_COLS, ctrl_rows, n_ctrl, row_stride, ctrl_id, rows, [&](int, const double* r) -> std::string {
         for (int k = 0; k < T2D_PURSUIT_COLS; ++k) {
-            rows[(size_t)c * T2D_PURSUIT_COLS + k] = r[k];
             const bool may = (k == T2D_PURSUIT_WHEEL_BASE && r[k] != r[k]) || (k == T2D_PURSUIT_HORIZON && r[k] == HUGE_VAL);
-            if (!std::isfinite(r[k]) && !may)
-                return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: column " + std::to_string(k) + " is not finite" + row);
+            if (!std::isfinite(r[k]) && !may) return "column " + std::to_string(k) + " is not finite";
         }
         // pure_pursuit_controller.py:31-32
-        if (r[T2D_PURSUIT_MIN_PRE_AIMING] <= 0)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: min_pre_aiming_distance must be positive" + row);
+        if (r[T2D_PURSUIT_MIN_PRE_AIMING] <= 0) return "min_pre_aiming_distance must be positive";
         const double lat = r[T2D_PURSUIT_LAT_MODE], lon = r[T2D_PURSUIT_LON_MODE];
-        if (!(lat == 0.0 || lat == 1.0) || !(lon == 0.0 || lon == 1.0 || lon == 2.0))
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: lat_mode must be 0 or 1 and lon_mode 0, 1 or 2" + row);
-        lon_of[c] = (int)lon;
+        if (!(lat == 0.0 || lat == 1.0) || !(lon == 0.0 || lon == 1.0 || lon == 2.0)) return "lat_mode must be 0 or 1 and lon_mode 0, 1 or 2";
+        lon_of.push_back((int)lon);
         any_lat = any_lat || lat == 1.0;
         any_acc = any_acc || lon == 1.0;
         any_last = any_last || lon != 2.0;
-    }
-    T2D_HIP(p, quiesce(p));
-    std::vector<uint8_t> idm_ctrl;
-    if (p->idm_on) {
-        idm_ctrl.resize(N);
-        T2D_HIP(p, hipMemcpy(idm_ctrl.data(), p->d_idm_ctrl, (size_t)N, hipMemcpyDeviceToHost));
-    }
+        return "";
+    });
+    if (rc) return rc;
+    const int N = p->v.N;
     std::vector<float> ts(N, 0.f);
-    for (int i = 0; i < N; ++i) {
-        if (target_speed) ts[i] = target_speed[i];
-        if (ctrl_id[i] == T2D_PURSUIT_NONE) continue;
-        if (ctrl_id[i] >= n_ctrl)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: ctrl_id[" + std::to_string(i) + "] = " +
-                                                std::to_string((int)ctrl_id[i]) + " out of range");
-        // acceleration_controller.py:46-47 (the caller's acceleration needs no target speed)
-        if (lon_of[ctrl_id[i]] != 2 && !(ts[i] >= 0))
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: target_speed[" + std::to_string(i) + "] must be non-negative");
-        if (p->idm_on && idm_ctrl[i] != T2D_IDM_NONE)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: participant " + std::to_string(i) + " is IDM-controlled (t2d_set_idm)");
-        if (p->pid_on && p->pid_ctrl_host[i] != T2D_PID_NONE)
-            return fail(p, T2D_ERR_INVALID, "t2d_set_pursuit: participant " + std::to_string(i) + " is PID-controlled (t2d_set_pid)");
-    }
-    // everything new first, the installed controllers go only when nothing can fail any more
-    t2d::DevBuf<double> d_rows;
-    t2d::DevBuf<uint8_t> d_ctrl;
-    t2d::DevBuf<float> d_ts;
-    t2d::DevBuf<t2d_pursuit_record> d_rec;
-    int rc;
-    if ((rc = dev_replace(p, &d_rows, rows.data(), rows.size()))) return rc;
-    if ((rc = dev_replace(p, &d_ctrl, ctrl_id, (size_t)N))) return rc;
-    if ((rc = dev_replace(p, &d_ts, ts.data(), (size_t)N))) return rc;
-    T2D_HIP(p, d_rec.alloc_zeroed((size_t)N));
-    p->d_pursuit_rows = std::move(d_rows);
-    p->d_pursuit_ctrl = std::move(d_ctrl);
-    p->d_pursuit_target = std::move(d_ts);
-    p->d_pursuit_rec = std::move(d_rec);
-    p->pursuit_ctrl_host.assign(ctrl_id, ctrl_id + N);
-    p->pursuit_any_lat = any_lat;
-    p->pursuit_any_last = any_last;
-    t2d::PursuitView& cv = p->pursuit;
-    cv = t2d::PursuitView{};
-    cv.rows = p->d_pursuit_rows;
-    cv.ctrl_id = p->d_pursuit_ctrl;
-    cv.target_speed = p->d_pursuit_target;
-    cv.n_ctrl = n_ctrl;
-    cv.stage_xy = any_acc;
-    p->pursuit_on = true;
+    if (target_speed) ts.assign(target_speed, target_speed + N);
+    for (int i = 0; i < N; ++i)   // acceleration_controller.py:46-47 (the caller's acceleration needs no target speed)
+        if (ctrl_id[i] != kCtrlNone && lon_of[ctrl_id[i]] != 2 && !(ts[i] >= 0))
+            return fail(p, T2D_ERR_INVALID, who + ": target_speed[" + std::to_string(i) + "] must be non-negative");
+    T2D_HIP(p, quiesce(p));
+    if ((rc = one_controller(p, who, ctrl_id))) return rc;
+    t2d::PursuitFamily f;   // the new family whole; the installed one goes when nothing can fail any more
+    if ((rc = dev_replace(p, &f.d_rows, rows.data(), rows.size()))) return rc;
+    if ((rc = dev_replace(p, &f.d_ctrl, ctrl_id, (size_t)N))) return rc;
+    if ((rc = dev_replace(p, &f.d_target, ts.data(), (size_t)N))) return rc;
+    T2D_HIP(p, f.d_rec.alloc_zeroed((size_t)N));
+    f.ctrl_host.assign(ctrl_id, ctrl_id + N);
+    f.any_lat = any_lat;
+    f.any_last = any_last;
+    f.view = t2d::PursuitView{f.d_rows, f.d_ctrl, f.d_target, n_ctrl, any_acc};
+    f.on = true;
+    p->pursuit = std::move(f);
     return T2D_OK;
 }
 
 int t2d_pursuit_actions(t2d_pool* p, const float* act_in_dev, float* act_out_dev, t2d_pursuit_record* record_dev, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
-    if (!p->pursuit_on) return fail(p, T2D_ERR_STATE, "t2d_set_pursuit must precede t2d_pursuit_actions");
-    if (!p->have_params || !p->have_reset) return fail(p, T2D_ERR_STATE, "t2d_reset must precede t2d_pursuit_actions");
-    if (p->route.kind == 2)
-        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions follows route sets (t2d_set_routes); trace routes are the installed kind");
-    if (p->pursuit_any_lat && p->route.kind != 1)
-        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions: a row has lat_mode 1 and no route set is installed (t2d_set_routes)");
-    if (p->pursuit_any_last && !(p->v.out_mask & T2D_OUT_APPLIED))
-        return fail(p, T2D_ERR_STATE, "t2d_pursuit_actions: cruise / ACC read T2D_F_APPLIED0, which t2d_set_outputs switched off");
-    if (!act_out_dev) return fail(p, T2D_ERR_INVALID, "t2d_pursuit_actions: act_out_dev is required");
-    if (reinterpret_cast<uintptr_t>(record_dev) & 7u)
-        return fail(p, T2D_ERR_INVALID, "t2d_pursuit_actions: record_dev must be 8-byte aligned");
+    const bool no_last = p->pursuit.any_last && !(p->v.out_mask & T2D_OUT_APPLIED);
+    int rc = actions_gate(p, "t2d_pursuit_actions", "t2d_set_pursuit", p->pursuit.on, p->pursuit.any_lat ? "lat_mode 1" : nullptr,
+                          no_last ? "cruise / ACC read T2D_F_APPLIED0, which t2d_set_outputs switched off" : nullptr, act_out_dev,
+                          record_dev);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    int rc;
     touch(p, s);
     if ((rc = record_event(p, T2D_PROFILE_PURSUIT, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_pursuit(p->v, p->pursuit, p->route, act_in_dev, act_out_dev,
-                                   record_dev ? record_dev : p->d_pursuit_rec.get(), s));
+    T2D_HIP(p, t2d::launch_pursuit(p->v, p->pursuit.view, p->route, act_in_dev, act_out_dev,
+                                   record_dev ? record_dev : p->pursuit.d_rec.get(), s));
     return record_event(p, T2D_PROFILE_PURSUIT, s, false);
 }
 
 int t2d_pursuit_buffers(t2d_pool* p, void** records_dev, size_t* nbytes) {
     if (!p) return T2D_ERR_INVALID;
-    if (!records_dev || !nbytes) return fail(p, T2D_ERR_INVALID, "null output");
-    if (!p->pursuit_on) return fail(p, T2D_ERR_STATE, "t2d_set_pursuit must precede t2d_pursuit_buffers");
-    *records_dev = p->d_pursuit_rec;
-    *nbytes = (size_t)p->v.N * sizeof(t2d_pursuit_record);
-    return T2D_OK;
+    return own_records(p, p->pursuit.on, "t2d_set_pursuit must precede t2d_pursuit_buffers", p->pursuit.d_rec.get(),
+                       (size_t)p->v.N * sizeof(t2d_pursuit_record), records_dev, nbytes);
 }
 
 int t2d_verify_state(t2d_pool* p, const float* x_dev, const float* y_dev, const float* heading_dev,

@@ -9,21 +9,19 @@
 // The reference leaves cross_track_error / target_heading / target_speed to its caller and ships no caller: the measurement
 // against the installed route is BUILD-DEFINED (include/t2d.h states it, tests/pid_ref.py restates it in numpy).
 //
-// One workgroup per env, one lane per participant (max_agents rounded up to whole waves).  The env's route set is staged in
-// LDS exactly as off_route_set_kernel stages it (fp32 pairs behind the set's route offsets, widened on read): lanes on the same
-// route read the same address in the same iteration (one broadcast 8-byte read).  When a row uses the IDM law the env's (x, y)
-// go through LDS as fp64 pairs, NaN = inactive -- idm_kernel's scheme -- for find_leader.  fp64 in registers, plain vector
+// One workgroup per env, one lane per participant (scripted_launch, t2d_scripted_dev.h).  The env's route set is staged in LDS
+// by stage_route_set (fp32 pairs behind the set's route offsets, widened on read): lanes on the same route read the same
+// address in the same iteration (one broadcast 8-byte read).  The lane's participant, the caller's row and the wheel-base
+// fallback are that header's too (scripted_lane, action_row_in / _out, wheel_base_or_type).  When a row uses the IDM law the
+// env's (x, y) go through LDS as fp64 pairs, NaN = inactive (scripted_xy) -- idm_kernel's scheme -- for find_leader.  fp64 in registers, plain vector
 // stores, no atomics, no cross-lane traffic.  State: six fp64 words per participant, struct-of-arrays.
-#include <algorithm>
-
 #include "t2d_idm_dev.h"
 #include "t2d_route_dev.h"
+#include "t2d_scripted_dev.h"
 
 namespace t2d {
 
 namespace {
-
-constexpr int kPidBlock = 256;
 
 // _compute_pid: `integral / prev_error / prev_der` in, the state AFTER the call out; limits = (lo, hi) when LIMITS
 template <bool LIMITS>
@@ -56,49 +54,31 @@ T2D_DEV double pid_compute(double error, double& integral, double& prev_error, d
 
 // grid = n_env, block = max_agents rounded up to whole waves; dynamic LDS = RouteView::lds_bytes (route sets installed):
 //   float2 verts[nv] | int32 first_vertex[nr + 1]   of the env's set (nv <= T2D_MAX_ROUTE_SET_VERTS)
-__global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv, RouteView rv, const uint32_t* act_in, uint32_t* act_out,
+__global__ __launch_bounds__(kScriptedBlock) void pid_kernel(PoolView pv, PidView cv, RouteView rv, const uint32_t* act_in, uint32_t* act_out,
                                                         t2d_pid_record* out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pid_lds[];
-    __shared__ double2 s_xy[kPidBlock];
-    __shared__ float s_v[kPidBlock];
+    __shared__ double2 s_xy[kScriptedBlock];
+    __shared__ float s_v[kScriptedBlock];
     const int e = blockIdx.x, a = threadIdx.x;
-    const float2* lv = reinterpret_cast<const float2*>(pid_lds);
-    const int32_t* lo = nullptr;
-    if (rv.kind == 1) {
-        const int s = rv.set_of_env[e];
-        const int r0 = rv.set_route_start[s], nr = rv.set_route_start[s + 1] - r0;
-        const int v0 = rv.route_vert_off[r0], nv = rv.route_vert_off[r0 + nr] - v0;
-        float2* wv = reinterpret_cast<float2*>(pid_lds);
-        int32_t* wo = reinterpret_cast<int32_t*>(pid_lds + (size_t)nv * sizeof(float2));
-        const float2* gv = reinterpret_cast<const float2*>(rv.verts) + v0;
-        for (int k = a; k < nv; k += blockDim.x) wv[k] = gv[k];
-        for (int k = a; k <= nr; k += blockDim.x) wo[k] = rv.route_vert_off[r0 + k] - v0;
-        lo = wo;
-    }
-    const bool valid = a < pv.A;
-    const int i = e * pv.A + (valid ? a : 0);
+    StagedRoutes routes{reinterpret_cast<const float2*>(pid_lds), nullptr};
+    if (rv.kind == 1) routes = stage_route_set(pid_lds, rv, e);
+    const float2* lv = routes.verts;
+    const int32_t* lo = routes.first;
+    const ScriptedLane ln = scripted_lane(pv, cv.ctrl_id, e, a);
+    const bool active = ln.active;
+    const int i = ln.i, ctrl = ln.ctrl;
+    const uint32_t ids = ln.ids;
+    const float fx = ln.x, fy = ln.y, fh = ln.heading, fv = ln.speed;
     const double qnan = __builtin_nan("");
-    uint32_t ids = 0;
-    float fx = 0, fy = 0, fh = 0, fv = 0;
-    int ctrl = T2D_PID_NONE;
-    if (valid) {
-        ids = pv.ids[i];
-        fx = pv.x[i];
-        fy = pv.y[i];
-        fh = pv.heading[i];
-        fv = pv.speed[i];
-        ctrl = cv.ctrl_id[i];
-    }
-    const bool active = valid && ((ids >> kIdsActiveShift) & 0xffu);
     if (cv.stage_xy) {
-        s_xy[a] = active ? make_double2((double)fx, (double)fy) : make_double2(qnan, qnan);
+        s_xy[a] = scripted_xy(ln);
         s_v[a] = fv;
     }
     __syncthreads();
-    if (!valid) return;
+    if (!ln.valid) return;
 
-    const uint32_t in0 = act_in ? act_in[2 * (size_t)i] : 0u, in1 = act_in ? act_in[2 * (size_t)i + 1] : 0u;
-    uint32_t o0 = in0, o1 = in1;
+    const ActionRow in = action_row_in(act_in, i);
+    ActionRow o = in;
     t2d_pid_record r;
     r.cross_track = qnan;
     r.lat_error = qnan;
@@ -169,11 +149,7 @@ __global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv,
                                                               dt, alpha, 0.0, 0.0, sat);
                     const double ms = c[T2D_PID_MAX_STEERING];
                     if (lat_mode == 2) {
-                        double wb = c[T2D_PID_WHEEL_BASE];
-                        if (wb != wb) {
-                            const int type = (ids >> kIdsTypeShift) & 0xff;
-                            wb = pv.params[T2D_P_LF * T2D_MAX_TYPES + type] + pv.params[T2D_P_LR * T2D_MAX_TYPES + type];
-                        }
+                        const double wb = wheel_base_or_type(c[T2D_PID_WHEEL_BASE], pv, ids);
                         if (wb <= 0.0) r.events |= T2D_PID_BAD_WHEEL_BASE;   // (the state above is updated all the same)
                         else steering = clipd(lat_out * (2.0 / wb), -ms, ms);
                     } else {
@@ -208,7 +184,7 @@ __global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv,
                     r.leader = lead;
                 }
             } else if (lon_mode == 3) {
-                accel = (double)__uint_as_float(in1);
+                accel = (double)__uint_as_float(in.w1);
             }
             // ---- commit
             if (__builtin_isfinite(steering) && __builtin_isfinite(accel)) {
@@ -216,8 +192,7 @@ __global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv,
                 for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) S[w] = T[w];
                 r.action[0] = steering;
                 r.action[1] = accel;
-                o0 = __float_as_uint((float)steering);
-                o1 = __float_as_uint((float)accel);
+                o = {__float_as_uint((float)steering), __float_as_uint((float)accel)};
             } else {
                 r.events |= T2D_PID_NONFINITE;
             }
@@ -226,12 +201,11 @@ __global__ __launch_bounds__(kPidBlock) void pid_kernel(PoolView pv, PidView cv,
         for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) cv.state[w * N + i] = S[w];
     }
     out[i] = r;
-    act_out[2 * (size_t)i] = o0;
-    act_out[2 * (size_t)i + 1] = o1;
+    action_row_out(act_out, i, o);
 }
 
-__global__ __launch_bounds__(kPidBlock) void pid_reset_kernel(int N, int A, PidView cv, const uint8_t* mask) {
-    const int i = blockIdx.x * kPidBlock + threadIdx.x;
+__global__ __launch_bounds__(kScriptedBlock) void pid_reset_kernel(int N, int A, PidView cv, const uint8_t* mask) {
+    const int i = blockIdx.x * kScriptedBlock + threadIdx.x;
     if (i >= N || (mask && !mask[i / A])) return;
 #pragma unroll
     for (int w = 0; w < T2D_PID_STATE_WORDS; ++w) cv.state[(size_t)w * N + i] = 0.0;
@@ -241,15 +215,14 @@ __global__ __launch_bounds__(kPidBlock) void pid_reset_kernel(int N, int A, PidV
 
 hipError_t launch_pid(const PoolView& v, const PidView& cv, const RouteView& rv, const float* act_in, float* act_out,
                       t2d_pid_record* out, hipStream_t s) {
-    const int block = std::min(kPidBlock, (v.A + 63) & ~63);
-    const size_t lds = rv.kind == 1 ? (size_t)rv.lds_bytes : 0;
-    hipLaunchKernelGGL(pid_kernel, dim3(v.n_env), dim3(block), lds, s, v, cv, rv, reinterpret_cast<const uint32_t*>(act_in),
+    const ScriptedLaunch l = scripted_launch(v, rv);
+    hipLaunchKernelGGL(pid_kernel, dim3(v.n_env), dim3(l.block), l.lds, s, v, cv, rv, reinterpret_cast<const uint32_t*>(act_in),
                        reinterpret_cast<uint32_t*>(act_out), out);
     return hipGetLastError();
 }
 
 hipError_t launch_pid_reset(const PoolView& v, const PidView& cv, const uint8_t* mask, hipStream_t s) {
-    hipLaunchKernelGGL(pid_reset_kernel, dim3((v.N + kPidBlock - 1) / kPidBlock), dim3(kPidBlock), 0, s, v.N, v.A, cv, mask);
+    hipLaunchKernelGGL(pid_reset_kernel, dim3((v.N + kScriptedBlock - 1) / kScriptedBlock), dim3(kScriptedBlock), 0, s, v.N, v.A, cv, mask);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -367,6 +368,64 @@ struct PursuitView {
     int32_t stage_xy;            // some row has lon_mode 1: the env's (x, y, speed, applied accel) go through LDS for the leader
 };
 
+// What one family of scripted action sources keeps in the pool: whether it is installed, the view its launch takes, the owners
+// the view borrows from, the host's copy of the assignment (the one-controller-per-participant rule reads it) and what the
+// installed rows imply for a call.  clear() is the uninstall: flags and view back to nothing, every block freed.
+inline hipError_t first_error(std::initializer_list<hipError_t> es) {
+    for (hipError_t e : es)
+        if (e != hipSuccess) return e;
+    return hipSuccess;
+}
+struct IdmFamily {
+    bool on = false;
+    IdmView view{};
+    DevBuf<double> d_rows;
+    DevBuf<uint8_t> d_ctrl;
+    std::vector<uint8_t> ctrl_host;
+    hipError_t clear() {
+        on = false;
+        view = IdmView{};
+        ctrl_host.clear();
+        return first_error({d_rows.reset(), d_ctrl.reset()});
+    }
+};
+struct PidFamily {
+    bool on = false;
+    PidView view{};
+    DevBuf<double> d_rows, d_state;
+    DevBuf<uint8_t> d_ctrl;
+    DevBuf<float> d_target;
+    DevBuf<int32_t> d_idm_row;
+    DevBuf<t2d_pid_record> d_rec;   // the pool's own records (a NULL record_dev)
+    std::vector<uint8_t> ctrl_host;
+    bool any_lat = false;           // some installed row has lat_mode != 0: a call needs route sets
+    int idm_rows_needed = 0;        // lon_mode 2: 1 + the largest idm_row in use (0: no such participant)
+    hipError_t clear() {
+        on = any_lat = false;
+        idm_rows_needed = 0;
+        view = PidView{};
+        ctrl_host.clear();
+        return first_error({d_rows.reset(), d_state.reset(), d_ctrl.reset(), d_target.reset(), d_idm_row.reset(), d_rec.reset()});
+    }
+};
+struct PursuitFamily {
+    bool on = false;
+    PursuitView view{};
+    DevBuf<double> d_rows;
+    DevBuf<uint8_t> d_ctrl;
+    DevBuf<float> d_target;
+    DevBuf<t2d_pursuit_record> d_rec;   // the pool's own records (a NULL record_dev)
+    std::vector<uint8_t> ctrl_host;
+    bool any_lat = false;    // some installed row has lat_mode 1: a call needs route sets
+    bool any_last = false;   // some installed row has lon_mode 0 / 1: a call reads T2D_F_APPLIED0 (T2D_OUT_APPLIED)
+    hipError_t clear() {
+        on = any_lat = any_last = false;
+        view = PursuitView{};
+        ctrl_host.clear();
+        return first_error({d_rows.reset(), d_ctrl.reset(), d_target.reset(), d_rec.reset()});
+    }
+};
+
 constexpr int kIdsModelShift = 0;
 constexpr int kIdsTypeShift = 8;
 constexpr int kIdsActiveShift = 16;
@@ -388,7 +447,9 @@ struct t2d_pool {
     std::string err;
     double host_params[T2D_MAX_TYPES][T2D_PARAM_COLS]{};
     // Ownership: every DevBuf / PinBuf member below owns its block and frees it when the pool is deleted (or when a setter
-    // resets / replaces it); the view structs next to them hold plain pointers borrowed from these owners.
+    // resets / replaces it); the view structs next to them hold plain pointers borrowed from these owners.  The scripted
+    // action sources keep theirs together (IdmFamily / PidFamily / PursuitFamily): their setters stage new blocks in locals
+    // and move them in when nothing can fail any more, and an uninstall frees them (clear()).
     t2d::DevBuf<> field_buf[T2D_F_COUNT];
     void* field_ptr[T2D_F_COUNT]{};   // t2d_get_field's lookup table: field_buf[f].get()
     size_t field_bytes[T2D_F_COUNT]{};
@@ -472,11 +533,10 @@ struct t2d_pool {
     long long geo_gen = 0, cam_geo_gen = -1;
     bool cam_type_default = true;   // class_of_type follows the parameter table's shapes
     t2d::DevBuf<float> d_snap_omega[2];
-    // IDM agents (row f3)
-    bool idm_on = false;
-    t2d::IdmView idm{};
-    t2d::DevBuf<double> d_idm_rows;
-    t2d::DevBuf<uint8_t> d_idm_ctrl;
+    // scripted action sources (t2d_set_idm / t2d_set_pid / t2d_set_pursuit; the structs above)
+    t2d::IdmFamily idm;
+    t2d::PidFamily pid;
+    t2d::PursuitFamily pursuit;
     t2d::DevBuf<float> d_snap[6];     // x, y, heading, speed, vx, vy at episode start
     t2d::DevBuf<uint32_t> d_snap_ids;
     t2d::DevBuf<uint32_t> d_wgmap;   // step-launch placement (t2d_debug_set_step_placement)
@@ -560,29 +620,6 @@ struct t2d_pool {
     t2d::DevBuf<double> d_rs_follow_f64;     // what rs_follow.f64 / .i32 borrow
     t2d::DevBuf<int32_t> d_rs_follow_i32;
     t2d::DevBuf<t2d_rs_follow_record> d_rs_follow_rec;
-    // lane-keeping PID controllers (t2d_set_pid): the view, what it borrows, the pool's own records and the host's copy of the
-    // assignment (t2d_set_idm checks new IDM assignments against it)
-    bool pid_on = false;
-    t2d::PidView pid{};
-    t2d::DevBuf<double> d_pid_rows, d_pid_state;
-    t2d::DevBuf<uint8_t> d_pid_ctrl;
-    t2d::DevBuf<float> d_pid_target;
-    t2d::DevBuf<int32_t> d_pid_idm_row;
-    t2d::DevBuf<t2d_pid_record> d_pid_rec;
-    std::vector<uint8_t> pid_ctrl_host;
-    bool pid_any_lat = false;        // some installed row has lat_mode != 0: a call needs route sets
-    int pid_idm_rows_needed = 0;     // lon_mode 2: 1 + the largest idm_row in use (0: no such participant)
-    // pure pursuit and cruise / ACC controllers (t2d_set_pursuit): the view, what it borrows, the pool's own records and the
-    // host's copy of the assignment (t2d_set_idm / t2d_set_pid check new assignments against it)
-    bool pursuit_on = false;
-    t2d::PursuitView pursuit{};
-    t2d::DevBuf<double> d_pursuit_rows;
-    t2d::DevBuf<uint8_t> d_pursuit_ctrl;
-    t2d::DevBuf<float> d_pursuit_target;
-    t2d::DevBuf<t2d_pursuit_record> d_pursuit_rec;
-    std::vector<uint8_t> pursuit_ctrl_host;
-    bool pursuit_any_lat = false;    // some installed row has lat_mode 1: a call needs route sets
-    bool pursuit_any_last = false;   // some installed row has lon_mode 0 / 1: a call reads T2D_F_APPLIED0 (T2D_OUT_APPLIED)
     // profiling
     t2d::DevBuf<unsigned long long> d_dbg;   // what v.dbg borrows (-DT2D_TIMING builds)
     bool profiling = false;

@@ -12,21 +12,19 @@
 // that is stays BUILD-DEFINED here: the rest of the installed route from the participant's projection onward (include/t2d.h
 // states the walk, tests/pursuit_ref.py restates it in numpy).
 //
-// pid_kernel's shape: one workgroup per env, one lane per participant (max_agents rounded up to whole waves); the env's route
-// set staged in LDS as fp32 pairs behind the set's route offsets; the projection is route_measure (t2d_route_dev.h), the one
-// pid_kernel runs.  When a row uses ACC the env's (x, y) go through LDS as fp64 pairs, NaN = inactive, beside its speed and
-// applied acceleration, for idm::find_leader.  The walk is a per-lane loop over LDS of data-dependent length, bounded by the
+// Built from t2d_scripted_dev.h, as pid_kernel is: one workgroup per env, one lane per participant (scripted_launch); the env's
+// route set staged in LDS by stage_route_set; the lane's participant, the caller's row and the wheel-base fallback from
+// scripted_lane, action_row_in / _out and wheel_base_or_type; the projection is route_measure (t2d_route_dev.h), the one
+// pid_kernel runs.  Its own: the lane's T2D_F_APPLIED0, and when a row uses ACC the env's (x, y) through LDS as fp64 pairs
+// (scripted_xy: NaN = inactive) beside its speed and applied acceleration, for idm::find_leader.  The walk is a per-lane loop over LDS of data-dependent length, bounded by the
 // route's segment count.  fp64 in registers, plain vector stores, no atomics, no cross-lane traffic, no state.
-#include <algorithm>
-
 #include "t2d_idm_dev.h"
 #include "t2d_route_dev.h"
+#include "t2d_scripted_dev.h"
 
 namespace t2d {
 
 namespace {
-
-constexpr int kPursuitBlock = 256;
 
 // the two clips both acceleration laws end with (acceleration_controller.py:86-91, :117-122)
 T2D_DEV double accel_clips(double accel, double accel_last, const double* c) {
@@ -37,50 +35,31 @@ T2D_DEV double accel_clips(double accel, double accel_last, const double* c) {
 
 // grid = n_env, block = max_agents rounded up to whole waves; dynamic LDS = RouteView::lds_bytes (route sets installed):
 //   float2 verts[nv] | int32 first_vertex[nr + 1]   of the env's set (nv <= T2D_MAX_ROUTE_SET_VERTS)
-__global__ __launch_bounds__(kPursuitBlock) void pursuit_kernel(PoolView pv, PursuitView cv, RouteView rv, const uint32_t* act_in,
+__global__ __launch_bounds__(kScriptedBlock) void pursuit_kernel(PoolView pv, PursuitView cv, RouteView rv, const uint32_t* act_in,
                                                                 uint32_t* act_out, t2d_pursuit_record* out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pursuit_lds[];
-    __shared__ double2 s_xy[kPursuitBlock];
-    __shared__ float2 s_va[kPursuitBlock];   // (speed, applied acceleration)
+    __shared__ double2 s_xy[kScriptedBlock];
+    __shared__ float2 s_va[kScriptedBlock];   // (speed, applied acceleration)
     const int e = blockIdx.x, a = threadIdx.x;
-    const float2* lv = reinterpret_cast<const float2*>(pursuit_lds);
-    const int32_t* lo = nullptr;
-    if (rv.kind == 1) {
-        const int s = rv.set_of_env[e];
-        const int r0 = rv.set_route_start[s], nr = rv.set_route_start[s + 1] - r0;
-        const int v0 = rv.route_vert_off[r0], nv = rv.route_vert_off[r0 + nr] - v0;
-        float2* wv = reinterpret_cast<float2*>(pursuit_lds);
-        int32_t* wo = reinterpret_cast<int32_t*>(pursuit_lds + (size_t)nv * sizeof(float2));
-        const float2* gv = reinterpret_cast<const float2*>(rv.verts) + v0;
-        for (int k = a; k < nv; k += blockDim.x) wv[k] = gv[k];
-        for (int k = a; k <= nr; k += blockDim.x) wo[k] = rv.route_vert_off[r0 + k] - v0;
-        lo = wo;
-    }
-    const bool valid = a < pv.A;
-    const int i = e * pv.A + (valid ? a : 0);
+    StagedRoutes routes{reinterpret_cast<const float2*>(pursuit_lds), nullptr};
+    if (rv.kind == 1) routes = stage_route_set(pursuit_lds, rv, e);
+    const float2* lv = routes.verts;
+    const int32_t* lo = routes.first;
+    const ScriptedLane ln = scripted_lane<true>(pv, cv.ctrl_id, e, a, pv.applied0);   // (+ the acceleration the last step applied)
+    const bool active = ln.active;
+    const int i = ln.i, ctrl = ln.ctrl;
+    const uint32_t ids = ln.ids;
+    const float fx = ln.x, fy = ln.y, fh = ln.heading, fv = ln.speed, fa = ln.also;
     const double qnan = __builtin_nan("");
-    uint32_t ids = 0;
-    float fx = 0, fy = 0, fh = 0, fv = 0, fa = 0;
-    int ctrl = T2D_PURSUIT_NONE;
-    if (valid) {
-        ids = pv.ids[i];
-        fx = pv.x[i];
-        fy = pv.y[i];
-        fh = pv.heading[i];
-        fv = pv.speed[i];
-        fa = pv.applied0[i];
-        ctrl = cv.ctrl_id[i];
-    }
-    const bool active = valid && ((ids >> kIdsActiveShift) & 0xffu);
     if (cv.stage_xy) {
-        s_xy[a] = active ? make_double2((double)fx, (double)fy) : make_double2(qnan, qnan);
+        s_xy[a] = scripted_xy(ln);
         s_va[a] = make_float2(fv, fa);
     }
     __syncthreads();
-    if (!valid) return;
+    if (!ln.valid) return;
 
-    const uint32_t in0 = act_in ? act_in[2 * (size_t)i] : 0u, in1 = act_in ? act_in[2 * (size_t)i + 1] : 0u;
-    uint32_t o0 = in0, o1 = in1;
+    const ActionRow in = action_row_in(act_in, i);
+    ActionRow o = in;
     t2d_pursuit_record r;
     r.point[0] = r.point[1] = qnan;
     r.pre_aiming_distance = qnan;
@@ -169,11 +148,7 @@ __global__ __launch_bounds__(kPursuitBlock) void pursuit_kernel(PoolView pv, Pur
                     r.point[1] = ty;
                     r.target_segment = tseg;
                     // _lateral_control
-                    double wb = c[T2D_PURSUIT_WHEEL_BASE];
-                    if (wb != wb) {
-                        const int type = (ids >> kIdsTypeShift) & 0xff;
-                        wb = pv.params[T2D_P_LF * T2D_MAX_TYPES + type] + pv.params[T2D_P_LR * T2D_MAX_TYPES + type];
-                    }
+                    const double wb = wheel_base_or_type(c[T2D_PURSUIT_WHEEL_BASE], pv, ids);
                     const double dy = ty - y, dx = tx - x;
                     const double angle = atan2_det(dy, dx);
                     const double distance = __builtin_sqrt(dy * dy + dx * dx);
@@ -186,7 +161,7 @@ __global__ __launch_bounds__(kPursuitBlock) void pursuit_kernel(PoolView pv, Pur
             // ---- longitudinal
             double accel;
             if (lon_mode == 2) {
-                accel = (double)__uint_as_float(in1);
+                accel = (double)__uint_as_float(in.w1);
             } else {
                 const double kp = c[T2D_PURSUIT_KP];
                 int lead = -1;
@@ -218,25 +193,22 @@ __global__ __launch_bounds__(kPursuitBlock) void pursuit_kernel(PoolView pv, Pur
             if (__builtin_isfinite(steering) && __builtin_isfinite(accel)) {
                 r.action[0] = steering;
                 r.action[1] = accel;
-                o0 = __float_as_uint((float)steering);
-                o1 = __float_as_uint((float)accel);
+                o = {__float_as_uint((float)steering), __float_as_uint((float)accel)};
             } else {
                 r.events |= T2D_PURSUIT_NONFINITE;
             }
         }
     }
     out[i] = r;
-    act_out[2 * (size_t)i] = o0;
-    act_out[2 * (size_t)i + 1] = o1;
+    action_row_out(act_out, i, o);
 }
 
 }  // namespace
 
 hipError_t launch_pursuit(const PoolView& v, const PursuitView& cv, const RouteView& rv, const float* act_in, float* act_out,
                           t2d_pursuit_record* out, hipStream_t s) {
-    const int block = std::min(kPursuitBlock, (v.A + 63) & ~63);
-    const size_t lds = rv.kind == 1 ? (size_t)rv.lds_bytes : 0;
-    hipLaunchKernelGGL(pursuit_kernel, dim3(v.n_env), dim3(block), lds, s, v, cv, rv, reinterpret_cast<const uint32_t*>(act_in),
+    const ScriptedLaunch l = scripted_launch(v, rv);
+    hipLaunchKernelGGL(pursuit_kernel, dim3(v.n_env), dim3(l.block), l.lds, s, v, cv, rv, reinterpret_cast<const uint32_t*>(act_in),
                        reinterpret_cast<uint32_t*>(act_out), out);
     return hipGetLastError();
 }

@@ -6,7 +6,8 @@
 //
 // Two access patterns, one arithmetic (t2d_route_dev.h):
 //   set routes    few polylines shared by many participants.  One workgroup per env; the vertices of the env's route set are
-//                 staged once into LDS as fp32 pairs (widened on read) behind the set's route offsets; lane a sweeps the route
+//                 staged once into LDS as fp32 pairs (widened on read) behind the set's route offsets (stage_route_set,
+//                 t2d_scripted_dev.h: pid_kernel and pursuit_kernel stage the same way); lane a sweeps the route
 //                 of participant a.  Lanes on the same route read the same LDS address in the same iteration (one broadcast
 //                 8-byte read); lanes on routes of different lengths diverge in the loop's trip count only.
 //   trace routes  one polyline per participant: the (x, y) of a source participant in slots first..last of a recorded
@@ -14,10 +15,9 @@
 //                 ([capacity][N_src]); with route_of = the own agent index consecutive lanes read consecutive words of a row.
 //                 Small pools with long traces: G lanes per participant (off_route_trace_group_kernel).
 // Both write f32 distance and u8 verdict per participant with vector stores and change no pool field.
-#include <algorithm>
-
 #include "t2d_pool.h"
 #include "t2d_route_dev.h"
+#include "t2d_scripted_dev.h"
 
 namespace t2d {
 
@@ -34,14 +34,9 @@ __device__ __forceinline__ bool route_live(uint32_t ids, int r, float x, float y
 __global__ __launch_bounds__(kBlock) void off_route_set_kernel(PoolView pv, RouteView rv, float* dist, uint8_t* off) {
     extern __shared__ __attribute__((aligned(16))) unsigned char route_lds[];
     const int e = blockIdx.x;
-    const int s = rv.set_of_env[e];
-    const int r0 = rv.set_route_start[s], nr = rv.set_route_start[s + 1] - r0;
-    const int v0 = rv.route_vert_off[r0], nv = rv.route_vert_off[r0 + nr] - v0;
-    float2* lv = reinterpret_cast<float2*>(route_lds);
-    int32_t* lo = reinterpret_cast<int32_t*>(route_lds + (size_t)nv * sizeof(float2));
-    const float2* gv = reinterpret_cast<const float2*>(rv.verts) + v0;
-    for (int k = threadIdx.x; k < nv; k += blockDim.x) lv[k] = gv[k];
-    for (int k = threadIdx.x; k <= nr; k += blockDim.x) lo[k] = rv.route_vert_off[r0 + k] - v0;
+    const StagedRoutes routes = stage_route_set(route_lds, rv, e);
+    const float2* lv = routes.verts;
+    const int32_t* lo = routes.first;
     __syncthreads();
     const int a = threadIdx.x;
     if (a >= pv.A) return;
@@ -163,8 +158,8 @@ __global__ __launch_bounds__(kBlock) void off_route_trace_group_kernel(PoolView 
 
 hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist, uint8_t* off, hipStream_t s) {
     if (rv.kind == 1) {
-        const int block = std::min(kBlock, (v.A + 63) & ~63);
-        hipLaunchKernelGGL(off_route_set_kernel, dim3(v.n_env), dim3(block), (size_t)rv.lds_bytes, s, v, rv, dist, off);
+        const ScriptedLaunch l = scripted_launch(v, rv);
+        hipLaunchKernelGGL(off_route_set_kernel, dim3(v.n_env), dim3(l.block), l.lds, s, v, rv, dist, off);
     } else if (rv.log2_group > 0) {
         const int per_block = kBlock >> rv.log2_group;
         hipLaunchKernelGGL(off_route_trace_group_kernel, dim3((v.N + per_block - 1) / per_block), dim3(kBlock), 0, s, v, rv, dist, off);

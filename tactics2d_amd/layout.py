@@ -59,6 +59,9 @@ PROFILE_CAMERA = 11          # kernel id of t2d_camera_render in t2d_profile_rea
 RS_SLOTS, RS_MAX_SEGMENTS, RS_MAX_POSES, RS_MAX_BEAMS = 48, 5, 1024, 1024
 RS_NO_TARGET, RS_FAR, RS_FOUND, RS_NONE_FREE, RS_UNCHECKED = range(5)
 RS_RECORD_BYTES = 96
+# the records as columns of their int32 ("<i4") and float64 ("<f8") views: field -> (view, column or columns of that view)
+RS_RECORD_FIELDS = {"status": ("<i4", 0), "slot": ("<i4", 1), "n_seg": ("<i4", 2), "n_visited": ("<i4", 3), "steer": ("<i4", slice(4, 9)),
+                    "distance": ("<f8", slice(5, 10)), "length": ("<f8", 10), "shortest": ("<f8", 11)}
 PROFILE_RS_PLAN = 13         # kernel id of t2d_rs_plan in t2d_profile_read
 # Dubins paths and sampled curve lines (t2d_dubins_paths / t2d_curve_lines / t2d_curve_routes): slots, the word record's size
 # in bytes (f64 seg[5], i8 letter[5], i8 n_seg, 2 bytes of padding), the sampling rules, the kernel id
@@ -68,6 +71,8 @@ CURVE_DUBINS, CURVE_RS = 0, 1
 PROFILE_CURVE_ROUTES = 17
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
+RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),
+                           "action": ("<f8", slice(2, 4)), "distance_to_go": ("<f8", 4), "total_error": ("<f8", 5)}
 RS_FOLLOW_ADOPTED, RS_FOLLOW_POP_REACHED, RS_FOLLOW_POP_RISING, RS_FOLLOW_FINISHED, RS_FOLLOW_RESET, RS_FOLLOW_DROPPED = \
     1, 2, 4, 8, 16, 32
 PROFILE_RS_FOLLOW = 14
@@ -88,6 +93,8 @@ PID_STATE_WORDS = 6   # lat integral, prev_error, prev_derivative, then the same
 PID_NONE = 255
 PID_ROUTE_END, PID_NONFINITE, PID_RESET, PID_NO_ROUTE, PID_BAD_WHEEL_BASE, PID_SATURATED = 1, 2, 4, 8, 16, 32
 PID_RECORD_BYTES = 48
+PID_RECORD_FIELDS = {"cross_track": ("<f8", 0), "lat_error": ("<f8", 1), "segment": ("<i4", 4), "leader": ("<i4", 5), "events": ("<i4", 6),
+                     "action": ("<f8", slice(4, 6))}
 PROFILE_PID = 15
 # pure pursuit and cruise / ACC controllers (t2d_set_pursuit / t2d_pursuit_actions): parameter-row columns, mode values, event
 # bits, the record's size in bytes, the kernel id
@@ -100,6 +107,9 @@ PURSUIT_LON_CRUISE, PURSUIT_LON_ACC, PURSUIT_LON_CALLER = 0, 1, 2      # values 
 PURSUIT_NONE = 255
 PURSUIT_ROUTE_END, PURSUIT_NONFINITE, PURSUIT_WRAPPED, PURSUIT_NO_ROUTE, PURSUIT_NO_LEADER = 1, 2, 4, 8, 16
 PURSUIT_RECORD_BYTES = 72
+PURSUIT_RECORD_FIELDS = {"point": ("<f8", slice(0, 2)), "pre_aiming_distance": ("<f8", 2), "distance": ("<f8", 3), "cross_track": ("<f8", 4),
+                         "segment": ("<i4", 10), "target_segment": ("<i4", 11), "leader": ("<i4", 12), "events": ("<i4", 13),
+                         "action": ("<f8", slice(7, 9))}
 PROFILE_PURSUIT = 16
 # host-frame sections (t2d_frame_config)
 FRAME_LIDAR, FRAME_TARGET, FRAME_ZEROCOPY = 1, 2, 4

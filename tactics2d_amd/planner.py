@@ -9,6 +9,7 @@ replaces the env's action row by the PID follower's.  There is no CPU path.
 import numpy as np
 
 from . import layout as L
+from .controller import _ActionWriter
 from .participant import MAX_STEER, VEHICLE_TEMPLATE
 
 STATUS_NAMES = ("no_target", "far", "found", "none_free", "unchecked")   # layout.RS_NO_TARGET ...
@@ -105,18 +106,20 @@ def rs_follow_params(planner_params, steer_ratio=0.98, max_speed=0.5, max_accele
                 kd_s=0.0, yaw_weight=0.5, reach_radius=0.02, rising_radius=0.1, steer_bound=steer_bound, accel_bound=accel_bound)
 
 
-class RSFollower:
+class RSFollower(_ActionWriter):
     """pool: the ParticipantPool of `planner` (an RSPlanner, whose radius and center_shift it takes).  follow() returns zero-copy
     torch views of the follower's records (ParticipantPool.rs_follow_views) beside the action rows it wrote."""
 
+    _record_bytes, _records, _n_rows = L.RS_FOLLOW_RECORD_BYTES, "rs_follow_views", "n_env"
+
     def __init__(self, pool, planner, **overrides):
-        self.pool, self.planner = pool, planner
+        super().__init__(pool)
+        self.planner = planner
         self.params = rs_follow_params(planner.params)
         unknown = set(overrides) - set(self.params)
         if unknown:
             raise TypeError(f"unknown follower options {sorted(unknown)}")
         self.params.update(overrides)
-        self._rec = self._views = self._act = None
         pool.rs_follow_config(**self.params)
 
     def follow(self, actions, plan=None, out=None, stream=None):
@@ -125,32 +128,12 @@ class RSFollower:
         out: float32 [n_env, 2] tensor for the rows to step (None: a buffer of the follower's own).  Asynchronous on `stream`.
         Returns dict(action_rows, executing, segment, events, steps, action, distance_to_go, total_error), valid until the
         next follow()."""
-        import torch
-        pool = self.pool
-        dev = torch.device("cuda", pool.device_id)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        for t in (actions, out):
-            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (pool.n_env, 2) or not t.is_contiguous()):
-                raise ValueError(f"action rows must be a contiguous float32 [{pool.n_env}, 2] tensor")
-        if self._rec is None:
-            self._rec = torch.zeros((pool.n_env, L.RS_FOLLOW_RECORD_BYTES // 8), dtype=torch.float64, device=dev)
-            self._views = pool.rs_follow_views(self._rec.data_ptr(), owner=self._rec)
-            self._act = torch.zeros((pool.n_env, 2), dtype=torch.float32, device=dev)
-        rows = self._act if out is None else out
         if plan is not None:
             plan_ptr = plan["status"].data_ptr()   # (the record's first word)
         else:
             plan_ptr = self.planner._out.data_ptr() if self.planner._out is not None else None
-        pool.rs_follow(None if actions is None else actions.data_ptr(), rows.data_ptr(), plan_ptr, self._rec.data_ptr(), st.cuda_stream)
-        return dict(self._views, action_rows=rows)
+        return self._write(lambda act_in, act_out, rec, st: self.pool.rs_follow(act_in, act_out, plan_ptr, rec, st), actions, out, stream)
 
     def reset(self, mask=None, stream=None):
         """agent.reset() for the envs where `mask` (a uint8 / bool CUDA tensor [n_env]) is non-zero; None: every env"""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.pool.device_id))
-        if mask is not None:
-            mask = mask.to(torch.uint8).contiguous()
-            if tuple(mask.shape) != (self.pool.n_env,):
-                raise ValueError(f"mask must have {self.pool.n_env} elements")
-            self._mask = mask   # (kept alive until the launch has run)
-        self.pool.rs_follow_reset(None if mask is None else mask.data_ptr(), st.cuda_stream)
+        self._reset(self.pool.rs_follow_reset, mask, stream)

@@ -255,15 +255,7 @@ class ParticipantPool:
         """Zero-copy torch views of t2d_rs_plan_record [n_env] at `ptr` (None: the pool's own records): status, slot, n_seg,
         n_visited int32 [n]; steer int32 [n, 5] (+1 L, -1 R, 0 S); distance float64 [n, 5] (signed, metres); length, shortest
         float64 [n]."""
-        import torch
-        if ptr is None:
-            ptr = self.rs_plan_buffer()[0]
-        dev, n = f"cuda:{self.device_id}", self.n_env
-        keep = owner if owner is not None else self
-        i32 = torch.as_tensor(_DevArray(ptr, (n, L.RS_RECORD_BYTES // 4), "<i4", keep), device=dev)
-        f64 = torch.as_tensor(_DevArray(ptr, (n, L.RS_RECORD_BYTES // 8), "<f8", keep), device=dev)
-        return dict(status=i32[:, 0], slot=i32[:, 1], n_seg=i32[:, 2], n_visited=i32[:, 3], steer=i32[:, 4:9],
-                    distance=f64[:, 5:10], length=f64[:, 10], shortest=f64[:, 11])
+        return self._record_views(ptr, self._lib.t2d_rs_plan_buffers, self.n_env, L.RS_RECORD_BYTES, L.RS_RECORD_FIELDS, owner)
 
     # ---------------------------------------------------------------- Reeds-Shepp path follower
     def rs_follow_config(self, **params):
@@ -286,29 +278,46 @@ class ParticipantPool:
         """Zero-copy torch views of t2d_rs_follow_record [n_env] at `ptr` (None: the pool's own records): executing, segment,
         events, steps int32 [n]; action float64 [n, 2] (normalised; NaN: the policy's row went through); distance_to_go,
         total_error float64 [n]."""
+        return self._record_views(ptr, self._lib.t2d_rs_follow_buffers, self.n_env, L.RS_FOLLOW_RECORD_BYTES,
+                                  L.RS_FOLLOW_RECORD_FIELDS, owner)
+
+    def _record_views(self, ptr, own_buffer, n_rows, record_bytes, fields, owner):
+        """Zero-copy torch views of the records [n_rows] of record_bytes each at `ptr` (None: the pool's own, which own_buffer
+        -- a t2d_*_buffers entry point -- locates), one per entry of `fields` (a layout.*_RECORD_FIELDS table); `owner` (None:
+        the pool) is kept alive by the views."""
         import torch
         if ptr is None:
             p_, nb = C.c_void_p(), C.c_size_t()
-            self._ck(self._lib.t2d_rs_follow_buffers(self._h, C.byref(p_), C.byref(nb)))
+            self._ck(own_buffer(self._h, C.byref(p_), C.byref(nb)))
             ptr = p_.value
-        dev, n = f"cuda:{self.device_id}", self.n_env
         keep = owner if owner is not None else self
-        i32 = torch.as_tensor(_DevArray(ptr, (n, L.RS_FOLLOW_RECORD_BYTES // 4), "<i4", keep), device=dev)
-        f64 = torch.as_tensor(_DevArray(ptr, (n, L.RS_FOLLOW_RECORD_BYTES // 8), "<f8", keep), device=dev)
-        return dict(executing=i32[:, 0], segment=i32[:, 1], events=i32[:, 2], steps=i32[:, 3], action=f64[:, 2:4],
-                    distance_to_go=f64[:, 4], total_error=f64[:, 5])
+        cols = {t: torch.as_tensor(_DevArray(ptr, (n_rows, record_bytes // int(t[2])), t, keep), device=f"cuda:{self.device_id}")
+                for t in ("<i4", "<f8")}
+        return {name: cols[t][:, c] for name, (t, c) in fields.items()}
+
+    def _set_ctrl(self, setter, cols, ctrl_rows, ctrl_id, *per_participant):
+        """One t2d_set_* call: ctrl_rows [n_ctrl, >= cols] as contiguous float64 and ctrl_id uint8 [n], then the family's further
+        per-participant arrays (None: NULL).  ctrl_rows=None uninstalls (n_ctrl 0, every pointer NULL)."""
+        if ctrl_rows is None:
+            self._ck(setter(self._h, None, 0, 0, None, *[None] * len(per_participant)))
+            return
+        rows = np.ascontiguousarray(ctrl_rows, np.float64)
+        if rows.ndim != 2:
+            raise ValueError(f"ctrl_rows must be 2-D [n_ctrl, >= {cols}]")
+        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
+        self._ck(setter(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid), *map(_p, per_participant)))
+
+    def _f32_per_participant(self, value, name):
+        """float32 [n] of a scalar (broadcast) or an array; None stays None"""
+        if value is None:
+            return None
+        v = np.asarray(value, np.float32)
+        return _arr(np.broadcast_to(v.reshape(-1) if v.ndim else v, (self.n,)), np.float32, self.n, name)
 
     def set_idm(self, ctrl_rows, ctrl_id):
         """Install IDM controllers: ctrl_rows [n_ctrl, 8] (layout.IDM_*), ctrl_id [n] uint8 (IDM_NONE =
         action supplied by the caller).  ctrl_rows=None uninstalls."""
-        if ctrl_rows is None:
-            self._ck(self._lib.t2d_set_idm(self._h, None, 0, 0, None))
-            return
-        rows = np.ascontiguousarray(ctrl_rows, np.float64)
-        if rows.ndim != 2:
-            raise ValueError("ctrl_rows must be 2-D [n_ctrl, >= 8]")
-        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
-        self._ck(self._lib.t2d_set_idm(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid)))
+        self._set_ctrl(self._lib.t2d_set_idm, L.IDM_COLS, ctrl_rows, ctrl_id)
 
     def idm_actions(self, forced_leader_ptr=None, stream=None):
         """IDMController.step for every controlled participant (also runs inside step()/integrate())."""
@@ -319,18 +328,8 @@ class ParticipantPool:
         """Install PID controllers (t2d_set_pid): ctrl_rows [n_ctrl, 14] (layout.PID_*; controller.PIDController.row()), ctrl_id
         uint8 [n] (PID_NONE = the caller's row goes through), target_speed float32 [n] (a scalar broadcasts; None: zeros),
         idm_row int32 [n] (rows of set_idm for lon_mode 2; None: row 0).  ctrl_rows=None uninstalls."""
-        if ctrl_rows is None:
-            self._ck(self._lib.t2d_set_pid(self._h, None, 0, 0, None, None, None))
-            return
-        rows = np.ascontiguousarray(ctrl_rows, np.float64)
-        if rows.ndim != 2:
-            raise ValueError("ctrl_rows must be 2-D [n_ctrl, >= 14]")
-        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
-        ts = None if target_speed is None else _arr(np.broadcast_to(np.asarray(target_speed, np.float32).reshape(-1)
-                                                    if np.ndim(target_speed) else np.float32(target_speed), (self.n,)),
-                                                    np.float32, self.n, "target_speed")
-        ir = _arr(idm_row, np.int32, self.n, "idm_row")
-        self._ck(self._lib.t2d_set_pid(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid), _p(ts), _p(ir)))
+        self._set_ctrl(self._lib.t2d_set_pid, L.PID_COLS, ctrl_rows, ctrl_id, self._f32_per_participant(target_speed, "target_speed"),
+                       _arr(idm_row, np.int32, self.n, "idm_row"))
 
     def pid_actions(self, act_in_ptr, act_out_ptr, record_ptr=None, stream=None):
         """t2d_pid_actions: one launch; float32 [n, 2] (steering, accel) rows from act_in_ptr (None: zeros) to act_out_ptr (may
@@ -353,35 +352,17 @@ class ParticipantPool:
 
     def pid_records(self, ptr=None, owner=None):
         """Zero-copy torch views of t2d_pid_record [n] at `ptr` (None: the pool's own records): cross_track, lat_error float64
-        [n]; segment, leader, events int32 [n]; action float64 [n, 2] (NaN: the caller's row went through)."""
-        import torch
-        if ptr is None:
-            p_, nb = C.c_void_p(), C.c_size_t()
-            self._ck(self._lib.t2d_pid_buffers(self._h, C.byref(p_), C.byref(nb)))
-            ptr = p_.value
-        dev, n = f"cuda:{self.device_id}", self.n
-        keep = owner if owner is not None else self
-        i32 = torch.as_tensor(_DevArray(ptr, (n, L.PID_RECORD_BYTES // 4), "<i4", keep), device=dev)
-        f64 = torch.as_tensor(_DevArray(ptr, (n, L.PID_RECORD_BYTES // 8), "<f8", keep), device=dev)
-        return dict(cross_track=f64[:, 0], lat_error=f64[:, 1], segment=i32[:, 4], leader=i32[:, 5], events=i32[:, 6],
-                    action=f64[:, 4:6])
+        [n]; segment, leader, events int32 [n]; action float64 [n, 2] (NaN: the caller's row went through).  Views of the pool's own records are valid until the next
+        set_pid, which replaces or frees them."""
+        return self._record_views(ptr, self._lib.t2d_pid_buffers, self.n, L.PID_RECORD_BYTES, L.PID_RECORD_FIELDS, owner)
 
     # ---------------------------------------------------------------- pure pursuit and cruise / ACC controllers
     def set_pursuit(self, ctrl_rows, ctrl_id=None, target_speed=None):
         """Install pure-pursuit / acceleration controllers (t2d_set_pursuit): ctrl_rows [n_ctrl, 13] (layout.PURSUIT_*;
         controller.PurePursuitController.row() / AccelerationController.row()), ctrl_id uint8 [n] (PURSUIT_NONE = the caller's row
         goes through), target_speed float32 [n] (a scalar broadcasts; None: zeros).  ctrl_rows=None uninstalls."""
-        if ctrl_rows is None:
-            self._ck(self._lib.t2d_set_pursuit(self._h, None, 0, 0, None, None))
-            return
-        rows = np.ascontiguousarray(ctrl_rows, np.float64)
-        if rows.ndim != 2:
-            raise ValueError("ctrl_rows must be 2-D [n_ctrl, >= 13]")
-        cid = _arr(ctrl_id, np.uint8, self.n, "ctrl_id")
-        ts = None if target_speed is None else _arr(np.broadcast_to(np.asarray(target_speed, np.float32).reshape(-1)
-                                                    if np.ndim(target_speed) else np.float32(target_speed), (self.n,)),
-                                                    np.float32, self.n, "target_speed")
-        self._ck(self._lib.t2d_set_pursuit(self._h, _p(rows), rows.shape[0], rows.shape[1], _p(cid), _p(ts)))
+        self._set_ctrl(self._lib.t2d_set_pursuit, L.PURSUIT_COLS, ctrl_rows, ctrl_id,
+                       self._f32_per_participant(target_speed, "target_speed"))
 
     def pursuit_actions(self, act_in_ptr, act_out_ptr, record_ptr=None, stream=None):
         """t2d_pursuit_actions: one launch; float32 [n, 2] (steering, accel) rows from act_in_ptr (None: zeros) to act_out_ptr
@@ -393,17 +374,7 @@ class ParticipantPool:
         pre_aiming_distance, distance, cross_track float64 [n]; segment, target_segment, leader, events int32 [n]; action
         float64 [n, 2] (NaN: the caller's row went through).  Views of the pool's own records are valid until the next set_pursuit, which
         replaces or frees them."""
-        import torch
-        if ptr is None:
-            p_, nb = C.c_void_p(), C.c_size_t()
-            self._ck(self._lib.t2d_pursuit_buffers(self._h, C.byref(p_), C.byref(nb)))
-            ptr = p_.value
-        dev, n = f"cuda:{self.device_id}", self.n
-        keep = owner if owner is not None else self
-        i32 = torch.as_tensor(_DevArray(ptr, (n, L.PURSUIT_RECORD_BYTES // 4), "<i4", keep), device=dev)
-        f64 = torch.as_tensor(_DevArray(ptr, (n, L.PURSUIT_RECORD_BYTES // 8), "<f8", keep), device=dev)
-        return dict(point=f64[:, 0:2], pre_aiming_distance=f64[:, 2], distance=f64[:, 3], cross_track=f64[:, 4],
-                    segment=i32[:, 10], target_segment=i32[:, 11], leader=i32[:, 12], events=i32[:, 13], action=f64[:, 7:9])
+        return self._record_views(ptr, self._lib.t2d_pursuit_buffers, self.n, L.PURSUIT_RECORD_BYTES, L.PURSUIT_RECORD_FIELDS, owner)
 
     def verify_state_ptr(self, x_ptr, y_ptr, heading_ptr, speed_ptr, interval_ms, valid_ptr, stream=None):
         """verify_state of device-resident candidate columns against the pool's current state."""
