@@ -47,6 +47,8 @@
  *   t2d_dubins_paths /    <- Dubins.get_all_path / get_path / get_curve  interpolator/dubins.py:240-331
  *   t2d_curve_lines /        DubinsPath.get_curve_line :28-104; ReedsSheppPath.get_curve_line  interpolator/reeds_shepp.py:46-139
  *   t2d_curve_routes         Circle.get_arc  geometry/circle.py:106-139 (the curve written into the routes above)
+ *   t2d_spline_curves /   <- Bezier.get_curve / BSpline.get_curve / CubicSpline.get_curve  interpolator/bezier.py, b_spline.py,
+ *   t2d_spline_routes        cubic_spline.py over interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -1032,6 +1034,62 @@ int t2d_curve_routes(t2d_pool* pool, const void* words_dev, const double* start_
                      int32_t route, int32_t* count_dev, void* hip_stream);
 int t2d_route_vertices(t2d_pool* pool, void** verts_dev, size_t* n_vertices);
 
+/* Bezier, B-spline and cubic spline curves on the device -- interpolator/bezier.py, b_spline.py, cubic_spline.py and the compiled
+ * module behind them, interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp, restated operation by operation in
+ * fp64 (+ - * / and comparisons only, every sum in the reference's order: tests/spline_ref.py).
+ *   Bezier     N control points, n_interpolation >= 2 points: binomials b[k] = b[k-1] * (N-k) / k, t = i * (1 / (n-1)), powers by
+ *              repeated multiplication, terms b[k] * (1-t)^(N-1-k) * t^k accumulated from k = 0 upward.
+ *   B-spline   n_interpolation >= 1 points at u = u_start + j * ((u_end - u_start) / n_interpolation), j < n_interpolation,
+ *              u_start = knots[degree], u_end = knots[n_ctrl]: THE END OF THE CURVE IS NEVER SAMPLED.  The basis is the triangular
+ *              table of basis_function: degree 0 is half-open (k[idx] <= u < k[idx+1], 0 at the last knot), a term with a zero
+ *              denominator is 0, and the point is the sum over ALL control points in order.  knots_dev NULL: the Python
+ *              default, np.linspace(0, 1, n_ctrl + degree + 1), computed on the device as i * (1 / (num - 1)), the last one 1.
+ *   cubic      y as a function of strictly increasing x, (n_ctrl-1) * n_interpolation + 1 points.  Inside a segment the abscissa
+ *              is ACCUMULATED, xi += h / (n_interpolation-1): the last sample of a segment only approximates the next knot, the
+ *              next segment starts on the knot itself (a near-duplicate vertex), and the last control point is appended
+ *              exactly.  Natural and Clamped: the Thomas recursion.  NotAKnot: BandedSolve as written (pivot from at most two
+ *              rows below, strict >, columns i .. i+2 only); with THREE control points its matrix is singular: where the
+ *              elimination cancels exactly (equal spacing always, most other rows) it returns m = 0 and the curve is the
+ *              polyline through the points; where a rounding residue is left, that residue is the last pivot and the curve is
+ *              what it gives -- the reference's either way.  derivs_dev is read under T2D_SPLINE_CLAMPED only.
+ * BUILD-DEFINED, per row: count 0 and nothing else written where n_ctrl is below the family's minimum (Bezier 2, cubic 3,
+ * B-spline degree + 1) or above max_ctrl, where the x of a cubic row is not strictly increasing, where knots decrease, or where
+ * a control point, knot or (Clamped) derivative the row reads is not finite.  One bad row touches only its own outputs.  A curve
+ * of more than max_points points writes its first max_points and count holds the FULL count (saturating at INT32_MAX).
+ *   t2d_spline_curves  n curves of ONE family in ONE launch, asynchronous on hip_stream, no pool: kind T2D_SPLINE_*; ctrl_dev
+ *                      f64 [n][max_ctrl][2] (16-byte aligned), n_ctrl_dev i32 [n] (row e uses its first n_ctrl[e] points),
+ *                      n_interpolation; B-spline: degree and knots_dev f64 [n][max_ctrl + degree + 1] (row e uses its first
+ *                      n_ctrl[e] + degree + 1) or NULL; cubic: boundary_type T2D_SPLINE_NATURAL / _CLAMPED / _NOT_A_KNOT and
+ *                      derivs_dev f64 [n][2] or NULL (0, 0) -> xy_dev f64 [n][max_points][2] (16-byte aligned), count_dev i32
+ *                      [n].  Arguments of another family are ignored.  T2D_ERR_INVALID, nothing launched: n < 0, max_points
+ *                      <= 0, another kind or boundary type, n_interpolation below the family's minimum (2, 1, 2), degree < 0
+ *                      or > T2D_SPLINE_MAX_DEGREE, max_ctrl < 1 or > T2D_SPLINE_MAX_CTRL, a null or misaligned pointer.
+ *   t2d_spline_routes  the same sampler, curve e for env e (n = n_env), written as fp32 vertices into route `route` of env e's
+ *                      installed set under the rules of t2d_curve_routes: the route's vertex count is the capacity; count c ==
+ *                      0 leaves the route untouched; c <= capacity: vertices k >= c repeat the curve's LAST WRITTEN POINT -- for
+ *                      a B-spline that is its last SAMPLE, not the curve's end --; c > capacity: the first `capacity` points.
+ *                      count_dev i32 [n_env] (may be NULL) = c.  T2D_ERR_STATE unless route sets are the installed kind, no
+ *                      two envs share a set and every env's set has a route `route`; T2D_ERR_INVALID as above and for route
+ *                      < 0.  kernel_id T2D_PROFILE_SPLINE_ROUTES in t2d_profile_read.
+ * T2D_SPLINE_CURVES_PER_BLOCK curves share a workgroup (one wave each; the per-curve working set, 10 KB for a cubic spline, lives
+ * in LDS, which is what the two caps bound).                                                                              */
+#define T2D_SPLINE_BEZIER 0
+#define T2D_SPLINE_BSPLINE 1
+#define T2D_SPLINE_CUBIC 2
+#define T2D_SPLINE_NATURAL 1
+#define T2D_SPLINE_CLAMPED 2
+#define T2D_SPLINE_NOT_A_KNOT 3
+#define T2D_SPLINE_MAX_CTRL 32
+#define T2D_SPLINE_MAX_DEGREE 5
+#define T2D_SPLINE_CURVES_PER_BLOCK 4
+#define T2D_PROFILE_SPLINE_ROUTES 18
+int t2d_spline_curves(int32_t device_id, int32_t n, int32_t kind, const double* ctrl_dev, const int32_t* n_ctrl_dev, int32_t max_ctrl,
+                      int32_t n_interpolation, int32_t degree, const double* knots_dev, int32_t boundary_type, const double* derivs_dev,
+                      int32_t max_points, double* xy_dev, int32_t* count_dev, void* hip_stream);
+int t2d_spline_routes(t2d_pool* pool, int32_t kind, const double* ctrl_dev, const int32_t* n_ctrl_dev, int32_t max_ctrl,
+                      int32_t n_interpolation, int32_t degree, const double* knots_dev, int32_t boundary_type, const double* derivs_dev,
+                      int32_t route, int32_t* count_dev, void* hip_stream);
+
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
  * over the action row of an env while a path is being executed and leaves the policy's row alone otherwise.
@@ -1475,7 +1533,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
  * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
  * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions),
- * 17 = curve lines into the route sets (t2d_curve_routes).  */
+ * 17 = curve lines into the route sets (t2d_curve_routes), 18 = spline curves into the route sets (t2d_spline_routes).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

@@ -3208,6 +3208,31 @@ int t2d_curve_routes(t2d_pool* p, const void* words_dev, const double* start_dev
     return record_event(p, T2D_PROFILE_CURVE_ROUTES, s, false);
 }
 
+int t2d_spline_routes(t2d_pool* p, int32_t kind, const double* ctrl_dev, const int32_t* n_ctrl_dev, int32_t max_ctrl,
+                      int32_t n_interpolation, int32_t degree, const double* knots_dev, int32_t boundary_type, const double* derivs_dev,
+                      int32_t route, int32_t* count_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (const char* why = t2d::spline_args_error(kind, ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev, boundary_type,
+                                                 derivs_dev))
+        return fail(p, T2D_ERR_INVALID, std::string("t2d_spline_routes: ") + why);
+    if (reinterpret_cast<uintptr_t>(count_dev) & 3u) return fail(p, T2D_ERR_INVALID, "t2d_spline_routes: misaligned count_dev");
+    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_spline_routes: route must be >= 0");
+    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_spline_routes writes into route sets: t2d_set_routes must precede it");
+    if (!p->route_sets_distinct)
+        return fail(p, T2D_ERR_STATE, "t2d_spline_routes: two envs share a route set; install one set per env (set_of_env)");
+    if (route >= p->route_min_limit)
+        return fail(p, T2D_ERR_STATE, "t2d_spline_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
+                                          std::to_string(p->route_min_limit) + " routes)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, T2D_PROFILE_SPLINE_ROUTES, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_spline_routes(p->v, p->route, kind, ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev,
+                                         boundary_type, derivs_dev, route, count_dev, s));
+    return record_event(p, T2D_PROFILE_SPLINE_ROUTES, s, false);
+}
+
 int t2d_route_vertices(t2d_pool* p, void** verts_dev, size_t* n_vertices) {
     if (!p) return T2D_ERR_INVALID;
     if (!verts_dev || !n_vertices) return fail(p, T2D_ERR_INVALID, "null output");

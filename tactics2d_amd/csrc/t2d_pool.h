@@ -658,6 +658,13 @@ hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist,
 // curve lines into the route sets (t2d_curve.hip): curve e -> the fp32 vertices of route `route` of env e's set
 hipError_t launch_curve_routes(const PoolView& v, const RouteView& rv, const void* words, const double* start, double radius,
                                double step, int rule, int route, int32_t* count, hipStream_t s);
+// spline curves (t2d_spline.hip): what is wrong with a launch's arguments (null: nothing), and curve e -> the fp32 vertices of
+// route `route` of env e's set
+const char* spline_args_error(int kind, const double* ctrl, const int32_t* n_ctrl, int max_ctrl, int n_interp, int degree,
+                              const double* knots, int boundary, const double* derivs);
+hipError_t launch_spline_routes(const PoolView& v, const RouteView& rv, int kind, const double* ctrl, const int32_t* n_ctrl,
+                                int max_ctrl, int n_interp, int degree, const double* knots, int boundary, const double* derivs,
+                                int route, int32_t* count, hipStream_t s);
 // racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
 hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
 hipError_t launch_trackgen(const TrackGenView& g, int n, int mode, hipStream_t s);

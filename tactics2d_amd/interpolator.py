@@ -1,12 +1,15 @@
-"""Reeds-Shepp and Dubins curves for batches of queries on the device (tactics2d/interpolator/reeds_shepp.py, dubins.py).
+"""Reeds-Shepp and Dubins curves for batches of queries, and Bezier, B-spline and cubic spline curves for batches of control
+polygons, on the device (tactics2d/interpolator/reeds_shepp.py, dubins.py, bezier.py, b_spline.py, cubic_spline.py).
 
 `ReedsShepp(radius).get_all_path(...)` is the reference's method of that name for n queries in one launch of
 t2d_rs_paths (include/t2d.h): the 48 slots of the reference's list, in its order, as device tensors.  `Dubins(radius)` is the
 same for the six Dubins words (t2d_dubins_paths).  `get_curve(...)` of either class samples the shortest path of every query into
 the point list of the reference's get_curve_line (t2d_curve_lines); `curve_lines(...)` is that call for words of the caller's own.
+`Bezier`, `BSpline` and `CubicSpline` have the reference's get_curve for n control polygons in one launch of t2d_spline_curves.
 There is no CPU path: without a device the calls raise T2DError.
 """
 import ctypes as C
+import enum
 import functools
 
 import numpy as np
@@ -356,3 +359,210 @@ class Dubins(metaclass=_DubinsTables):
             out = curve_lines(words, path._inputs[0], self.radius, step_size, L.CURVE_DUBINS, max_points, self.device_id, st)
         out.slot = path.slot
         return out
+
+
+# ---- Bezier, B-spline and cubic spline curves (t2d_spline_curves) ----------------------------------------------------------------
+class SplineCurves:
+    """What Bezier / BSpline / CubicSpline.get_curve return: device tensors, one row per control polygon.  xy float64
+    [n, max_points, 2]: the first min(count, max_points) rows of a curve are its points, the rest is not written; count int32 [n]:
+    the curve's FULL point count (0: no curve -- too few control points in the row, abscissae that do not increase, knots that
+    decrease, an input that is not finite; > max_points: truncated)."""
+
+    def __init__(self, xy, count):
+        self.xy, self.count = xy, count
+
+
+SPLINE_KINDS = {"bezier": L.SPLINE_BEZIER, "bspline": L.SPLINE_BSPLINE, "cubic": L.SPLINE_CUBIC}
+_SHAPE_MESSAGE = "Control points should have shape (n, 2)."
+
+
+def _is_tensor(x):
+    import torch
+    return isinstance(x, torch.Tensor)
+
+
+def _used(values, used):
+    """numpy [n, k] with the entries past each row's `used` count replaced by the row's last used one (their differences are 0)"""
+    v = np.asarray(values, np.float64)
+    idx = np.minimum(np.arange(v.shape[1])[None, :], np.maximum(np.asarray(used).reshape(-1, 1) - 1, 0))
+    return np.take_along_axis(v, idx, 1)
+
+
+def spline_check(kind, control_points, n_ctrl=None, n_interpolation=100, degree=0, knot_vectors=None,
+                 boundary_type=L.SPLINE_NOT_A_KNOT, first_derivatives=None):
+    """The host side of a t2d_spline_curves / t2d_spline_routes call: every check that needs no device, raising the reference's
+    ValueError with its message (bezier.py:29-39, b_spline.py:39-51, cubic_spline.py:56-75 and the invalid_argument of the
+    compiled module); data-dependent ones (increasing x, non-decreasing knots) only for numpy inputs -- for device tensors those
+    rows come back with count 0.  Returns (kind, n, m, n_interpolation, degree, boundary_type, full point count of an m-point row)."""
+    kind = SPLINE_KINDS.get(kind, kind)
+    if kind not in SPLINE_KINDS.values():
+        raise ValueError(f"kind must be one of {sorted(SPLINE_KINDS)}")
+    shape = tuple(control_points.shape) if hasattr(control_points, "shape") else np.asarray(control_points).shape
+    if len(shape) not in (2, 3) or shape[-1] != 2:
+        raise ValueError(_SHAPE_MESSAGE)
+    n, m = (1, shape[0]) if len(shape) == 2 else shape[:2]
+    n_interpolation, degree = int(n_interpolation), int(degree)
+    if kind == L.SPLINE_BSPLINE:
+        if degree < 0:
+            raise ValueError("Degree must be non-negative.")
+        expected = m + degree + 1
+        if knot_vectors is not None:
+            kshape = tuple(knot_vectors.shape)
+            if kshape not in ((n, expected), (expected,)) or (len(kshape) == 1 and n != 1):
+                raise ValueError(f"Expected {expected} knots, got {kshape[-1] if kshape else 0}.")
+            if not _is_tensor(knot_vectors):
+                k = np.asarray(knot_vectors, np.float64).reshape(n, expected)
+                if n_ctrl is not None and not _is_tensor(n_ctrl):
+                    k = _used(k, np.asarray(n_ctrl) + degree + 1)
+                if np.any(np.diff(k, axis=1) < 0):
+                    raise ValueError("Knot vector must be non-decreasing.")
+        if m < degree + 1:
+            raise ValueError("Number of control points must be at least degree + 1.")
+        if n_interpolation <= 0:
+            raise ValueError("Number of interpolation points must be positive.")
+        if degree > L.SPLINE_MAX_DEGREE:
+            raise ValueError(f"degree {degree} is above the device cap of {L.SPLINE_MAX_DEGREE}")
+    elif kind == L.SPLINE_CUBIC:
+        names = ", ".join(CubicSpline.BoundaryType.__members__)
+        try:
+            boundary_type = CubicSpline.BoundaryType(boundary_type)
+        except ValueError:
+            raise ValueError(f"Invalid boundary type: {boundary_type}. Available options are: {names} or an integer value from 1 to "
+                             f"{len(CubicSpline.BoundaryType.__members__)}.") from None
+        if m < 3:
+            raise ValueError("Need at least 3 control points.")
+        if not _is_tensor(control_points):
+            x = np.asarray(control_points, np.float64).reshape(n, m, 2)[:, :, 0]
+            d = np.diff(x, axis=1)
+            if n_ctrl is not None and not _is_tensor(n_ctrl):
+                d = np.where(np.arange(1, m)[None, :] < np.asarray(n_ctrl).reshape(-1, 1), d, 1.0)
+            if np.any(d <= 0):
+                raise ValueError("x-values must be strictly increasing.")
+        if n_interpolation < 2:
+            raise ValueError("Number of interpolation points must be at least 2.")
+        boundary_type = boundary_type.value
+    elif n_interpolation < 2:
+        raise ValueError("n_interpolation must be greater than or equal to 2.")
+    if m > L.SPLINE_MAX_CTRL:
+        raise ValueError(f"{m} control points are above the device cap of {L.SPLINE_MAX_CTRL}")
+    if n_ctrl is not None and tuple(n_ctrl.shape) != (n,):
+        raise ValueError(f"n_ctrl must have shape ({n},)")
+    if first_derivatives is not None and tuple(np.shape(first_derivatives)) not in ((2,), (n, 2)):
+        raise ValueError(f"first_derivatives must be a pair or have shape ({n}, 2)")
+    full = (m - 1) * n_interpolation + 1 if kind == L.SPLINE_CUBIC else n_interpolation
+    return kind, n, m, n_interpolation, degree, boundary_type if kind == L.SPLINE_CUBIC else 0, full
+
+
+def spline_inputs(dev, n, m, control_points, n_ctrl, knot_vectors, first_derivatives):
+    """The device tensors of a launch: ctrl float64 [n, m, 2], n_ctrl int32 [n], knots float64 [n, m + degree + 1] or None,
+    derivs float64 [n, 2] or None.  A contiguous float64 CUDA tensor is used in place, anything else is uploaded or converted."""
+    import torch
+
+    def f64(x, shape):
+        if x is None:
+            return None
+        t = x.to(dev, torch.float64) if _is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, np.float64)).to(dev)
+        return t.reshape(shape).contiguous()
+
+    ctrl = f64(control_points, (n, m, 2))
+    if n_ctrl is None:
+        n_ctrl = torch.full((n,), m, dtype=torch.int32, device=dev)
+    elif _is_tensor(n_ctrl):
+        n_ctrl = n_ctrl.to(dev, torch.int32).contiguous()
+    else:
+        n_ctrl = torch.as_tensor(np.ascontiguousarray(n_ctrl, np.int32)).to(dev)
+    knots = f64(knot_vectors, (n, -1))
+    derivs = f64(first_derivatives, (-1, 2))
+    if derivs is not None and derivs.shape[0] != n:   # (one pair for every row)
+        derivs = derivs.expand(n, 2).contiguous()
+    return ctrl, n_ctrl, knots, derivs
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def spline_curves(kind, control_points, n_ctrl=None, n_interpolation=100, degree=0, knot_vectors=None,
+                  boundary_type=L.SPLINE_NOT_A_KNOT, first_derivatives=None, max_points=None, device_id=0, stream=None):
+    """t2d_spline_curves: the curves of n control polygons of one family ("bezier" / "bspline" / "cubic" or layout.SPLINE_*) in
+    one launch, asynchronous on `stream`.  The arguments are those of the three classes below.  Returns SplineCurves."""
+    import torch
+    kind, n, m, n_interpolation, degree, boundary_type, full = spline_check(kind, control_points, n_ctrl, n_interpolation, degree,
+                                                                            knot_vectors, boundary_type, first_derivatives)
+    lib = _ffi.lib()
+    dev, st = _stream_of(device_id, stream)
+    max_points = full if max_points is None else int(max_points)
+    with torch.cuda.stream(st):
+        ctrl, n_ctrl, knots, derivs = spline_inputs(dev, n, m, control_points, n_ctrl, knot_vectors, first_derivatives)
+        xy = torch.empty((n, max(max_points, 0), 2), dtype=torch.float64, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        _ffi.check(lib.t2d_spline_curves(device_id, n, kind, ctrl.data_ptr(), n_ctrl.data_ptr(), m, n_interpolation, degree, _ptr(knots),
+                                         boundary_type, _ptr(derivs), max_points, xy.data_ptr(), count.data_ptr(), st.cuda_stream),
+                   None, lib)
+    out = SplineCurves(xy, count)
+    out._inputs = (ctrl, n_ctrl, knots, derivs)   # (kept alive with the result)
+    return out
+
+
+class Bezier:
+    """Bezier (interpolator/bezier.py) for batches."""
+
+    @staticmethod
+    def get_curve(control_points, n_interpolation, order=None, n_ctrl=None, max_points=None, device_id=0, stream=None):
+        """Bezier.get_curve (bezier.py:16-44) for n control polygons in one launch.  control_points [n, m, 2], or [m, 2] for a batch
+        of one: numpy, or a float64 CUDA tensor (a contiguous one is read in place); n_ctrl int [n] (optional): row e uses its
+        first n_ctrl[e] points; n_interpolation >= 2 points per curve; order: None or m - 1, as in the reference.  max_points: the
+        rows of the result (default: n_interpolation).  Asynchronous on `stream` (a torch stream; default: the current one).
+        Returns SplineCurves.  The reference's ValueErrors are raised with its messages."""
+        shape = tuple(control_points.shape) if hasattr(control_points, "shape") else ()
+        if len(shape) not in (2, 3) or shape[-1] != 2:
+            raise ValueError(_SHAPE_MESSAGE)
+        m = shape[-2]
+        order = m - 1 if order is None else int(order)
+        if order < 1:
+            raise ValueError("Order must be greater than or equal to one.")
+        if m != order + 1:
+            raise ValueError("Number of control points must be equal to order plus one.")
+        return spline_curves(L.SPLINE_BEZIER, control_points, n_ctrl, n_interpolation, max_points=max_points, device_id=device_id,
+                             stream=stream)
+
+
+class BSpline:
+    """BSpline (interpolator/b_spline.py) for batches."""
+
+    @staticmethod
+    def get_curve(control_points, knot_vectors=None, degree=0, n_interpolation=100, n_ctrl=None, max_points=None, device_id=0,
+                  stream=None):
+        """BSpline.get_curve (b_spline.py:16-57) for n control polygons in one launch; the conventions of Bezier.get_curve.
+        knot_vectors [n, m + degree + 1] (or [m + degree + 1] for a batch of one), numpy or a float64 CUDA tensor; None: the
+        reference's default, np.linspace(0, 1, n_ctrl + degree + 1) per row, made on the device.  A row of n_ctrl[e] points uses
+        its first n_ctrl[e] + degree + 1 knots.  n_interpolation >= 1 points per curve at u_start + j (u_end - u_start) /
+        n_interpolation: the curve's end is not among them.  degree <= layout.SPLINE_MAX_DEGREE."""
+        return spline_curves(L.SPLINE_BSPLINE, control_points, n_ctrl, n_interpolation, degree, knot_vectors, max_points=max_points,
+                             device_id=device_id, stream=stream)
+
+
+class CubicSpline:
+    """CubicSpline (interpolator/cubic_spline.py) for batches."""
+
+    class BoundaryType(enum.Enum):
+        """Natural: zero second derivative at both ends; Clamped: the given first derivatives; NotAKnot: the first two and the last
+        two cubics are one cubic each."""
+        Natural = 1
+        Clamped = 2
+        NotAKnot = 3
+
+    @staticmethod
+    def get_curve(control_points, first_derivatives=(0, 0), n_interpolation=100, boundary_type=BoundaryType.NotAKnot, n_ctrl=None,
+                  max_points=None, device_id=0, stream=None):
+        """CubicSpline.get_curve (cubic_spline.py:36-84) for n control polygons in one launch; the conventions of Bezier.get_curve.
+        y as a function of strictly increasing x; (n_ctrl - 1) * n_interpolation + 1 points per curve, n_interpolation >= 2 per
+        segment (the abscissa is accumulated step by step, so a segment's last sample only approximates the next knot, which the
+        next segment then repeats exactly).  first_derivatives: a pair for every row or [n, 2], read under Clamped only;
+        boundary_type: a BoundaryType or 1 .. 3.  With three control points the NotAKnot system is singular and the curve is, for
+        most rows, the polyline through them, as in the reference.  max_points default: (m - 1) *
+        n_interpolation + 1."""
+        if isinstance(first_derivatives, tuple) and tuple(first_derivatives) == (0, 0):
+            first_derivatives = None
+        return spline_curves(L.SPLINE_CUBIC, control_points, n_ctrl, n_interpolation, 0, None, boundary_type, first_derivatives,
+                             max_points, device_id, stream)

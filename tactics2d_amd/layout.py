@@ -69,6 +69,13 @@ DUBINS_SLOTS = 6
 CURVE_WORD_BYTES = 48
 CURVE_DUBINS, CURVE_RS = 0, 1
 PROFILE_CURVE_ROUTES = 17
+# Bezier, B-spline and cubic spline curves (t2d_spline_curves / t2d_spline_routes): the families, the cubic spline's boundary
+# types, the caps of a launch, the curves that share a workgroup, the kernel id
+SPLINE_BEZIER, SPLINE_BSPLINE, SPLINE_CUBIC = 0, 1, 2
+SPLINE_NATURAL, SPLINE_CLAMPED, SPLINE_NOT_A_KNOT = 1, 2, 3
+SPLINE_MAX_CTRL, SPLINE_MAX_DEGREE = 32, 5
+SPLINE_CURVES_PER_BLOCK = 4
+PROFILE_SPLINE_ROUTES = 18
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),

@@ -557,6 +557,35 @@ class ParticipantPool:
         self._curve_inputs = (words, starts)   # (kept alive until the launch has run)
         return count
 
+    def spline_routes(self, kind, control_points, n_ctrl=None, n_interpolation=100, degree=0, knot_vectors=None, boundary_type=3,
+                      first_derivatives=None, route=0, count=None, stream=None):
+        """t2d_spline_routes: one Bezier / B-spline / cubic spline curve per env (kind "bezier" / "bspline" / "cubic" or
+        layout.SPLINE_*; control_points [n_env, m, 2] and the other arguments as in interpolator.Bezier / BSpline / CubicSpline
+        .get_curve, numpy or float64 CUDA tensors) into route `route` of each env's own route set, under the rules of curve_routes:
+        the route's vertex count is the capacity, vertices past the curve's points repeat its last point (for a B-spline its last
+        sample, not the curve's end), a row without a curve leaves the route as it is.  Needs set_routes with one set per env.
+        Returns the int32 CUDA tensor [n_env] of the curves' full point counts (`count`, or a new one).  Asynchronous."""
+        import torch
+        from . import interpolator as I
+        kind, n, m, n_interpolation, degree, boundary_type, _ = I.spline_check(kind, control_points, n_ctrl, n_interpolation, degree,
+                                                                               knot_vectors, boundary_type, first_derivatives)
+        if n != self.n_env:
+            raise ValueError(f"control_points must hold one control polygon per env: [{self.n_env}, m, 2]")
+        dev = torch.device("cuda", self.device_id)
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous()):
+            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):   # (uploads and conversions ahead of the launch, on its stream)
+            if count is None:
+                count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
+            inputs = I.spline_inputs(dev, n, m, control_points, n_ctrl, knot_vectors, first_derivatives)
+        ctrl, n_ctrl, knots, derivs = inputs
+        self._ck(self._lib.t2d_spline_routes(self._h, kind, ctrl.data_ptr(), n_ctrl.data_ptr(), m, n_interpolation, degree,
+                                             None if knots is None else knots.data_ptr(), boundary_type,
+                                             None if derivs is None else derivs.data_ptr(), int(route), count.data_ptr(), st))
+        self._spline_inputs = inputs   # (kept alive until the launch has run)
+        return count
+
     def route_vertices(self):
         """Zero-copy torch view float32 [n_vertices, 2] of the installed route sets' vertices on the device (t2d_route_vertices), in
         the order set_routes flattened them: what curve_routes writes into.  Valid until the routes are replaced or cleared.  The
