@@ -24,11 +24,11 @@
 //   2. broad phase -> compacted work queues -> dense narrow phase, three times (participant
 //      pairs, static polygons, lane polygons):
 //        * pairs: envs that fit a wave (A_pad <= 64) stage (x, y, R) in LDS and compare bounding circles on
-//          packed fp32 (two partners per v_pk_* instruction, 1 cm margin), each verdict shifted into the lane's
-//          candidate word by v_cmp + v_addc; an env that IS a wave sweeps a ring (lane i against i+1 .. i+32),
+//          packed fp32 (two partners per v_pk_* instruction, 1 cm margin), each verdict -- a sign bit -- shifted into the
+//          lane's candidate word by one v_alignbit_b32; an env that IS a wave sweeps a ring (lane i against i+1 .. i+32),
 //          so each unordered pair is tested once; larger envs walk an LDS spatial-hash grid (cell >=
 //          largest circum-diameter, atomicExch-built linked lists).
-//        * polygons: a branch-free box sweep over the env's polygons in the LDS record (same packed / addc form).
+//        * polygons: a branch-free box sweep over the env's polygons in the LDS record (same packed / sign-bit form).
 //      Survivors are compacted (one LDS atomic per lane) into a per-wave LDS queue and processed
 //      one entry per lane -- dense lanes instead of per-lane divergent loops, and no register-
 //      resident per-participant state, which keeps the kernel at 4 waves / SIMD.  Odd waves visit the
@@ -115,6 +115,12 @@ T2D_DEV Quad load_obb_lds(const double* base) {  // &s_v[0][lane], planes kBlock
         r.y[j] = base[(2 * j + 1) * kBlock];
     }
     return r;
+}
+
+// what the certifying filters take of a box (RectEdges): vertices 0, 1 and 3 of its planes and the centre of s_cxy
+T2D_DEV RectEdges load_rect_lds(const double* base, float cx, float cy) {
+    const double x0 = base[0], y0 = base[kBlock], x1 = base[2 * kBlock], y1 = base[3 * kBlock], x3 = base[6 * kBlock], y3 = base[7 * kBlock];
+    return RectEdges{x0 - x3, y0 - y3, x1 - x0, y1 - y0, (double)cx, (double)cy};
 }
 
 // ---- generic (slow, rare) paths: circles (pedestrians) against polygons streamed from LDS ------
@@ -236,16 +242,16 @@ T2D_DEV void wave_sync() {
 // called by all 64 lanes of the wave (mask 0 for idle lanes).
 template <bool SWAP, bool RING = false, class F>
 T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_id, uint32_t* queue, int* qcount,
-                                 int lane, F process, bool narrow = false, int ring_mask = 63) {
+                                 int lane, F process, bool narrow = false) {
     // entry = participant | other << 8.  SWAP = false: this lane is the participant (own_id = tid)
     // and the bits name the other object (id_base + bit); SWAP = true: this lane owns the other
     // object (own_id = polygon index) and the bits name participants (id_base + bit).
     // narrow (wave-uniform): every lane's mask fits in 32 bits -- the emit loop then runs on half the registers.
     auto entry = [&](int a) -> uint32_t {
-        if (RING) {  // bit a = the participant a + 1 places further round its env (pair broad phase, env <= wave)
-            const int other = id_base + ((own_id - id_base + 1 + a) & ring_mask);
-            return own_id < other ? (uint32_t)own_id | ((uint32_t)other << 8) : (uint32_t)other | ((uint32_t)own_id << 8);
-        }
+        // RING: bit a = the participant a + 1 places further round its env (pair broad phase, env <= wave).  The entry is
+        // (own_id | a << 8), a = offset - 1: who that is, and which of the two comes first, is worked out by `process` (process_ring), which
+        // runs densely, one pair per lane -- this loop the whole wave walks once per set bit of its busiest lane
+        if (RING) return (uint32_t)own_id | ((uint32_t)a << 8);
         return SWAP ? (uint32_t)(id_base + a) | ((uint32_t)own_id << 8) : (uint32_t)own_id | ((uint32_t)(id_base + a) << 8);
     };
     for (;;) {
@@ -1198,7 +1204,9 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         if (gl.has[1]) {
             const float4* sr = reinterpret_cast<const float4*>(s_geo + gl.off_safe) + env_local * kSafeRects;
             // box inside rectangle: max(xmin - lo_x, hi_x - xmax, ymin - lo_y, hi_y - ymax) <= 0, two packed additions
-            // with the box's (-lo, hi) pairs, a max3 and a max per rectangle (the form of the box sweeps below)
+            // with the box's (-lo, hi) pairs, a max3 and a max per rectangle (the form of the box sweeps below).
+            // (The compare stays here: the sign of the smallest of the four maxima -- the sweeps' sign-bit form -- gives the
+            // same flags and measured as a loss on the 512 x 32 intersection pool)
             typedef float f2s __attribute__((ext_vector_type(2)));
             const f2s cxp = {-box_lo_x, box_hi_x}, cyp = {-box_lo_y, box_hi_y};
 #pragma unroll
@@ -1238,17 +1246,18 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         const int ki = s_kind[i], kj = s_kind[j];
         bool hit;
         if (ki == T2D_SHAPE_OBB && kj == T2D_SHAPE_OBB) {
-            const Quad A = load_obb_lds(&s_v[0][i]), B = load_obb_lds(&s_v[0][j]);
 #ifndef T2D_NO_RECT_FILTER
             // two boxes: four projections certify the answer unless the boxes are within ~1e-7 m of touching
-            // (rect_pair_filter); only then -- practically never -- the wave runs the 32 orientations of the oracle's test
-            const int v = rect_pair_filter(A, B);
+            // (rect_pair_filter, on three vertices and the stored centre of each); only then -- practically never -- the
+            // wave reads the boxes whole and runs the 32 orientations of the oracle's test
+            const int v = rect_pair_filter(load_rect_lds(&s_v[0][i], s_cxy[0][i], s_cxy[1][i]), load_rect_lds(&s_v[0][j], s_cxy[0][j], s_cxy[1][j]));
             hit = v == 1;
             if (__ballot(v == 2) != 0ull) {
-                if (v == 2) hit = sat_quads(A, B);
+                asm volatile("" ::: "memory");
+                if (v == 2) hit = sat_quads(load_obb_lds(&s_v[0][i]), load_obb_lds(&s_v[0][j]));
             }
 #else
-            hit = sat_quads(A, B);
+            hit = sat_quads(load_obb_lds(&s_v[0][i]), load_obb_lds(&s_v[0][j]));
 #endif
         } else if (ki == T2D_SHAPE_OBB) {   // circle j against box i
             hit = circle_vs_generic((double)s_cxy[0][j], (double)s_cxy[1][j], rad_of(j), PolyRef{nullptr, &s_v[0][i], 4});
@@ -1263,6 +1272,13 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
             atomicOr(&s_flags[i], T2D_FLAG_COLLISION_DYNAMIC);
             atomicOr(&s_flags[j], T2D_FLAG_COLLISION_DYNAMIC);
         }
+    };
+    // an entry of the ring sweep's queue (participant | offset - 1 << 8, see compact_and_process) -> its unordered pair: the
+    // partner sits offset places further round the env, whose slots start at a multiple of A_pad
+    auto process_ring = [&](uint32_t e) {
+        const int own = (int)(e & 255u), a = (int)(e >> 8);
+        const int other = own ^ ((own ^ (own + 1 + a)) & (A_pad - 1));   // (own's env, the place (agent + 1 + a) mod A_pad)
+        process_pair((uint32_t)(own < other ? own : other) | ((uint32_t)(own < other ? other : own) << 8));
     };
     const KernargView ev_args = late_args();   // the event stages' layout offsets are fetched here, not at the kernel's entry
     const auto& gl2 = ev_args->geo_layout;
@@ -1280,7 +1296,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
             // certifies that, a box whose centre lies inside the polygon is a hit (rect_vs_convex_filter); the rest -- touching, overlapping, or separated only by an edge of the
             // box -- take the oracle's 32 orientations (both quads are read again there: held across the filter they cost
             // the kernel 19 spilled registers)
-            const int v = rect_vs_convex_filter(load_obb_lds(&s_v[0][i]), load_quad_f32(xy + 2 * v0, n));
+            const int v = rect_vs_convex_filter(load_rect_lds(&s_v[0][i], s_cxy[0][i], s_cxy[1][i]), load_quad_f32(xy + 2 * v0, n));
             hit = v == 1;
             if (__ballot(v == 2) != 0ull) {
                 asm volatile("" ::: "memory");
@@ -1319,15 +1335,17 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         uint32_t bits = point_in_quad(load_quad_f32(xy + 2 * v0, n), cx, cy) ? 1u : 0u;   // 3 or 4 vertices (fans of quads)
         bool cut = false;
         if (s_kind[i] == T2D_SHAPE_OBB) {
+            // (c = the stored centre -- within 4.5e-13 m of the centre of the box the exact test sees, see RectEdges: inside the
+            // margin's thousandfold.  The box is read whole once, ahead of the loop: in lane-dense envs some lane of the wave has
+            // a piece through its pose on most trips, and reading it again for each of them made the intersection pool 4 % slower)
             const Quad A = load_obb_lds(&s_v[0][i]);
             const double px = A.x[0] - A.x[3], py = A.y[0] - A.y[3], qx = A.x[1] - A.x[0], qy = A.y[1] - A.y[0];
-            const double c2x = A.x[0] + A.x[2], c2y = A.y[0] + A.y[2];   // twice the centre
             for (int b = b0; b < b1; ++b) {
                 const double2 Pa = bnd[2 * b], Pb = bnd[2 * b + 1];
                 const double nx = Pa.y - Pb.y, ny = Pb.x - Pa.x;
-                const double s2 = __builtin_fma(nx, c2x - 2.0 * Pa.x, ny * (c2y - 2.0 * Pa.y));
+                const double s1 = __builtin_fma(nx, cx - Pa.x, ny * (cy - Pa.y));
                 const double e2 = __builtin_fabs(__builtin_fma(nx, px, ny * py)) + __builtin_fabs(__builtin_fma(nx, qx, ny * qy));
-                const bool clear = __builtin_fabs(s2) > e2 + 2e-9 * (__builtin_fabs(nx) + __builtin_fabs(ny));
+                const bool clear = __builtin_fabs(s1 + s1) > e2 + 2e-9 * (__builtin_fabs(nx) + __builtin_fabs(ny));
                 if (__ballot(!clear) != 0ull) {
                     if (!clear) cut |= piece_meets_quad_interior(A, Pa.x, Pa.y, Pb.x, Pb.y);
                 }
@@ -1376,18 +1394,27 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         if (log2A > 0) {
             // (x, y, R) of the wave's 64 lanes go through LDS (the wave's queue storage, idle until the
             // compaction below) and come back two agents at a time as wave-uniform 8-B reads; the
-            // distance test runs on packed fp32 (v_pk_*: 2 agents per instruction) and each verdict is
-            // shifted into the lane's candidate word by v_cmp + v_addc (carry-in = the compare mask):
-            // 5 VALU instructions per agent instead of 11.  Agents are visited in descending order so
-            // that agent a lands on bit a.  Inactive lanes are parked at x = 1e30 (distance^2 = inf).
+            // distance test runs on packed fp32 (v_pk_*: 2 agents per instruction): g = (R_i + R_j)^2 - d^2 as one
+            // packed fma, whose SIGN is the verdict "clear of each other", shifted into the lane's word by one
+            // v_alignbit_b32 (h = h << 1 | sign) and inverted once after the sweep: 4 VALU instructions per agent
+            // (round 2's v_cmp + v_addc form: 5; the plain one: 11).  Agents are visited in descending order so
+            // that agent a lands on bit a.  Inactive lanes are parked at x = 1e30 (distance^2 = inf, g = -inf).
+            // Still a superset of what the exact tests accept: two shapes that touch have centres no further apart
+            // than the sum of their (bounding) radii, and each R32 carries 5 mm on top of its radius, so for them
+            // g >= (R + 1 cm)^2 - R^2 > 2e-2 R (R the sum of the radii), against a rounding of g -- the fp32 differences,
+            // their squares, the sum and the fma, each relative 2^-24 of terms no larger than (R + 1 cm)^2 -- below
+            // 4e-7 (R + 1 cm)^2, smaller than 2e-2 R for any R < 10 km: g > 0, sign clear.  g = +0 counts as a candidate
+            // as q <= r did; only pairs within that rounding of the 1 cm margin can differ from the compare form.
             typedef float f2 __attribute__((ext_vector_type(2)));
             float* const bx = reinterpret_cast<float*>(queue);
             float* const by = bx + 96;
             float* const bR = by + 96;
             static_assert(3 * 96 <= kQueueCap, "broad-phase staging must fit in the wave's queue");
             // (the centre comes back from LDS: carried in registers since the pose phase it cost the kernel a spill)
-            const float fx_b = s_cxy[0][tid], fy = s_cxy[1][tid];
-            const float px = active ? fx_b : 1e30f;
+            // (an inactive lane never wrote its centre: what sits there may be a NaN, whose sign would be read as a verdict --
+            // both coordinates are parked)
+            const float fx_b = s_cxy[0][tid], fy_b = s_cxy[1][tid];
+            const float px = active ? fx_b : 1e30f, fy = active ? fy_b : 0.0f;
             // every env of the wave gets a segment of 1.5 * A_pad entries: its agents, then its first half again, so
             // that the ring sweep below reads agent + offset without wrapping (64 / A_pad segments: 96 entries in all)
             const int n_off = A_pad >> 1;                           // partners per lane: agent + 1 .. agent + A_pad / 2
@@ -1406,7 +1433,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
             // pair is tested once (offset d lands on bit d - 1; offset n_off is seen from both ends and kept by the
             // lower half).  K pairs of offsets per batch: all 3K (unaligned 2 x 4 B) LDS reads are issued before the
             // first compare, so one LDS latency is exposed per batch instead of per pair.
-            uint32_t h = 0u;
+            uint32_t h = ~0u;   // (all ones: the sweep shifts n_off "clear" bits in underneath, the complement is the candidate word)
             auto batch = [&](uint32_t& hh, int top, auto kc) {   // offsets top + 2K - 1 ... top
                 constexpr int K = decltype(kc)::value;
                 f2 ox[K], oy[K], oR[K];
@@ -1420,11 +1447,10 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const f2 dx = px2 - ox[k], dy = py2 - oy[k], rr = pR2 + oR[k];
-                    const f2 q = __builtin_elementwise_fma(dy, dy, dx * dx), r = rr * rr;
-                    asm volatile("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
-                                 : "+v"(hh) : "v"(q.y), "v"(r.y) : "vcc");
-                    asm volatile("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
-                                 : "+v"(hh) : "v"(q.x), "v"(r.x) : "vcc");
+                    const f2 q = __builtin_elementwise_fma(dy, dy, dx * dx);
+                    const f2 g = __builtin_elementwise_fma(rr, rr, -q);   // (R_i + R_j)^2 - distance^2: sign set = clear of each other
+                    hh = __builtin_amdgcn_alignbit(hh, __float_as_uint(g.y), 31);   // hh = hh << 1 | sign
+                    hh = __builtin_amdgcn_alignbit(hh, __float_as_uint(g.x), 31);
                 }
             };
             using K1 = std::integral_constant<int, 1>;
@@ -1432,10 +1458,15 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
             if (log2A == 6) {          // env == wave: constant trip count, fully unrolled
 #pragma unroll
                 for (int top = 25; top >= 1; top -= 8) batch(h, top, K4{});
+                h = ~h;                // (the sweep collected "clear" bits under the ones h started with: candidates = the zeros)
             } else if (n_off >= 8) {   // A_pad = 16 or 32
                 for (int top = n_off - 7; top >= 1; top -= 8) batch(h, top, K4{});
+                h = ~h;
             } else if (n_off >= 2) {   // A_pad = 4 or 8
+                // (one or two trips: unrolled by the compiler, this loop's trip arithmetic sat in spilled scalars)
+#pragma unroll 1
                 for (int top = n_off - 1; top >= 1; top -= 2) batch(h, top, K1{});
+                h = ~h;
             } else {                   // A_pad = 2: the one partner
                 const float dx = px - bx[slot + 1], dy = fy - by[slot + 1], rr = R32 + bR[slot + 1];
                 h = (dx * dx + dy * dy <= rr * rr) ? 1u : 0u;
@@ -1445,7 +1476,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         }
         T2D_MARK(3);
         if (!active || (T2D_PROBE_SKIP & 2)) cand = 0ull;
-        compact_and_process<false, true>(cand, slot0, tid, queue, qcount, lane, process_pair, true, A_pad - 1);
+        compact_and_process<false, true>(cand, slot0, tid, queue, qcount, lane, process_ring, true);
     } else {
         // spatial-hash walk; pairs go straight to the narrow phase (i < j de-duplicates)
         if (active) {
@@ -1478,9 +1509,13 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         // box-vs-box sweep of boxes [first, first + cn) of `bb`: the box's float4 (xmin, xmax, ymin, ymax) comes from the LDS
         // record (one 16-B read, wave-uniform address when the env is a wave), the four inequalities collapse into
         // max(xmin - hi_x, lo_x - xmax, ymin - hi_y, lo_y - ymax) <= 0 -- two packed subtractions with the participant's
-        // (-hi, lo) pairs, one max3, one max -- and v_cmp + v_addc shifts the verdict into the mask (descending order, so
-        // box q lands on bit q).  6 VALU per box instead of ~11.  (ox, oy) = (-hi_x, lo_x), (-hi_y, lo_y) of the
-        // participant's box, or of a point.
+        // (-hi, lo) pairs, one max3, one max -- and the SIGN of that maximum m is the verdict: one v_alignbit_b32 shifts it
+        // into the mask (h = h << 1 | sign; descending order, so box q lands on bit q).  5 VALU per box (v_cmp + v_addc: 6;
+        // the plain form: ~11).  (ox, oy) = (-hi_x, lo_x), (-hi_y, lo_y) of the participant's box, or of a point.
+        // Against m <= 0 the sign loses exactly m = +0 (m = -0 is kept).  Still a superset of what the exact tests accept:
+        // the pose box was rounded OUTWARDS by |x| 1.2e-7 + 1e-6 past the fp32 rounding of the fp64 extent (2^-24 |x|), the
+        // polygon's box is the exact extent of its fp32 vertices, and a rounded fp32 difference keeps the sign of the exact
+        // one -- so a pose that touches or overlaps the polygon has all four differences below zero by 1e-6 or more: m < 0.
         typedef float f2p __attribute__((ext_vector_type(2)));
         auto box_sweep = [&](const float4* bb, int first, int cn, const f2p bxp, const f2p byp) -> unsigned long long {
             uint32_t hw[2] = {0u, 0u};
@@ -1492,12 +1527,14 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                     const f2p tx = {b.x, -b.y}, ty = {b.z, -b.w};
                     const f2p dx = tx + bxp, dy = ty + byp;   // (xmin - hi_x, lo_x - xmax), (ymin - hi_y, lo_y - ymax)
                     const float m = __builtin_fmaxf(__builtin_fmaxf(dx.x, dx.y), __builtin_fmaxf(dy.x, dy.y));
-                    asm volatile("v_cmp_ge_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(h) : "v"(m) : "vcc");
+                    h = __builtin_amdgcn_alignbit(h, __float_as_uint(m), 31);   // h = h << 1 | sign(m)
                 };
                 // the (top & 3) highest boxes one at a time, the rest four per trip with the four 16-B reads issued
                 // before the first compare: one LDS round trip per four boxes instead of one each
                 int a = top - 1;
+#pragma unroll 1
                 for (; (a & 3) != 3 && a >= 0; --a) verdict(bb[first + hb * 32 + a]);
+#pragma unroll 1
                 for (; a >= 3; a -= 4) {
                     const float4* q = bb + first + hb * 32 + a;
                     const float4 b0 = q[0], b1 = q[-1], b2 = q[-2], b3 = q[-3];

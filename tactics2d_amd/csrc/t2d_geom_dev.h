@@ -57,57 +57,74 @@ T2D_DEV bool sat_quads(const Quad& A, const Quad& B) {
     return !separated;
 }
 
+// A participant's box as the two filters below take it: the full edge vectors P = v0 - v3 (length) and Q = v1 - v0 (width)
+// -- three of its four vertices -- and its centre c.  The step kernel has the centre as the stored fp32 state, exact in
+// fp64 (rect_edges_of: from the vertices, for callers that hold a Quad).  The box the exact tests see is the one the pose
+// phase wrote -- vertex = fl(c +- offset), one rounding each, <= 2^-53 |coordinate| (4.5e-13 m at 4 km) off the exact
+// rectangle about c -- so the centre of THAT box and c differ by no more than that: part of the roundings quoted below.
+struct RectEdges {
+    double px, py, qx, qy, cx, cy;
+};
+
+T2D_DEV RectEdges rect_edges_of(const Quad& A) {
+    return RectEdges{A.x[0] - A.x[3], A.y[0] - A.y[3], A.x[1] - A.x[0], A.y[1] - A.y[0], 0.5 * (A.x[0] + A.x[2]), 0.5 * (A.y[0] + A.y[2])};
+}
+
 // Certifying filter in front of sat_quads for two RECTANGLES (participant boxes: vertex order front-right, front-left,
 // rear-left, rear-right, participant/element/vehicle.py:132-142).  Two rectangles are disjoint iff one of their four edge
 // directions separates them, so four projections decide what sat_quads decides with 32 orientations -- where the answer is
-// not a matter of rounding.  With the full edge vectors P = v0 - v3 (length), Q = v1 - v0 (width) and D = twice the centre
-// offset, the gap along n is  |n.D| - (|n.PA| + |n.QA| + |n.PB| + |n.QB|) = 2 |n| x (distance between the projections).
+// not a matter of rounding.  With the full edge vectors P = v0 - v3 (length), Q = v1 - v0 (width) and d = the centre
+// offset, the gap along n is  2 |n.d| - (|n.PA| + |n.QA| + |n.PB| + |n.QB|) = 2 |n| x (distance between the projections).
 // Returns 0: separated by more than kRectMargin / (2 |n|) >= 2.5e-8 m along some edge direction (the edge of that box
 // facing the other one then has all four vertices of the other strictly outside by that much: sat_quads finds it);
 // 1: the projections overlap by more than that on all four (every edge of either box then has a vertex of the other box
 // inside by that much: sat_quads finds no separating edge); 2: closer to touching than that -- undecided, the caller runs
-// sat_quads.  The rounding of either evaluation is ~1e-11 m, three orders below the margin, so 0 / 1 are sat_quads' answers.
+// sat_quads.  The rounding of either evaluation is ~1e-11 m (the filter's: the edge vectors and d one rounding of a
+// coordinate each, ~1e-12 m, then sums of five products of a few metres; plus the 4.5e-13 m between c and the box's own
+// centre), three orders below the margin, so 0 / 1 are sat_quads' answers.
 constexpr double kRectMargin = 1e-6;
-T2D_DEV int rect_pair_filter(const Quad& A, const Quad& B) {
-    const double pax = A.x[0] - A.x[3], pay = A.y[0] - A.y[3], qax = A.x[1] - A.x[0], qay = A.y[1] - A.y[0];
-    const double pbx = B.x[0] - B.x[3], pby = B.y[0] - B.y[3], qbx = B.x[1] - B.x[0], qby = B.y[1] - B.y[0];
-    const double dx = (B.x[0] + B.x[2]) - (A.x[0] + A.x[2]), dy = (B.y[0] + B.y[2]) - (A.y[0] + A.y[2]);
+T2D_DEV int rect_pair_filter(const RectEdges& A, const RectEdges& B) {
+    const double pax = A.px, pay = A.py, qax = A.qx, qay = A.qy;
+    const double pbx = B.px, pby = B.py, qbx = B.qx, qby = B.qy;
+    const double dx = B.cx - A.cx, dy = B.cy - A.cy;
     auto dot = [](double ax, double ay, double bx, double by) { return __builtin_fma(ax, bx, ay * by); };
     const double papb = dot(pax, pay, pbx, pby), paqb = dot(pax, pay, qbx, qby);
     const double qapb = dot(qax, qay, pbx, pby), qaqb = dot(qax, qay, qbx, qby);
     // (P.Q of one box is zero up to rounding, ~1e-15 of the margin: left out)
-    const double g0 = __builtin_fabs(dot(pax, pay, dx, dy)) - (dot(pax, pay, pax, pay) + __builtin_fabs(papb) + __builtin_fabs(paqb));
-    const double g1 = __builtin_fabs(dot(qax, qay, dx, dy)) - (dot(qax, qay, qax, qay) + __builtin_fabs(qapb) + __builtin_fabs(qaqb));
-    const double g2 = __builtin_fabs(dot(pbx, pby, dx, dy)) - (dot(pbx, pby, pbx, pby) + __builtin_fabs(papb) + __builtin_fabs(qapb));
-    const double g3 = __builtin_fabs(dot(qbx, qby, dx, dy)) - (dot(qbx, qby, qbx, qby) + __builtin_fabs(paqb) + __builtin_fabs(qaqb));
+    const double g0 = __builtin_fma(2.0, __builtin_fabs(dot(pax, pay, dx, dy)), -(dot(pax, pay, pax, pay) + __builtin_fabs(papb) + __builtin_fabs(paqb)));
+    const double g1 = __builtin_fma(2.0, __builtin_fabs(dot(qax, qay, dx, dy)), -(dot(qax, qay, qax, qay) + __builtin_fabs(qapb) + __builtin_fabs(qaqb)));
+    const double g2 = __builtin_fma(2.0, __builtin_fabs(dot(pbx, pby, dx, dy)), -(dot(pbx, pby, pbx, pby) + __builtin_fabs(papb) + __builtin_fabs(qapb)));
+    const double g3 = __builtin_fma(2.0, __builtin_fabs(dot(qbx, qby, dx, dy)), -(dot(qbx, qby, qbx, qby) + __builtin_fabs(paqb) + __builtin_fabs(qaqb)));
     const double g = __builtin_fmax(__builtin_fmax(g0, g1), __builtin_fmax(g2, g3));
     return g > kRectMargin ? 0 : (g < -kRectMargin ? 1 : 2);
 }
+T2D_DEV int rect_pair_filter(const Quad& A, const Quad& B) { return rect_pair_filter(rect_edges_of(A), rect_edges_of(B)); }
 
 // Certificate of separation in front of sat_quads(A, B) for a RECTANGLE A (participant box) and a convex CCW polygon B:
 // true when some edge of B has the whole of A strictly on its outer side -- A's support along the edge's outward normal
 // n = (ey, -ex) does not reach the edge's line: n.(c - B_j) - (|n.P| + |n.Q|) / 2 > margin (P, Q the box's edge vectors, c its
 // centre; everything below carries the factor 2).  Then orient(B_j, B_k, A_i) < 0 for all four vertices by more than the margin
-// (1e-9 |n|, a nanometre: a thousand times the rounding of either evaluation), which is the oracle's separating-edge rule.
+// (1e-9 |n|, a nanometre: a thousand times the rounding of either evaluation -- c - B_j is exact or one rounding of a coordinate,
+// the box's own centre lies within 4.5e-13 m of c, see RectEdges), which is the oracle's separating-edge rule.
 // Padded vertices (triangles repeat vertex 0) give a zero normal: never certifies.
 // Returns 0: separated (certified), 1: intersecting (certified: the box's centre lies strictly inside B -- inside every edge
 // by the same margin -- so no edge of either polygon can have all of the other's vertices outside), 2: undecided.
-T2D_DEV int rect_vs_convex_filter(const Quad& A, const Quad& B) {
-    const double px = A.x[0] - A.x[3], py = A.y[0] - A.y[3], qx = A.x[1] - A.x[0], qy = A.y[1] - A.y[0];
-    const double c2x = A.x[0] + A.x[2], c2y = A.y[0] + A.y[2];
+T2D_DEV int rect_vs_convex_filter(const RectEdges& A, const Quad& B) {
     bool out = false, in = true;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int k = (j + 1) & 3;
         const double nx = B.y[k] - B.y[j], ny = B.x[j] - B.x[k];
-        const double s2 = __builtin_fma(nx, c2x - 2.0 * B.x[j], ny * (c2y - 2.0 * B.y[j]));
-        const double e2 = __builtin_fabs(__builtin_fma(nx, px, ny * py)) + __builtin_fabs(__builtin_fma(nx, qx, ny * qy));
+        const double s1 = __builtin_fma(nx, A.cx - B.x[j], ny * (A.cy - B.y[j]));
+        const double s2 = s1 + s1;   // (exact)
+        const double e2 = __builtin_fabs(__builtin_fma(nx, A.px, ny * A.py)) + __builtin_fabs(__builtin_fma(nx, A.qx, ny * A.qy));
         const double m = 2e-9 * (__builtin_fabs(nx) + __builtin_fabs(ny));
         out |= s2 - e2 > m;
         in &= (s2 < -m) | ((nx == 0.0) & (ny == 0.0));   // (the zero-length edge of a padded triangle says nothing)
     }
     return out ? 0 : (in ? 1 : 2);
 }
+T2D_DEV int rect_vs_convex_filter(const Quad& A, const Quad& B) { return rect_vs_convex_filter(rect_edges_of(A), B); }
 
 T2D_DEV bool point_in_quad(const Quad& B, double x, double y) {
     bool in = true;

@@ -569,12 +569,13 @@ T2D_DEV StepOut step_pointmass(PF P, double x, double y, double vx, double vy, d
     double nvx = vx + ax * dt;
     double nvy = vy + ay * dt;
     double ns = __builtin_sqrt(nvx * nvx + nvy * nvy);
-    double ox, oy, ovx, ovy;
+    double ox, oy, ovx, ovy, ospeed;
     if (!(flags & T2D_RANGE_SPEED) || (lo <= ns && ns <= hi)) {
         ox = x + vx * dt + 0.5 * ax * (dt * dt);
         oy = y + vy * dt + 0.5 * ay * (dt * dt);
         ovx = nvx;
         ovy = nvy;
+        ospeed = ns;   // sqrt(ovx * ovx + ovy * ovy) on the same operands: the same bits, already computed
     } else {
         bool lower = ns < lo;
         double bound = lower ? lo : hi;
@@ -596,8 +597,9 @@ T2D_DEV StepOut step_pointmass(PF P, double x, double y, double vx, double vy, d
         ovy = vy + ay * t1;
         ox = x + vx * t1 + 0.5 * ax * (t1 * t1) + ovx * t2;
         oy = y + vy * t1 + 0.5 * ay * (t1 * t1) + ovy * t2;
+        ospeed = __builtin_sqrt(ovx * ovx + ovy * ovy);
     }
-    return StepOut{ox, oy, atan2_det(ovy, ovx), __builtin_sqrt(ovx * ovx + ovy * ovy), ovx, ovy, ax, ay, true};
+    return StepOut{ox, oy, atan2_det(ovy, ovx), ospeed, ovx, ovy, ax, ay, true};
 }
 
 
