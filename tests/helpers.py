@@ -347,6 +347,21 @@ def count_vertices_in_but_not_contained(O, sc, flags, envs=None):
     return n
 
 
+def lane_safe_rects(lanes):
+    """t2d_lane_safe_rects for every env of a lane CSR triple: [n_env, SAFE_RECTS, 4] fp32 (xmin, xmax, ymin, ymax; an unused slot is
+    not finite) -- the rectangles inside which the step kernel certifies a pose as on-lane without the lane sweep.  Host-only entry
+    point of libt2d_hip.so: no device is touched."""
+    import ctypes as C
+    from tactics2d_amd import _ffi, layout as L
+    eo, vo, xy = (np.ascontiguousarray(a, dt) for a, dt in zip(lanes, (np.int32, np.int32, np.float32)))
+    n_env = len(eo) - 1
+    out = np.zeros((n_env, L.SAFE_RECTS, 4), np.float32)
+    rc = _ffi.lib().t2d_lane_safe_rects(n_env, eo.ctypes.data_as(C.c_void_p), vo.ctypes.data_as(C.c_void_p), xy.ctypes.data_as(C.c_void_p),
+                                        out.ctypes.data_as(C.c_void_p))
+    assert rc == 0, rc
+    return out
+
+
 def gpu_collide(sc):
     from tactics2d_amd import layout as L
     from tactics2d_amd.pool import ParticipantPool

@@ -1,5 +1,12 @@
 """GPU parity of t2d_collide / t2d_step (through the C ABI): event flags bit-exact against the
-oracle's brute-force fp64 evaluation on identical fp32 inputs.  Run with -m gpu."""
+oracle's brute-force fp64 evaluation on identical fp32 inputs.  Run with -m gpu.
+
+These are not saturation tests.  Measured on the CPU for the nine scenes of test_flags_bit_exact, per wave as the kernel assigns lanes
+to waves, against the step kernel's queue capacity kQueueCap = 288:
+    candidate pairs (bounding circles), densest scene (40 x 64, half inactive)    279
+    candidate pairs, next densest scene                                            109
+    pose-box / polygon-box overlaps                                                 81
+No wave reaches a second round of compact_and_process; tests/test_gpu_saturation.py is where the queues overflow."""
 import numpy as np
 import pytest
 
