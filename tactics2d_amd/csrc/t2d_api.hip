@@ -31,9 +31,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1, ncclInt32 = 2, ncclUint32 = 3 } nccl
 
 #include "t2d_pool.h"
 #include "t2d_host.h"
-#ifndef T2D_LOOP_MAX_WGS_PER_CU
-#define T2D_LOOP_MAX_WGS_PER_CU 2
-#endif
+#include "t2d_step_plan.h"
 #ifdef T2D_DEBUG_HOOKS
 #include "../../include/t2d_debug.h"
 #endif
@@ -447,6 +445,8 @@ int t2d_create(int32_t n_env, int32_t max_agents, int32_t device_id, t2d_pool** 
     t2d_pool* p = new (std::nothrow) t2d_pool();
     if (!p) return fail(nullptr, T2D_ERR_NOMEM, "host allocation failed");
     p->device = device_id;
+    // (read once, here; 0 where the query fails: such a pool takes no form that counts on resident workgroups)
+    (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, device_id);
     p->v.n_env = n_env;
     p->v.A = max_agents;
     p->v.N = n_env * max_agents;
@@ -992,7 +992,6 @@ static int prepare_interval(t2d_pool* p, int interval_ms, hipStream_t s) {
         // ... and only pools that put at least two waves on every SIMD: a lone wave is a latency chain, and the table's scalar
         // loads (cache misses on first touch) lengthen it by more than the twenty loop trips they replace (same-box A/B,
         // 512 x 32 envs one launch per step: 12.8 -> 13.4 us with the series)
-        if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
         const bool fills = (long long)p->v.N >= 2LL * 64 * 4 * (p->device_cus > 0 ? p->device_cus : 256);
         kinematics_resum_table(p->v, p->kin_resum && (fills || p->kin_resum_forced) ? kn : 0);
         touch(p, s);
@@ -1005,6 +1004,36 @@ static int prepare_interval(t2d_pool* p, int interval_ms, hipStream_t s) {
 // Replayed participants (T2D_MODEL_REPLAY rows): pools that hold one keep helper launches around the step, as pools with a drift
 // row do -- no single-ego kernel, no chained form, controllers in a launch of their own
 static bool side_models(const t2d_pool* p) { return p->has_drift || p->replay_types != 0u; }
+
+// what plan_step (t2d_step_plan.h) decides the form of the pool's step launch from.  t2d_step fills it on every call: plain reads,
+// no allocation, no walk over a vector
+static StepFacts step_facts(const t2d_pool* p) {
+    StepFacts f{};
+    f.n_env = p->v.n_env;
+    f.A = p->v.A;
+    f.epb = p->v.geo_layout.epb;
+    f.device_cus = p->device_cus;
+    f.lane_polys = p->hgeo[1].present && !p->hgeo[1].env_off.empty() ? (long long)p->hgeo[1].env_off.back() : 0;
+    f.has_geo = p->v.geo != nullptr;
+    f.has_static = p->v.geo_layout.has[0];
+    f.has_lanes = p->v.geo_layout.has[1];
+    f.wgmap = p->v.wgmap != nullptr;
+    f.overlapped = p->v.overlapped;
+    f.fused_step = p->fused_step;
+    f.grid_tier = p->grid_tier;
+    f.side_models = side_models(p);
+    f.scene_regen = p->scene_regen;
+    f.ego_eligible = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
+    f.iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;
+    f.idm_on = p->idm.on;
+    f.chain_steps = p->chain_steps;
+    f.chain_loop = p->chain_loop;
+    f.chain_pipe = p->chain_pipe;
+    f.chain_pipe2 = p->chain_pipe2;
+    f.split_steps = p->split_steps;
+    f.chain_depth = p->chain_depth;
+    return f;
+}
 
 // what must hold before a stepping call enqueues anything for a pool with replayed participants
 static int replay_check(t2d_pool* p, int interval_ms) {
@@ -1051,17 +1080,6 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     return record_event(p, 0, s, false);
 }
 
-// a pool with installed IDM controllers whose step launch runs them itself (envs of 2..64 participants: an env's positions
-// then sit in one wave's LDS slots; no IoU events: those pools keep the general instantiations): every workgroup ahead of
-// its integrator (t2d_step, the chained form of t2d_step_n), or the integrator waves of the PIPE form where the pool is
-// small enough for it.  t2d_set_step_chaining(pool, 0, *) keeps idm_kernel a launch of its own (tests hold the two
-// against each other).
-static bool idm_in_step(t2d_pool* p) {
-    // (not pools with SingleTrackDrift participants: drift_kernel runs between the controllers and the step launch and reads
-    // the accelerations the controllers wrote -- t2d_step's order is IDM, drift, step -- so there idm_kernel stays a launch)
-    return p->idm.on && p->chain_steps && p->fused_step && !p->grid_tier && !side_models(p) && p->v.A >= 2 && p->v.A <= 64 &&
-           !(p->status_cfg.check_no_action || p->status_cfg.check_arrival);
-}
 static void fill_idm(t2d::PoolView& v, t2d_pool* p) {
     v.idm_rows = p->idm.view.rows;
     v.idm_ctrl_all = p->idm.view.ctrl_id;
@@ -1070,36 +1088,20 @@ static void fill_idm(t2d::PoolView& v, t2d_pool* p) {
     v.idm_act0_own = (float*)p->field_ptr[T2D_F_ACT0];
     v.idm_act1_own = (float*)p->field_ptr[T2D_F_ACT1];
 }
-static bool idm_in_pipe(t2d_pool* p) {
-    if (!idm_in_step(p) || !p->chain_loop || !p->chain_pipe) return false;
-    if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
-    const int wgs = (p->v.n_env + p->v.geo_layout.epb - 1) / p->v.geo_layout.epb;
-    return p->device_cus > 0 && wgs <= p->device_cus;
-}
 
-// small pools of 33..64-agent envs: the fused step gives every env a workgroup of its own (collide_kernel<..., SPLIT>)
-static bool use_split(t2d_pool* p) {
-    if (!p->split_steps) return false;
-    if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
-    int log2A = 1;
-    while ((1 << log2A) < p->v.A) ++log2A;
-    return t2d::split_eligible(p->v, p->status_cfg, log2A, p->device_cus);
-}
-
-static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStream_t s, int fuse_variant = -1) {
+// events (and status) of the poses as they are -- or, `step` = the plan of a fused one-launch step, the whole step
+static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStream_t s, const StepPlan* step = nullptr) {
     int rc;
     touch(p, s);
+    const int fuse_variant = step ? p->integrator_variant : -1;
     const int kid = fuse_variant >= 0 ? 2 : 1;
     if ((rc = record_event(p, kid, s, true))) return rc;
-    // single-ego pools (ParkingEnv: one box-shaped participant per env, no lanes) step with one WAVE per env
-    // (t2d_ego.hip) instead of one lane per participant; same arithmetic, same results (t2d_set_ego_kernel(pool, 0)
-    // keeps such a pool on the general kernel: the two are held against each other in tests/test_gpu_ego.py)
     p->scene_committed_in_step = false;
     if (p->grid_tier) {   // the map's verdicts for the poses as they are now, ahead of the event kernel that ORs them in
         if (fuse_variant >= 0) return fail(p, T2D_ERR_STATE, "internal: a grid-tier pool took the fused step");
         T2D_HIP(p, t2d::launch_map_events(p->v, p->mapgrid, p->d_grid_seg, p->d_map_flags, s));
     }
-    if (fuse_variant >= 0 && p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present) {
+    if (step && step->ego) {
         t2d::PoolView v = p->v;
         // staged scene regeneration: the step's own epilogue moves finished envs into their next lot (no launch behind it)
         if (with_status && p->scene_regen && p->scene.ring > 0 && p->d_scene_view) {
@@ -1109,12 +1111,8 @@ static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStrea
         T2D_HIP(p, t2d::launch_ego_step(v, p->status_cfg, interval_ms, fuse_variant, s));
     } else {
         t2d::PoolView v = p->v;
-        const bool idm_fused = fuse_variant >= 0 && idm_in_step(p);
-        // (one workgroup per env fills the GPU with a quarter of the envs: for a pool that has the GPU to itself, not for env
-        // groups whose launches are meant to overlap -- round 4: a group of 1024 envs took every workgroup slot and the groups
-        // ran one after the other, 44 us per step of 4 groups)
-        v.split_step = fuse_variant >= 0 && !idm_fused && !p->v.overlapped && use_split(p);
-        if (idm_fused) fill_idm(v, p);
+        v.split_step = step && step->split;
+        if (step && step->idm_fused) fill_idm(v, p);
         T2D_HIP(p, t2d::launch_collide(v, p->status_cfg, with_status, interval_ms, fuse_variant, s));
     }
     return record_event(p, kid, s, false);
@@ -1190,7 +1188,8 @@ int t2d_check_status(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
 
 int t2d_step(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if (!p) return T2D_ERR_INVALID;
-    if (!p->fused_step || p->grid_tier) {
+    const StepPlan plan = plan_step(step_facts(p), 1);
+    if (!plan.fused) {
         int rc = t2d_integrate(p, interval_ms, hip_stream);
         if (rc != T2D_OK) return rc;
         return t2d_check_status(p, interval_ms, hip_stream);
@@ -1202,11 +1201,11 @@ int t2d_step(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
     if ((rc = replay_check(p, interval_ms))) return rc;
     if ((rc = prepare_interval(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     if ((rc = claim_record_slot(p, (hipStream_t)hip_stream))) return rc;
-    // (installed IDM controllers: a launch of their own ahead of the step -- or, idm_in_step, the front of the step launch)
-    if (p->idm.on && !idm_in_step(p) && (rc = idm_impl(p, (hipStream_t)hip_stream))) return rc;
+    // (installed IDM controllers: a launch of their own ahead of the step -- or, plan.idm_fused, the front of the step launch)
+    if (p->idm.on && !plan.idm_fused && (rc = idm_impl(p, (hipStream_t)hip_stream))) return rc;
     if (p->has_drift && (rc = drift_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
     if (p->replay_types && (rc = replay_impl(p, interval_ms, (hipStream_t)hip_stream))) return rc;
-    rc = collide_impl(p, true, interval_ms, (hipStream_t)hip_stream, p->integrator_variant);
+    rc = collide_impl(p, true, interval_ms, (hipStream_t)hip_stream, &plan);
     if (rc == T2D_OK) p->step_count++;
     if (rc == T2D_OK) rc = regenerate_done_scenes(p, (hipStream_t)hip_stream);
     return rc;
@@ -1227,14 +1226,10 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_step_n");
     if (interval_ms <= 0) return fail(p, T2D_ERR_INVALID, "interval_ms must be positive");
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
-    const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;   // per-env history read by the epilogue
-    // (the single-ego kernel has a LOOP form of its own, which reads the history with sc1 loads: IoU events are fine there)
-    const bool chain = p->chain_steps && n_steps >= 2 && p->fused_step && !p->grid_tier && (!p->idm.on || idm_in_step(p)) && !side_models(p) &&
-                       !p->scene_regen && (ego ? p->chain_loop : !iou);
+    const StepPlan plan = plan_step(step_facts(p), n_steps);
     const float *a0 = p->v.act0, *a1 = p->v.act1;
     int rc = T2D_OK;
-    if (!chain) {   // kernels outside the fused step (IDM, drift, scene regeneration, the single-ego kernel): step by step
+    if (!plan.multi) {   // step by step
         for (int k = 0; k < n_steps && rc == T2D_OK; ++k) {
             p->v.act0 = a0 + (size_t)k * act_step_stride;
             p->v.act1 = a1 + (size_t)k * act_step_stride;
@@ -1251,8 +1246,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         int n = std::min(n_steps - done, (int)T2D_RECORD_RING);
         // the chained form of large pools: chain_depth steps per workgroup (launches of a multiple of it; what is left over
         // at the end of a call goes out one step per workgroup)
-        const int depth = p->chain_loop && !ego && !p->idm.on && p->chain_depth > 1 && n >= p->chain_depth && log2_pad(p->v.A) <= 6
-                              ? p->chain_depth : 1;
+        const int depth = plan.chain_k > 1 && n >= plan.chain_k ? plan.chain_k : 1;
         n -= n % depth;
         const int slot0 = (int)(p->step_count % T2D_RECORD_RING);
         for (int k = 0; k < n; ++k) {
@@ -1267,51 +1261,20 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         v.chain_done = p->d_chain;
         v.chain_err = reinterpret_cast<uint32_t*>(p->d_chain + p->chain_slots);
         v.chain_base = p->chain_count;
-        v.split_step = use_split(p);
-        v.chain_real_wgs = v.split_step ? p->v.n_env : (p->v.n_env + p->v.geo_layout.epb - 1) / p->v.geo_layout.epb;
         v.chain_act_step = act_step_stride;
-        // pools whose step launch is at most two workgroups per CU (all resident at once): the workgroups loop over the
-        // steps themselves; larger pools chain one workgroup per (env set, step)
-        {
-            if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
-            const int loop_wgs = (p->v.n_env + p->v.geo_layout.epb - 1) / p->v.geo_layout.epb;
-            const bool loop_ok = p->chain_loop && p->device_cus > 0 && loop_wgs <= T2D_LOOP_MAX_WGS_PER_CU * p->device_cus;
-            // ... and at most one workgroup per CU (envs of up to 64 participants): integrator waves a step ahead (PIPE)
-            v.pipe_step = loop_ok && p->chain_pipe && loop_wgs <= p->device_cus && p->v.A <= 64;
-            // (pools with lane polygons: the lane stage on a wave of its own -- needs three sets of waves in a workgroup)
-            // -- where the lane stage is long enough to pay for the poses derived a second time: five lane polygons per env
-            // and more (measured: 4 per env, the highway pool, 8.8 us per step without lane waves and 10.0 with them; 6 per
-            // env 8.1 / 7.6; 4..16 per env, the mixed pool, 11.0 / 9.2)
-            const size_t lane_polys = p->hgeo[1].present && !p->hgeo[1].env_off.empty() ? (size_t)p->hgeo[1].env_off.back() : 0;
-            if (v.pipe_step && p->chain_pipe2 && p->v.geo && p->v.geo_layout.has[1] && lane_polys >= 5 * (size_t)p->v.n_env &&
-                3 * (p->v.geo_layout.epb << log2_pad(p->v.A)) <= 1024)
-                v.pipe_step = 2;
-            if (v.pipe_step) {   // (preferred to the one-workgroup-per-env chain: the whole step overlaps, not only its stages)
-                v.split_step = 0;
-                v.chain_real_wgs = loop_wgs;
-            }
-            if (p->idm.on) {   // the integrator waves run the controllers (no lane waves then) -- or every workgroup of the chained form
-                v.pipe_step = idm_in_pipe(p) ? 1 : 0;
-                if (!v.pipe_step) {
-                    v.split_step = 0;
-                    v.chain_real_wgs = loop_wgs;
-                }
-                fill_idm(v, p);
-            }
-            v.loop_steps = (!v.split_step && loop_ok && !(p->idm.on && !v.pipe_step)) ? n : 0;
-        }
+        v.split_step = plan.split;
+        v.pipe_step = plan.pipe;
+        v.chain_real_wgs = plan.real_wgs;
+        if (plan.idm_fused) fill_idm(v, p);
         v.record_ring = (uint2*)p->field_ptr[T2D_F_RECORD];
         v.record_slot0 = slot0;
         // CHAIN forms (one workgroup per (env set, step), ordered by the counters in d_chain): the counters continue from
         // launch to launch only while the launches have one shape -- a pool that changes form (t2d_set_idm, new geometry,
         // t2d_set_split_step, t2d_set_step_chaining) starts them afresh, on the stream -- and every fragment carries the
         // checkpoint a failed hand-off is rolled back to
-        const bool chain_form = !ego && v.loop_steps == 0;
-        v.chain_k = 0;
-        if (chain_form && !v.split_step && depth > 1) {
-            v.chain_k = depth;
-            v.loop_steps = depth;
-        }
+        const bool chain_form = !plan.ego && !plan.loop;
+        v.chain_k = chain_form && !plan.split && depth > 1 ? depth : 0;
+        v.loop_steps = v.chain_k ? v.chain_k : plan.loop ? n : 0;
         if (chain_form) {
             const uint32_t sig = ((uint32_t)v.chain_real_wgs << 1) | (v.split_step ? 1u : 0u) | 0x80000000u;
             if (sig != p->chain_sig) {
@@ -1335,14 +1298,8 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         // synchronisation carried one)
         p->ckpt_armed = chain_form && (p->chain_used ? p->ckpt_armed : true);
         if ((rc = record_event(p, 7, s, true))) return rc;
-        if (ego) {   // 16 lanes per env, each group of lanes loops over the steps
-            v.loop_steps = n;
-            // (at most one workgroup of 16 envs per CU: integrator waves a step ahead of the event waves, t2d_ego.hip)
-            v.pipe_step = p->chain_pipe && p->device_cus > 0 && (p->v.n_env + 15) / 16 <= p->device_cus;
-            T2D_HIP(p, t2d::launch_ego_step(v, p->status_cfg, interval_ms, p->integrator_variant, s));
-        } else {
-            T2D_HIP(p, t2d::launch_step_chain(v, p->status_cfg, interval_ms, p->integrator_variant, n, s));
-        }
+        if (plan.ego) T2D_HIP(p, t2d::launch_ego_step(v, p->status_cfg, interval_ms, p->integrator_variant, s));
+        else T2D_HIP(p, t2d::launch_step_chain(v, p->status_cfg, interval_ms, p->integrator_variant, n, s));
         if ((rc = record_event(p, 7, s, false))) return rc;
         if (chain_form) p->chain_count += (uint32_t)n;   // (only these launches move the counters)
         p->chain_used = true;
@@ -1354,27 +1311,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
 
 int t2d_step_form(t2d_pool* p, int32_t n_steps) {
     if (!p) return -1;
-    const bool ego = p->ego_kernel && p->v.A == 1 && p->all_boxes && !side_models(p) && !p->hgeo[1].present;
-    const bool iou = p->status_cfg.check_no_action || p->status_cfg.check_arrival;
-    if (!p->fused_step || p->grid_tier || side_models(p) || p->scene_regen) return T2D_FORM_UNFUSED;
-    const bool chain = p->chain_steps && n_steps >= 2 && (ego ? p->chain_loop : !iou);
-    if (p->idm.on) {
-        if (ego || !idm_in_step(p)) return T2D_FORM_UNFUSED;
-        return !chain ? T2D_FORM_STEP : idm_in_pipe(p) ? T2D_FORM_LOOP_PIPE : T2D_FORM_CHAIN;
-    }
-    if (ego) {
-        if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
-        if (chain && p->chain_pipe && p->device_cus > 0 && (p->v.n_env + 15) / 16 <= p->device_cus) return T2D_FORM_EGO_LOOP_PIPE;
-        return chain ? T2D_FORM_EGO_LOOP : T2D_FORM_EGO;
-    }
-    const bool split = use_split(p);
-    if (!chain) return split ? T2D_FORM_STEP_SPLIT : T2D_FORM_STEP;
-    const int wgs = (p->v.n_env + p->v.geo_layout.epb - 1) / p->v.geo_layout.epb;
-    if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
-    const bool loop_ok = p->chain_loop && p->device_cus > 0 && wgs <= T2D_LOOP_MAX_WGS_PER_CU * p->device_cus;
-    if (loop_ok && p->chain_pipe && wgs <= p->device_cus && p->v.A <= 64) return T2D_FORM_LOOP_PIPE;
-    if (split) return T2D_FORM_CHAIN_SPLIT;
-    return loop_ok ? T2D_FORM_LOOP : T2D_FORM_CHAIN;
+    return plan_step(step_facts(p), n_steps).form;   // (the plan t2d_step / t2d_step_n launch from)
 }
 
 int t2d_set_split_step(t2d_pool* p, int32_t on) {

@@ -49,6 +49,7 @@
 #include "t2d_geom_dev.h"
 #include "t2d_idm_dev.h"
 #include "t2d_integrate_dev.h"
+#include "t2d_step_plan.h"
 
 // s_sleep between two polls of a PIPE progress word, in units of 64 cycles.  A waiting wave shares its SIMD with the wave it
 // waits for: measured on cfg3 / cfg4 / cfg5 / cfg2 (us per step) 0: 8.9 / 6.4 / 9.4 / -; 1: 8.8 / 6.4 / 9.2 / 4.9; 4: 8.6 / 6.5 /
@@ -2017,8 +2018,7 @@ const char* g_last_collide_form = "";
 // resident workgroups per CU of the fused step kernel with this pool's geometry record (the metric scenes are sized
 // for 4: one wave-round of 1024 workgroups on 256 CUs) and the LDS bytes per workgroup
 hipError_t step_occupancy(const PoolView& v, int* blocks_per_cu, size_t* lds_bytes) {
-    int log2A = 1;
-    while ((1 << log2A) < v.A) ++log2A;
+    const int log2A = host::log2_pad(v.A);
     const int block = v.geo_layout.epb << log2A;
     const size_t dyn = v.geo ? (size_t)v.geo_layout.stride * 4 : 0;
     hipFuncAttributes fa{};
@@ -2028,20 +2028,9 @@ hipError_t step_occupancy(const PoolView& v, int* blocks_per_cu, size_t* lds_byt
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, collide_kernel<true, 1, false>, block, dyn);
 }
 
-// SPLIT (one env per workgroup, its event stages on four waves): envs of 33..64 participants, workgroups of the full
-// 256 threads, no IoU events, and few enough envs for every workgroup of a step to be resident (four per CU)
-bool split_eligible(const PoolView& v, const t2d_status_config& cfg, int log2A, int device_cus) {
-    // ... and only where there is something to run side by side: envs with static obstacles next to their lanes (measured:
-    // roundabout / intersection pools gain 7-10 %; a highway pool -- pairs and a few lane rectangles, nothing else -- loses 9 %
-    // to the extra barriers and the poses derived four times)
-    return log2A == 6 && !(cfg.check_no_action || cfg.check_arrival) && device_cus > 0 &&
-           v.n_env <= 4 * device_cus && !v.wgmap && v.geo && v.geo_layout.has[0] && v.geo_layout.has[1];
-}
-
 hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, int interval_ms, int variant, int n_steps,
                              hipStream_t s) {
-    int log2A = 1;
-    while ((1 << log2A) < v.A) ++log2A;
+    const int log2A = host::log2_pad(v.A);
     const int EPB = v.geo_layout.epb;
     if (cfg.check_no_action || cfg.check_arrival) return hipErrorInvalidValue;   // (see below)
     if (v.split_step) {   // small pool of 64-agent envs: one env per workgroup, chained per env
@@ -2110,8 +2099,7 @@ hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, in
 
 hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool with_status,
                           int interval_ms, int fuse_variant, hipStream_t s) {
-    int log2A = 1;   // at least two lanes per env (see log2_pad in t2d_api.hip)
-    while ((1 << log2A) < v.A) ++log2A;
+    const int log2A = host::log2_pad(v.A);   // (at least two lanes per env)
     const int EPB = v.geo_layout.epb;
     const dim3 grid((v.n_env + EPB - 1) / EPB), block(EPB << log2A);
     const size_t dyn = v.geo ? (size_t)v.geo_layout.stride * 4 : 0;

@@ -292,12 +292,6 @@ void build_safe_rects(int E, t2d_pool::HostGeo& g) {
     }
 }
 
-int log2_pad(int A) {  // lanes per env = 2^l >= A, at least 2: the second lane of a one-agent env evaluates the Arrival IoU
-    int l = 1;        // while the first evaluates the NoAction IoU (one SIMT pass instead of two calls in a row)
-    while ((1 << l) < A) ++l;
-    return l;
-}
-
 // dword offsets of one workgroup's record: env polygon ranges, polygon vertex ranges, AABBs, vertices (static, lanes)
 void fill_layout(t2d::GeoLayout& gl, int epb, const int mp[2], const int mv[2], int mb) {
     int off = 0;
@@ -319,8 +313,7 @@ void fill_layout(t2d::GeoLayout& gl, int epb, const int mp[2], const int mv[2], 
 // Envs per workgroup of the step launch: as many as 256 lanes hold -- fewer while that leaves compute units without a
 // workgroup (a pool of 512 envs x 32 participants is 64 workgroups of 8 envs, or 256 workgroups of 2: one per CU instead of
 // three CUs in four idle), down to one wave per workgroup.
-int envs_per_workgroup(t2d_pool* p, int log2A) {
-    if (p->device_cus == 0) (void)hipDeviceGetAttribute(&p->device_cus, hipDeviceAttributeMultiprocessorCount, p->device);
+int envs_per_workgroup(const t2d_pool* p, int log2A) {
     int epb = 256 >> log2A;
     // (halved only while the narrower workgroups still number at most the CUs: the looping forms of t2d_step_n with their
     // extra sets of waves want one workgroup per CU, not two)

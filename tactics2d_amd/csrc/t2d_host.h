@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "t2d_pool.h"
+#include "t2d_step_plan.h"
 
 namespace t2d {
 namespace host {
@@ -33,8 +34,7 @@ int dev_replace(t2d_pool* p, DevBuf<T>* dst, const T* src, size_t n) {
 // ---- geometry preparation (t2d_geometry_host.hip) -----------------------------------------------------------------------------
 double area2(const std::vector<double>& P);
 double orient_h(const double* p, const double* q, const double* r);
-int log2_pad(int A);
-int envs_per_workgroup(t2d_pool* p, int log2A);
+int envs_per_workgroup(const t2d_pool* p, int log2A);   // (log2A = log2_pad(max_agents): t2d_step_plan.h)
 int prepare_polys(t2d_pool* p, const int32_t* env_off, const int32_t* vert_off, const float* xy, t2d_pool::HostGeo& out);
 void build_lane_boundary(int E, t2d_pool::HostGeo& g);
 void build_safe_rects(int E, t2d_pool::HostGeo& g);

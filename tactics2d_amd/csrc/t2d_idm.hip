@@ -15,6 +15,7 @@
 // the pool's act0 field, steer 0 -> its act1 field (the reference returns (steering, acceleration); the physics
 // models take (accel, steer)), leader index -> T2D_F_LEADER.  HBM: 17 B read + 12 B written per participant.
 #include "t2d_idm_dev.h"
+#include "t2d_step_plan.h"
 
 namespace t2d {
 
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(kIdmBlock) void idm_kernel(PoolView pv, IdmView iv,
 
 hipError_t launch_idm(const PoolView& v, const IdmView& iv, const int32_t* forced_leader, float* act0_own, float* act1_own,
                       hipStream_t s) {
-    int log2A = 0;
-    while ((1 << log2A) < v.A) ++log2A;
+    const int log2A = v.A > 1 ? host::log2_pad(v.A) : 0;   // (one lane per participant: a one-agent env is not padded to two here)
     const int epb = kIdmBlock >> log2A;
     hipLaunchKernelGGL(idm_kernel, dim3((v.n_env + epb - 1) / epb), dim3(kIdmBlock), 0, s, v, iv, forced_leader, act0_own, act1_own, log2A);
     return hipGetLastError();

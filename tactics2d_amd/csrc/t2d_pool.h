@@ -699,7 +699,6 @@ const char* last_collide_form();   // template arguments of the collide_kernel i
 hipError_t launch_frame_pack(const PoolView& v, const FrameView& fv, hipStream_t s);
 // note that work of this pool was enqueued on `s` by code outside t2d_api.hip (a replayed graph): t2d_sync waits for it
 void pool_touch(t2d_pool* p, hipStream_t s);
-bool split_eligible(const PoolView& v, const t2d_status_config& cfg, int log2A, int device_cus);
 hipError_t launch_parking_scenes(const PoolView& v, const SceneView& sv, int n_env, int mode, hipStream_t s);
 hipError_t launch_scene_refill(const SceneView& sv, int n_env, hipStream_t s);
 // regenerate = 1: envs whose episode just ended take the scene staged for their next one, sixteen lanes per env

@@ -50,7 +50,7 @@ V_HALF = 8.5                      # slats reach v = x + y = -+ 8.5
 T_STATIC, T_LANE, T_LANE_OVERLAP = 3.0 / 64, 17.0 / 64, 51.0 / 128
 F_DYNAMIC, F_STATIC, F_OFF_LANE = 1, 2, 8
 # a static quad far from every participant: it gives the lane scenes the static stage without which a 64-agent pool does not take
-# the one-workgroup-per-env form (split_eligible wants both stages)
+# the one-workgroup-per-env form (plan_step's split wants both stages)
 DECOY = np.float32([[14.0, -15.0], [15.0, -15.0], [15.0, -14.0], [14.0, -14.0]])
 
 
