@@ -1090,6 +1090,73 @@ int t2d_spline_routes(t2d_pool* pool, int32_t kind, const double* ctrl_dev, cons
                       int32_t n_interpolation, int32_t degree, const double* knots_dev, int32_t boundary_type, const double* derivs_dev,
                       int32_t route, int32_t* count_dev, void* hip_stream);
 
+/* Spiral and ParamPoly3 curves and the plan-view reference line of an OpenDRIVE road on the device -- interpolator/spiral.py,
+ * interpolator/param_poly3.py and, of map/parser/parse_xodr.py, _sample_line / _sample_spiral / _sample_arc / _sample_poly3 /
+ * _sample_param_poly3 / _sample_geometry and the head of load_road (pts_arr, s_arr, kappa_arr), restated operation by operation in
+ * fp64 with the library's own sincos and its own Fresnel integrals (tests/road_ref.py).  One wave handles one
+ * curve or road, T2D_ROAD_CURVES_PER_BLOCK of them share a workgroup, a lane stores one 16-byte [x, y].
+ *   Spiral      n_interpolation >= 1 points at np.linspace(0, length, n).  gamma == 0 and start_curvature == 0: the line;
+ *               gamma == 0: the arc by its sin / cos differences; otherwise a (C(t) + i S(t)) exp(i theta_0), a = sqrt(pi /
+ *               |gamma|), t = s sqrt(|gamma| / pi), theta_0 = heading - k0^2 / (2 gamma).  AS WRITTEN (T2D_SPIRAL_REFERENCE) this
+ *               is the Euler spiral only for k0 == 0 and gamma > 0: |gamma| scales, nothing mirrors, and theta_0 is shifted but the
+ *               Fresnel argument is not.  T2D_SPIRAL_STANDARD (build-defined) is the clothoid of heading(s) = heading + k0 s +
+ *               gamma s^2 / 2, through the shifted argument t = (s + k0 / gamma) sqrt(|gamma| / pi) and the mirror for gamma < 0;
+ *               its line and arc branches are the same.
+ *   ParamPoly3  max(2, int(length / 0.1)) points (an fp64 division, truncated) at p = np.linspace(0, p_max, n), p_max = length
+ *               under p_range 1 (arcLength) and 1 under p_range 0 (normalized); u, v = a + b p + c p^2 + d p^3 summed left to right
+ *               with p^2 = p p and p^3 = (p p) p (numpy's p ** 3 goes through pow: at most an ulp away); [x, y] = (u cos + v
+ *               (-sin), u sin + v cos) + start.
+ *   plan view   per road up to max_geom records of T2D_PLANVIEW_RECORD_BYTES: i32 kind (T2D_GEOM_*), i32 p_range, f64 s, x, y, hdg,
+ *               length, f64 par[8] = spiral {curvStart, curvEnd}, arc {curvature}, poly3 {a, b, c, d}, paramPoly3 {aU, bU, cU, dU,
+ *               aV, bV, cV, dV}.  Geometries are sampled in order: line and poly3 max(2, int(length / 0.1) + 1) points (a line of
+ *               length <= 0: one); spiral Spiral's 100 points with curvature linspace(curvStart, curvEnd, 100) (length < 1e-6:
+ *               one point); arc |curvature| < 1e-9: the line sampler, with curvature 0; otherwise the circle by its tangent and
+ *               np.arange at 0.1 m of arc, WHICH NEVER SAMPLES THE ARC'S END; poly3 and paramPoly3 with their analytic curvature
+ *               (speed ** 1.5 as speed sqrt(speed)).  A geometry's last point is dropped if it equals the one before it; its s is
+ *               linspace(s, s + length, points left).  Over the concatenation, point k is kept if k == 0 or its distance
+ *               sqrt(dx dx + dy dy) to RAW point k - 1 (kept or not) is > 0.02.  A road of fewer than 2 kept points has no line:
+ *               count 0.  AS WRITTEN, a spiral shorter than about 1.98 m (99 steps of 0.02) loses every point but its first.
+ * BUILD-DEFINED, per row: count 0 and nothing else written where a value the row reads is not finite (the par entries of its
+ * kinds only), a length is < 0, a kind or a paramPoly3's p_range is unknown, n_geom is outside [1, max_geom], or the road has more
+ * than T2D_PLANVIEW_MAX_RAW raw points.  One bad row touches only its own outputs.  A curve or line of more than max_points points
+ * writes its first max_points and count holds the FULL count.
+ *   t2d_spiral_curves       n spirals in ONE launch, asynchronous on hip_stream, no pool: par_dev f64 [n][6] = {length, x0, y0,
+ *                           heading, start_curvature, gamma} -> xy_dev f64 [n][max_points][2] (16-byte aligned), count_dev i32 [n].
+ *   t2d_param_poly3_curves  par_dev f64 [n][12] = {length, x0, y0, heading, aU, bU, cU, dU, aV, bV, cV, dV}, p_range_dev i32 [n].
+ *   t2d_planview_lines      rec_dev [n][max_geom] records, n_geom_dev i32 [n] -> xy_dev f64 [n][max_points][2], s_dev and kappa_dev
+ *                           f64 [n][max_points] (either may be NULL), count_dev i32 [n].
+ *                           T2D_ERR_INVALID, nothing launched, for all three: n < 0, max_points <= 0, n_interpolation < 1, another
+ *                           rule, max_geom outside [1, T2D_PLANVIEW_MAX_GEOM], a null or misaligned pointer.
+ *   t2d_planview_routes     the same chain, road e for env e (n = n_env), written as fp32 vertices into route `route` of env e's
+ *                           installed set under the rules of t2d_curve_routes.  A set holds 4096 vertices and a road has ten raw
+ *                           points per metre, hence stride >= 1: the vertices are kept points 0, stride, 2 stride, ... and ALWAYS
+ *                           the last kept point; count c = the number of vertices that gives.  The route's vertex count is the
+ *                           capacity; c == 0 leaves the route untouched; c <= capacity: vertices k >= c repeat the last kept point;
+ *                           c > capacity: the first `capacity` of them.  count_dev i32 [n_env] (may be NULL).  T2D_ERR_STATE
+ *                           unless route sets are the installed kind, no two envs share a set and every env's set has a route
+ *                           `route`; T2D_ERR_INVALID as above and for stride < 1 or route < 0.  kernel_id
+ *                           T2D_PROFILE_PLANVIEW_ROUTES in t2d_profile_read.                                                    */
+#define T2D_SPIRAL_REFERENCE 0
+#define T2D_SPIRAL_STANDARD 1
+#define T2D_GEOM_LINE 0
+#define T2D_GEOM_SPIRAL 1
+#define T2D_GEOM_ARC 2
+#define T2D_GEOM_POLY3 3
+#define T2D_GEOM_PARAM_POLY3 4
+#define T2D_PLANVIEW_RECORD_BYTES 112
+#define T2D_PLANVIEW_MAX_GEOM 64
+#define T2D_PLANVIEW_MAX_RAW 1048576
+#define T2D_ROAD_CURVES_PER_BLOCK 4
+enum { T2D_PROFILE_PLANVIEW_ROUTES = 19 };   /* (the kernel ids after 18 are enumerators) */
+int t2d_spiral_curves(int32_t device_id, int32_t n, const double* par_dev, int32_t n_interpolation, int32_t rule, int32_t max_points,
+                      double* xy_dev, int32_t* count_dev, void* hip_stream);
+int t2d_param_poly3_curves(int32_t device_id, int32_t n, const double* par_dev, const int32_t* p_range_dev, int32_t max_points,
+                           double* xy_dev, int32_t* count_dev, void* hip_stream);
+int t2d_planview_lines(int32_t device_id, int32_t n, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule,
+                       int32_t max_points, double* xy_dev, double* s_dev, double* kappa_dev, int32_t* count_dev, void* hip_stream);
+int t2d_planview_routes(t2d_pool* pool, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule, int32_t stride,
+                        int32_t route, int32_t* count_dev, void* hip_stream);
+
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
  * over the action row of an env while a path is being executed and leaves the policy's row alone otherwise.
@@ -1533,7 +1600,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * 10 = racing tile progress (t2d_track_progress), 11 = BEV camera (t2d_camera_render), 12 = racing track regeneration
  * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
  * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions),
- * 17 = curve lines into the route sets (t2d_curve_routes), 18 = spline curves into the route sets (t2d_spline_routes).  */
+ * 17 = curve lines into the route sets (t2d_curve_routes), 18 = spline curves into the route sets (t2d_spline_routes),
+ * 19 = plan-view reference lines into the route sets (t2d_planview_routes).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

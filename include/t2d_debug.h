@@ -77,6 +77,8 @@ int t2d_debug_closed_loop_destroy(t2d_closed_loop* loop);
  *     ATAN2               a = y, b = x               one                            atan2_det
  *     MOD_TWO_PI, LOG, EXP  a = x                    one                            mod_two_pi, log_det, exp_det
  *     POW                 a = x, b = y               one                            pow_det(x, y)
+ *     FRESNEL             a = x                      S, C                           fresnel_det (fn 12: 11 stays unassigned,
+ *                                                                                   tests/test_gpu_math.py sends it as the unknown one)
  * Element i is computed by lane i % 64 of wave i / 64 in workgroups of 256, and the lanes past n leave before any wave-level
  * operation: the caller decides which inputs share a wave (the __ballot shortcuts of the steer variants).
  * table = 1 runs the same function compiled with T2D_TRIG_TABLE (constants from __constant__ tables, as t2d_collide.hip compiles
@@ -85,7 +87,8 @@ int t2d_debug_closed_loop_destroy(t2d_closed_loop* loop);
  * a table variant, n outside [1, T2D_MATH_MAX_N], a null array, an unknown device; T2D_ERR_HIP for a failing runtime call.   */
 enum {
     T2D_MATH_SINCOS = 0, T2D_MATH_SINCOS_SMALL = 1, T2D_MATH_SINCOS_STEER = 2, T2D_MATH_SINCOS_STEER_AND = 3, T2D_MATH_TAN = 4,
-    T2D_MATH_ATAN = 5, T2D_MATH_ATAN2 = 6, T2D_MATH_MOD_TWO_PI = 7, T2D_MATH_LOG = 8, T2D_MATH_EXP = 9, T2D_MATH_POW = 10
+    T2D_MATH_ATAN = 5, T2D_MATH_ATAN2 = 6, T2D_MATH_MOD_TWO_PI = 7, T2D_MATH_LOG = 8, T2D_MATH_EXP = 9, T2D_MATH_POW = 10,
+    T2D_MATH_FRESNEL = 12
 };
 #define T2D_MATH_MAX_N 16777216
 int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int64_t n, const double* a_host, const double* b_host,

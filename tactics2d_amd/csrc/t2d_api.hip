@@ -3170,6 +3170,29 @@ int t2d_spline_routes(t2d_pool* p, int32_t kind, const double* ctrl_dev, const i
     return record_event(p, T2D_PROFILE_SPLINE_ROUTES, s, false);
 }
 
+int t2d_planview_routes(t2d_pool* p, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule, int32_t stride,
+                        int32_t route, int32_t* count_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (const char* why = t2d::planview_args_error(rec_dev, n_geom_dev, max_geom, rule))
+        return fail(p, T2D_ERR_INVALID, std::string("t2d_planview_routes: ") + why);
+    if (stride < 1) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: stride must be >= 1");
+    if (reinterpret_cast<uintptr_t>(count_dev) & 3u) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: misaligned count_dev");
+    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: route must be >= 0");
+    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_planview_routes writes into route sets: t2d_set_routes must precede it");
+    if (!p->route_sets_distinct)
+        return fail(p, T2D_ERR_STATE, "t2d_planview_routes: two envs share a route set; install one set per env (set_of_env)");
+    if (route >= p->route_min_limit)
+        return fail(p, T2D_ERR_STATE, "t2d_planview_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
+                                          std::to_string(p->route_min_limit) + " routes)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, T2D_PROFILE_PLANVIEW_ROUTES, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_planview_routes(p->v, p->route, rec_dev, n_geom_dev, max_geom, rule, stride, route, count_dev, s));
+    return record_event(p, T2D_PROFILE_PLANVIEW_ROUTES, s, false);
+}
+
 int t2d_route_vertices(t2d_pool* p, void** verts_dev, size_t* n_vertices) {
     if (!p) return T2D_ERR_INVALID;
     if (!verts_dev || !n_vertices) return fail(p, T2D_ERR_INVALID, "null output");

@@ -48,6 +48,14 @@ struct CurvePlan {
 };
 
 #ifdef __HIPCC__
+// np.arange(start, stop, delta) as Circle.get_arc calls it: ceil((stop - start) / delta) values (none where that is <= 0),
+// value k = start + k * ((start + delta) - start).  One statement for curve_plan below and the plan-view arcs of t2d_road_dev.h.
+T2D_DEV double arange_count(double start, double stop, double delta) {
+    const double cnt = __builtin_ceil((stop - start) / delta);
+    return cnt > 0.0 ? cnt : 0.0;
+}
+T2D_DEV double arange_increment(double start, double delta) { return (start + delta) - start; }
+
 // ---- Dubins -------------------------------------------------------------------------------------------------------------------
 // The normalised query of get_all_path (:259-262) with the sines and cosines every word needs.
 struct DubinsGoal {
@@ -187,8 +195,7 @@ T2D_DEV bool curve_plan(const CurveWord& w, double sx, double sy, double sh, dou
                 const double a0 = left ? h - pio2 : h + pio2;
                 const double delta = cw ? -step / radius : step / radius;
                 const double stop = cw ? a0 - a : a0 + a;
-                cnt = __builtin_ceil((stop - a0) / delta);                    // np.arange's length
-                cnt = cnt > 0.0 ? cnt : 0.0;
+                cnt = arange_count(a0, stop, delta);
                 cnt = cnt < kCurveMaxCount ? cnt : kCurveMaxCount;
                 const double h_end = cw ? h - a : h + a;
                 sincos_det(stop, sn, cs);
@@ -205,7 +212,7 @@ T2D_DEV bool curve_plan(const CurveWord& w, double sx, double sy, double sh, dou
                     c.p0[i] = cx;
                     c.p1[i] = cy;
                     c.q0[i] = a0;
-                    c.q1[i] = (a0 + delta) - a0;               // numpy fills a0 + k * ((a0 + delta) - a0)
+                    c.q1[i] = arange_increment(a0, delta);
                 }
                 c.he[i] = h_end;
                 c.hs[i] = cnt > 1.0 ? (h_end - h) / (cnt - 1.0) : 0.0;

@@ -383,3 +383,85 @@ T2D_DEV double pow_det(double x, double y) {  // float.__pow__ on the IDM path (
 }
 
 }  // namespace t2d
+
+// ---- the Fresnel integrals S(x) = int_0^x sin(pi t^2 / 2) dt, C(x) likewise with cos (scipy.special.fresnel's convention) ----
+#include "t2d_fresnel_tab.h"
+
+namespace t2d {
+
+// The tables of scripts/make_fresnel_tables.py.  Indexed per lane: they stay tables in memory.
+static __device__ const double kFresnelAuxX[T2D_FRESNEL_AUX_INTERVALS] = T2D_FRESNEL_AUX_X;
+static __device__ const double kFresnelSSeries[T2D_FRESNEL_SERIES_TERMS] = T2D_FRESNEL_S_SERIES;
+static __device__ const double kFresnelCSeries[T2D_FRESNEL_SERIES_TERMS] = T2D_FRESNEL_C_SERIES;
+static __device__ const double kFresnelAuxMid[T2D_FRESNEL_AUX_INTERVALS] = T2D_FRESNEL_AUX_MID;
+static __device__ const double kFresnelAuxF[T2D_FRESNEL_AUX_INTERVALS][T2D_FRESNEL_AUX_TERMS] = T2D_FRESNEL_AUX_F;
+static __device__ const double kFresnelAuxG[T2D_FRESNEL_AUX_INTERVALS][T2D_FRESNEL_AUX_TERMS] = T2D_FRESNEL_AUX_G;
+constexpr double kFresnelSaturate = 9007199254740992.0;   // 2^53: f < 1 / (pi 2^53) < 2^-54, and 0.5 -+ that rounds to 0.5
+
+// Any finite x; odd in x; (+-0.5, +-0.5) from |x| >= 2^53 on (infinities included); NaN for NaN.  DESIGN.md 4.20.
+//   |x| < 1.5:  the Maclaurin series in x^4.
+//   above:      C = 1/2 + f sin(pi x^2/2) - g cos(pi x^2/2), S = 1/2 - f cos(pi x^2/2) - g sin(pi x^2/2) with f = F(u) / (pi x),
+//               g = G(u) / (pi^2 x^3), F and G one polynomial in u = 1 / x^4 per interval of |x|.  The angle never sees the
+//               rounding of pi/2 x^2: x^2 = hi + lo exactly (one fma), each part is reduced mod 4 exactly (sin and cos of
+//               pi/2 y have period 4 in y), and what is left, |r| <= 1/2 quarter turns, goes through sincos_det's two kernels.
+// Except for that one fma -- which only has to be exact -- every operation is a separately rounded * + - /, so that
+// tests/road_ref.py evaluates the same bits in numpy.  Largest error against mpmath on [0, 60]: 2.7e-16 (S), 2.2e-16 (C).
+T2D_DEV void fresnel_det(double x, double& S, double& C) {
+    const double ax = __builtin_fabs(x);
+    if (ax != ax) {
+        S = C = x;
+        return;
+    }
+    double s, c;
+    if (ax >= kFresnelSaturate) {
+        s = c = 0.5;
+    } else if (ax < kFresnelAuxX[0]) {
+        const double x2 = ax * ax, z = x2 * x2;
+        double ps = kFresnelSSeries[T2D_FRESNEL_SERIES_TERMS - 1], pc = kFresnelCSeries[T2D_FRESNEL_SERIES_TERMS - 1];
+#pragma unroll
+        for (int k = T2D_FRESNEL_SERIES_TERMS - 2; k >= 0; --k) {
+            ps = ps * z + kFresnelSSeries[k];
+            pc = pc * z + kFresnelCSeries[k];
+        }
+        s = (x2 * ax) * ps;
+        c = ax * pc;
+    } else {
+        int i = 0;
+#pragma unroll
+        for (int t = 1; t < T2D_FRESNEL_AUX_INTERVALS; ++t) i += ax >= kFresnelAuxX[t] ? 1 : 0;
+        const double x2 = ax * ax;
+        const double u = 1.0 / (x2 * x2);
+        const double v = u - kFresnelAuxMid[i];
+        double F = kFresnelAuxF[i][0], G = kFresnelAuxG[i][0];
+#pragma unroll
+        for (int k = 1; k < T2D_FRESNEL_AUX_TERMS; ++k) {
+            F = F * v + kFresnelAuxF[i][k];
+            G = G * v + kFresnelAuxG[i][k];
+        }
+        const double p = 0.3183098861837907 / ax;
+        const double f = F * p, g = G * ((p * p) / ax);
+        const double lo = __builtin_fma(ax, ax, -x2);
+        const double hm = x2 - 4.0 * __builtin_rint(x2 * 0.25), lm = lo - 4.0 * __builtin_rint(lo * 0.25);
+        const double y = hm + lm;                       // x^2 mod 4 in [-4, 4]
+        const double k = __builtin_rint(y);
+        const double r = (y - k) * kPio2Hi;
+        const double zz = r * r;
+        double sp = 1.58969099521155010221e-10, cp = -1.13596475577881948265e-11;
+        sp = sp * zz + -2.50507602534068634195e-08; cp = cp * zz + 2.08757232129817482790e-09;
+        sp = sp * zz + 2.75573137070700676789e-06;  cp = cp * zz + -2.75573143513906633035e-07;
+        sp = sp * zz + -1.98412698298579493134e-04; cp = cp * zz + 2.48015872894767294178e-05;
+        sp = sp * zz + 8.33333333332248946124e-03;  cp = cp * zz + -1.38888888888741095749e-03;
+        sp = sp * zz + -1.66666666666666324348e-01; cp = cp * zz + 4.16666666666666019037e-02;
+        const double sr = r + (r * zz) * sp, cr = (1.0 - 0.5 * zz) + (zz * zz) * cp;
+        const int quad = (int)k & 3;
+        double sn = (quad & 1) ? cr : sr, cs = (quad & 1) ? sr : cr;
+        sn = (quad & 2) ? -sn : sn;
+        cs = ((quad + 1) & 2) ? -cs : cs;
+        s = 0.5 - (f * cs + g * sn);
+        c = 0.5 + (f * sn - g * cs);
+    }
+    S = __builtin_copysign(s, x);
+    C = __builtin_copysign(c, x);
+}
+
+}  // namespace t2d

@@ -69,6 +69,10 @@ __global__ __launch_bounds__(256) void math_probe_kernel(long long n, const doub
         out[i] = M::exp_det(x);
     } else if constexpr (FN == T2D_MATH_POW) {
         out[i] = M::pow_det(x, b[i]);
+    } else if constexpr (FN == T2D_MATH_FRESNEL) {
+        double S, C;
+        M::fresnel_det(x, S, C);
+        out[i] = S; out[n + i] = C;
 #endif
     }
 }
@@ -96,6 +100,7 @@ hipError_t T2D_PROBE_LAUNCH(int fn, long long n, const double* a, const double* 
         case T2D_MATH_LOG: return launch_one<T2D_MATH_LOG>(n, a, b, out);
         case T2D_MATH_EXP: return launch_one<T2D_MATH_EXP>(n, a, b, out);
         case T2D_MATH_POW: return launch_one<T2D_MATH_POW>(n, a, b, out);
+        case T2D_MATH_FRESNEL: return launch_one<T2D_MATH_FRESNEL>(n, a, b, out);
 #endif
         default: return hipErrorInvalidValue;
     }
@@ -115,7 +120,7 @@ namespace {
 
 int n_outputs(int fn) {
     switch (fn) {
-        case T2D_MATH_SINCOS: case T2D_MATH_SINCOS_SMALL: case T2D_MATH_SINCOS_STEER: return 2;
+        case T2D_MATH_SINCOS: case T2D_MATH_SINCOS_SMALL: case T2D_MATH_SINCOS_STEER: case T2D_MATH_FRESNEL: return 2;
         case T2D_MATH_SINCOS_STEER_AND: return 4;
         case T2D_MATH_TAN: case T2D_MATH_ATAN: case T2D_MATH_ATAN2: case T2D_MATH_MOD_TWO_PI: case T2D_MATH_LOG:
         case T2D_MATH_EXP: case T2D_MATH_POW: return 1;

@@ -665,6 +665,11 @@ const char* spline_args_error(int kind, const double* ctrl, const int32_t* n_ctr
 hipError_t launch_spline_routes(const PoolView& v, const RouteView& rv, int kind, const double* ctrl, const int32_t* n_ctrl,
                                 int max_ctrl, int n_interp, int degree, const double* knots, int boundary, const double* derivs,
                                 int route, int32_t* count, hipStream_t s);
+// plan-view reference lines (t2d_road.hip): what is wrong with a launch's arguments (null: nothing), and road e -> the fp32
+// vertices of route `route` of env e's set
+const char* planview_args_error(const void* rec, const int32_t* n_geom, int max_geom, int rule);
+hipError_t launch_planview_routes(const PoolView& v, const RouteView& rv, const void* rec, const int32_t* n_geom, int max_geom, int rule,
+                                  int stride, int route, int32_t* count, hipStream_t s);
 // racing tile progress (t2d_track.hip): march, visited mask, status and reward of every env
 hipError_t launch_track_progress(const PoolView& v, const TrackView& tv, int write_status, hipStream_t s);
 hipError_t launch_trackgen(const TrackGenView& g, int n, int mode, hipStream_t s);

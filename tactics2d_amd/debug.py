@@ -111,7 +111,8 @@ def feedback_policy(p, act_out_ptr, v_target, k_speed, k_steer, stream=None):
 
 # t2d_debug_math's fn (include/t2d_debug.h: T2D_MATH_*) -> number of outputs
 MATH_FUNCTIONS = {"sincos": (0, 2), "sincos_small": (1, 2), "sincos_steer": (2, 2), "sincos_steer_and": (3, 4), "tan": (4, 1),
-                  "atan": (5, 1), "atan2": (6, 1), "mod_two_pi": (7, 1), "log": (8, 1), "exp": (9, 1), "pow": (10, 1)}
+                  "atan": (5, 1), "atan2": (6, 1), "mod_two_pi": (7, 1), "log": (8, 1), "exp": (9, 1), "pow": (10, 1),
+                  "fresnel": (12, 2)}
 
 
 def math(fn, a, b=None, table=False, device_id=0):

@@ -1,5 +1,7 @@
 """Reeds-Shepp and Dubins curves for batches of queries, and Bezier, B-spline and cubic spline curves for batches of control
-polygons, on the device (tactics2d/interpolator/reeds_shepp.py, dubins.py, bezier.py, b_spline.py, cubic_spline.py).
+polygons, on the device (tactics2d/interpolator/reeds_shepp.py, dubins.py, bezier.py, b_spline.py, cubic_spline.py); Spiral and
+ParamPoly3 curves (spiral.py, param_poly3.py) and, on top of them, the plan-view reference lines of OpenDRIVE roads
+(map/parser/parse_xodr.py): `Spiral`, `ParamPoly3`, `pack_planview`, `planview_lines`.
 
 `ReedsShepp(radius).get_all_path(...)` is the reference's method of that name for n queries in one launch of
 t2d_rs_paths (include/t2d.h): the 48 slots of the reference's list, in its order, as device tensors.  `Dubins(radius)` is the
@@ -566,3 +568,220 @@ class CubicSpline:
             first_derivatives = None
         return spline_curves(L.SPLINE_CUBIC, control_points, n_ctrl, n_interpolation, 0, None, boundary_type, first_derivatives,
                              max_points, device_id, stream)
+
+
+# ---- Spiral and ParamPoly3 curves, plan-view reference lines (t2d_spiral_curves / t2d_param_poly3_curves / t2d_planview_lines) ----
+# Not here: ParamPoly3.fit and split_polyline (np.polyfit on the host: not a hot path), lane widths and lane polygons off the
+# reference line, and the XML parser itself -- pack_planview takes the attributes of <geometry> elements already parsed.
+class RoadCurves:
+    """What Spiral / ParamPoly3.get_curve return for a batch: xy float64 [n, max_points, 2]: the first min(count, max_points) rows
+    of a curve are its points, the rest is not written; count int32 [n]: the curve's FULL point count (0: no curve -- a value that
+    is not finite, a negative length, an unknown p_range; > max_points: truncated).  Device tensors (numpy arrays where nothing
+    was launched: n_interpolation == 0)."""
+
+    def __init__(self, xy, count):
+        self.xy, self.count = xy, count
+
+
+class PlanviewLines:
+    """What planview_lines returns: device tensors, one row per road.  xy float64 [n, max_points, 2], s and kappa float64
+    [n, max_points]: the first min(count, max_points) rows are the road's kept points, their s and their curvature; count int32
+    [n]: the FULL number of kept points (0: the road has no line)."""
+
+    def __init__(self, xy, s, kappa, count):
+        self.xy, self.s, self.kappa, self.count = xy, s, kappa, count
+
+
+SPIRAL_RULES = {"reference": L.SPIRAL_REFERENCE, "standard": L.SPIRAL_STANDARD}
+P_RANGES = {"normalized": L.P_RANGE_NORMALIZED, "arcLength": L.P_RANGE_ARC_LENGTH}
+GEOMETRY_KINDS = {"line": L.GEOM_LINE, "spiral": L.GEOM_SPIRAL, "arc": L.GEOM_ARC, "poly3": L.GEOM_POLY3,
+                  "paramPoly3": L.GEOM_PARAM_POLY3}
+GEOMETRY_ATTRIBUTES = {"line": (), "spiral": ("curvStart", "curvEnd"), "arc": ("curvature",), "poly3": ("a", "b", "c", "d"),
+                       "paramPoly3": ("aU", "bU", "cU", "dU", "aV", "bV", "cV", "dV")}
+
+
+def _rule(rule):
+    rule = SPIRAL_RULES.get(rule, rule)
+    if rule not in SPIRAL_RULES.values():
+        raise ValueError(f"rule must be one of {sorted(SPIRAL_RULES)}")
+    return rule
+
+
+def _columns(dev, cols):
+    """float64 [n, len(cols)] on `dev` from scalars, arrays and tensors of n (or one) values each"""
+    import torch
+    parts = [c.to(dev, torch.float64).reshape(-1) if _is_tensor(c) else
+             torch.as_tensor(np.ascontiguousarray(np.asarray(c, np.float64).reshape(-1))).to(dev) for c in cols]
+    n = max(len(p) for p in parts)
+    return torch.stack([p.expand(n) if len(p) == 1 else p for p in parts], 1).contiguous()
+
+
+def _host_values(x):
+    return None if _is_tensor(x) else np.asarray(x, np.float64).reshape(-1)
+
+
+class Spiral:
+    """Spiral (interpolator/spiral.py) for batches."""
+
+    @staticmethod
+    def get_curve(length, start_point, heading, start_curvature, gamma, n_interpolation=100, rule="reference", max_points=None,
+                  device_id=0, stream=None):
+        """Spiral.get_curve (spiral.py:15-89).  Scalars (start_point a pair) give one curve as a numpy array (n_interpolation, 2);
+        arrays or float64 CUDA tensors of n values (start_point [n, 2]) give n curves in one launch of t2d_spiral_curves as
+        RoadCurves, asynchronous on `stream`.  rule "reference": the class as written -- the Euler spiral only for
+        start_curvature == 0 and gamma > 0 --; "standard": the clothoid heading + k0 s + gamma s^2 / 2.
+        n_interpolation == 0 gives (0, 2) and launches nothing.  The reference's ValueErrors are raised with its messages (a
+        negative length inside a device tensor is not looked at: that row comes back with count 0)."""
+        import torch
+        rule = _rule(rule)
+        single = not any(_is_tensor(v) or np.ndim(v) for v in (length, heading, start_curvature, gamma)) and not _is_tensor(start_point) and np.ndim(start_point) == 1
+        host = _host_values(length)
+        if host is not None and np.any(host < 0):
+            raise ValueError("Length must be non-negative.")
+        n_interpolation = int(n_interpolation)
+        if n_interpolation < 0:
+            raise ValueError("Number of interpolation points must be non-negative.")
+        if n_interpolation == 0:
+            if single:
+                return np.empty((0, 2))
+            n = max(int(np.prod(v.shape)) if hasattr(v, "shape") else np.size(v) for v in (length, heading, start_curvature, gamma))
+            return RoadCurves(np.empty((n, 0, 2)), np.zeros(n, np.int32))
+        lib = _ffi.lib()
+        dev, st = _stream_of(device_id, stream)
+        max_points = n_interpolation if max_points is None else int(max_points)
+        with torch.cuda.stream(st):
+            sp = start_point.to(dev, torch.float64).reshape(-1, 2) if _is_tensor(start_point) else np.asarray(start_point, np.float64).reshape(-1, 2)
+            par = _columns(dev, (length, sp[:, 0], sp[:, 1], heading, start_curvature, gamma))
+            n = par.shape[0]
+            xy = torch.empty((n, max(max_points, 0), 2), dtype=torch.float64, device=dev)
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+            _ffi.check(lib.t2d_spiral_curves(device_id, n, par.data_ptr(), n_interpolation, rule, max_points, xy.data_ptr(),
+                                             count.data_ptr(), st.cuda_stream), None, lib)
+        if single:
+            st.synchronize()
+            return xy[0, :min(int(count[0]), max_points)].cpu().numpy()
+        out = RoadCurves(xy, count)
+        out._inputs = (par,)   # (kept alive with the result)
+        return out
+
+
+class ParamPoly3:
+    """ParamPoly3 (interpolator/param_poly3.py) for batches: get_curve only (fit and split_polyline stay on the host)."""
+
+    @staticmethod
+    def get_curve(length, start_point, heading, aU, bU, cU, dU, aV, bV, cV, dV, p_range_type="normalized", max_points=None,
+                  device_id=0, stream=None):
+        """ParamPoly3.get_curve (param_poly3.py:17-65); the conventions of Spiral.get_curve.  A row has max(2, int(length / 0.1))
+        points: the result is ragged, count says how many rows of xy each curve has.  p_range_type: "normalized" / "arcLength",
+        one for all rows or a sequence of them (or int codes 0 / 1, an int32 tensor included); anything else is "normalized", as
+        in the reference.  max_points default: the longest row's count."""
+        import torch
+        single = not any(_is_tensor(v) or np.ndim(v) for v in (length, heading, aU, bU, cU, dU, aV, bV, cV, dV)) and not _is_tensor(start_point) and np.ndim(start_point) == 1
+        lib = _ffi.lib()
+        dev, st = _stream_of(device_id, stream)
+        with torch.cuda.stream(st):
+            sp = start_point.to(dev, torch.float64).reshape(-1, 2) if _is_tensor(start_point) else np.asarray(start_point, np.float64).reshape(-1, 2)
+            par = _columns(dev, (length, sp[:, 0], sp[:, 1], heading, aU, bU, cU, dU, aV, bV, cV, dV))
+            n = par.shape[0]
+            if _is_tensor(p_range_type):
+                p_range = p_range_type.to(dev, torch.int32).reshape(-1)
+            else:
+                codes = [v if isinstance(v, (int, np.integer)) else P_RANGES.get(v, L.P_RANGE_NORMALIZED)
+                         for v in ([p_range_type] if isinstance(p_range_type, (str, int, np.integer)) else list(p_range_type))]
+                p_range = torch.as_tensor(np.asarray(codes, np.int32)).to(dev)
+            p_range = (p_range.expand(n) if len(p_range) == 1 else p_range).contiguous()
+            if max_points is None:
+                finite = torch.nan_to_num(par[:, 0], nan=0.0, posinf=0.0, neginf=0.0).clamp(0.0, 1e8)
+                max_points = max(2, int((finite / 0.1).to(torch.int64).max()))
+            max_points = int(max_points)
+            xy = torch.empty((n, max(max_points, 0), 2), dtype=torch.float64, device=dev)
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+            _ffi.check(lib.t2d_param_poly3_curves(device_id, n, par.data_ptr(), p_range.data_ptr(), max_points, xy.data_ptr(),
+                                                  count.data_ptr(), st.cuda_stream), None, lib)
+        if single:
+            st.synchronize()
+            return xy[0, :min(int(count[0]), max_points)].cpu().numpy()
+        out = RoadCurves(xy, count)
+        out._inputs = (par, p_range)
+        return out
+
+
+def pack_planview(roads, max_geom=None):
+    """The records of t2d_planview_lines / t2d_planview_routes from parsed <planView> elements.  roads: one list per road of one
+    dict per <geometry>, with the OpenDRIVE attribute names: s, x, y, hdg, length and the child element under its own name as a
+    dict of ITS attributes -- {"s": 0.0, "x": .., "y": .., "hdg": .., "length": .., "arc": {"curvature": 0.05}}; "line": {} (or
+    None); "paramPoly3": {"aU": .., .., "dV": .., "pRange": "arcLength"} (pRange optional, "normalized" when absent or anything
+    else, as in the reference).  A flat dict naming the child under "type" with the child's attributes beside its own is taken
+    too.  Values may be numbers or the strings of the XML.  Returns (records float64 CPU tensor [n, max_geom, 14] -- the first
+    double of a record holds the two int32 kind and p_range --, n_geom int32 CPU tensor [n]); max_geom default: the longest road
+    (at least 1).  ValueError for a geometry without exactly one known child, a missing attribute, or more geometries than
+    max_geom / layout.PLANVIEW_MAX_GEOM."""
+    import torch
+    longest = max([len(r) for r in roads] + [1])
+    max_geom = longest if max_geom is None else int(max_geom)
+    if longest > max_geom or max_geom > L.PLANVIEW_MAX_GEOM or max_geom < 1:
+        raise ValueError(f"a road has {longest} geometries; max_geom is {max_geom}, the device cap layout.PLANVIEW_MAX_GEOM = {L.PLANVIEW_MAX_GEOM}")
+    rec = np.zeros((len(roads), max_geom, L.PLANVIEW_RECORD_BYTES // 8), np.float64)
+    head = rec.view(np.int32).reshape(len(roads), max_geom, L.PLANVIEW_RECORD_BYTES // 4)
+    for e, road in enumerate(roads):
+        for i, g in enumerate(road):
+            kinds = [k for k in GEOMETRY_KINDS if k in g] if "type" not in g else [g["type"]]
+            if len(kinds) != 1 or kinds[0] not in GEOMETRY_KINDS:
+                raise ValueError(f"road {e}, geometry {i}: exactly one of {sorted(GEOMETRY_KINDS)} is needed, got {kinds}")
+            child = g if "type" in g else (g[kinds[0]] or {})
+            try:
+                rec[e, i, 1:6] = [float(g[k]) for k in ("s", "x", "y", "hdg", "length")]
+                attrs = [float(child[k]) for k in GEOMETRY_ATTRIBUTES[kinds[0]]]
+            except KeyError as exc:
+                raise ValueError(f"road {e}, geometry {i} ({kinds[0]}): attribute {exc} is missing") from None
+            rec[e, i, 6:6 + len(attrs)] = attrs
+            head[e, i, 0] = GEOMETRY_KINDS[kinds[0]]
+            head[e, i, 1] = L.P_RANGE_ARC_LENGTH if child.get("pRange") == "arcLength" else L.P_RANGE_NORMALIZED
+    return torch.from_numpy(rec), torch.as_tensor(np.array([len(r) for r in roads], np.int32))
+
+
+def planview_inputs(dev, records, n_geom):
+    """(records float64 [n, max_geom, 14], n_geom int32 [n]) on `dev`, checked: what pack_planview returns, or the same on the device"""
+    import torch
+    if not _is_tensor(records) or records.dtype != torch.float64 or records.dim() != 3 or records.shape[2] != L.PLANVIEW_RECORD_BYTES // 8 \
+            or not 1 <= records.shape[1] <= L.PLANVIEW_MAX_GEOM:
+        raise ValueError(f"records must be a float64 tensor [n, max_geom <= {L.PLANVIEW_MAX_GEOM}, {L.PLANVIEW_RECORD_BYTES // 8}] (pack_planview)")
+    if not _is_tensor(n_geom) or tuple(n_geom.shape) != (records.shape[0],):
+        raise ValueError(f"n_geom must be an integer tensor [{records.shape[0]}]")
+    return records.to(dev).contiguous(), n_geom.to(dev, torch.int32).contiguous()
+
+
+def planview_max_points(records, n_geom):
+    """an upper bound of a road's raw (and so of its kept) points: per geometry int(length / 0.1) + 2, a spiral's 100"""
+    import torch
+    if records.shape[0] == 0:
+        return 1
+    length = torch.nan_to_num(records[:, :, 5], nan=0.0, posinf=0.0, neginf=0.0).clamp(0.0, 1e8)
+    used = torch.arange(records.shape[1], device=records.device)[None, :] < n_geom[:, None].to(records.device)
+    per = torch.maximum((length / 0.1).to(torch.int64) + 2, torch.tensor(100, device=records.device)) * used
+    return max(2, min(int(per.sum(1).max()), L.PLANVIEW_MAX_RAW))
+
+
+def planview_lines(records, n_geom, rule="reference", max_points=None, want_s=True, want_kappa=True, device_id=0, stream=None):
+    """t2d_planview_lines: the reference line of n roads in one launch, as load_road builds pts_arr, s_arr and kappa_arr
+    (map/parser/parse_xodr.py:773-809): every geometry sampled by its _sample_* method, a geometry's last point dropped where it
+    repeats the one before, then every point within 0.02 m of the RAW point before it dropped.  records, n_geom: pack_planview's
+    (CPU or CUDA tensors); rule: how spirals are evaluated (Spiral.get_curve); max_points default: a bound computed from the
+    lengths.  Asynchronous on `stream`.  Returns PlanviewLines (s / kappa None where not wanted)."""
+    import torch
+    rule = _rule(rule)
+    lib = _ffi.lib()
+    dev, st = _stream_of(device_id, stream)
+    with torch.cuda.stream(st):
+        records, n_geom = planview_inputs(dev, records, n_geom)
+        n, max_geom = records.shape[:2]
+        max_points = planview_max_points(records, n_geom) if max_points is None else int(max_points)
+        xy = torch.empty((n, max(max_points, 0), 2), dtype=torch.float64, device=dev)
+        s = torch.empty((n, max(max_points, 0)), dtype=torch.float64, device=dev) if want_s else None
+        kappa = torch.empty((n, max(max_points, 0)), dtype=torch.float64, device=dev) if want_kappa else None
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        _ffi.check(lib.t2d_planview_lines(device_id, n, records.data_ptr(), n_geom.data_ptr(), max_geom, rule, max_points, xy.data_ptr(),
+                                          _ptr(s), _ptr(kappa), count.data_ptr(), st.cuda_stream), None, lib)
+    out = PlanviewLines(xy, s, kappa, count)
+    out._inputs = (records, n_geom)
+    return out

@@ -76,6 +76,16 @@ SPLINE_NATURAL, SPLINE_CLAMPED, SPLINE_NOT_A_KNOT = 1, 2, 3
 SPLINE_MAX_CTRL, SPLINE_MAX_DEGREE = 32, 5
 SPLINE_CURVES_PER_BLOCK = 4
 PROFILE_SPLINE_ROUTES = 18
+# Spiral and ParamPoly3 curves and plan-view reference lines (t2d_spiral_curves / t2d_param_poly3_curves / t2d_planview_lines /
+# t2d_planview_routes): the spiral rules, the geometry kinds and pRange codes of a plan-view record, the record's size in bytes
+# (i32 kind, i32 p_range, f64 s, x, y, hdg, length, f64 par[8]), the caps, the curves that share a workgroup, the kernel id
+SPIRAL_REFERENCE, SPIRAL_STANDARD = 0, 1
+GEOM_LINE, GEOM_SPIRAL, GEOM_ARC, GEOM_POLY3, GEOM_PARAM_POLY3 = range(5)
+P_RANGE_NORMALIZED, P_RANGE_ARC_LENGTH = 0, 1
+PLANVIEW_RECORD_BYTES = 112
+PLANVIEW_MAX_GEOM, PLANVIEW_MAX_RAW = 64, 1 << 20
+ROAD_CURVES_PER_BLOCK = 4
+PROFILE_PLANVIEW_ROUTES = 19
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),

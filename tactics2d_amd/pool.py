@@ -586,6 +586,33 @@ class ParticipantPool:
         self._spline_inputs = inputs   # (kept alive until the launch has run)
         return count
 
+    def planview_routes(self, records, n_geom, stride=1, route=0, rule="reference", count=None, stream=None):
+        """t2d_planview_routes: the reference line of one OpenDRIVE plan view per env (records float64 [n_env, max_geom, 14] and
+        n_geom int [n_env] of interpolator.pack_planview, CPU or CUDA tensors; rule "reference" / "standard": how spirals are
+        evaluated, interpolator.Spiral.get_curve) into route `route` of each env's own route set, under the rules of
+        curve_routes.  A road has ten raw points per metre, hence stride >= 1: the vertices are the line's kept points 0, stride,
+        2 stride, ... and always its last one.  The route's vertex count is the capacity, vertices past the line's repeat its
+        last point, a line of more vertices than the capacity writes the first `capacity`, a road without a line leaves the
+        route as it is.  Needs set_routes with one set per env.  Returns the int32 CUDA tensor [n_env] of the lines' vertex
+        counts (`count`, or a new one).  Asynchronous."""
+        import torch
+        from . import interpolator as I
+        rule = I._rule(rule)
+        dev = torch.device("cuda", self.device_id)
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous()):
+            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
+        if hasattr(records, "shape") and len(records.shape) and records.shape[0] != self.n_env:
+            raise ValueError(f"records must hold one road per env: [{self.n_env}, max_geom, {L.PLANVIEW_RECORD_BYTES // 8}]")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):   # (uploads ahead of the launch, on its stream)
+            if count is None:
+                count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
+            inputs = I.planview_inputs(dev, records, n_geom)
+        self._ck(self._lib.t2d_planview_routes(self._h, inputs[0].data_ptr(), inputs[1].data_ptr(), inputs[0].shape[1], rule, int(stride),
+                                               int(route), count.data_ptr(), st))
+        self._planview_inputs = inputs   # (kept alive until the launch has run)
+        return count
+
     def route_vertices(self):
         """Zero-copy torch view float32 [n_vertices, 2] of the installed route sets' vertices on the device (t2d_route_vertices), in
         the order set_routes flattened them: what curve_routes writes into.  Valid until the routes are replaced or cleared.  The
