@@ -258,7 +258,7 @@ T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_i
     for (;;) {
         const int cnt = narrow ? __popc((uint32_t)mask) : __popcll(mask);
         if (__ballot(cnt > 0) == 0ull) break;
-        if (lane == 0) *qcount = 0;
+        if (lane == 0) *qcount = 0;   // (one lane, on purpose: DESIGN.md 8.26 (c))
         wave_sync();
         const int off = cnt > 0 ? atomicAdd(qcount, cnt) : kQueueCap;
         const int room = kQueueCap - off;
@@ -959,7 +959,10 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     {
         // rounds of 16-B loads this record needs (wave-uniform): 1 for the metric scenes (<= 4 KiB per workgroup) --
         // the unrolled generic form spends more on its per-load bounds logic than on the loads
-        const int rounds = stage_tables ? (n_vec + nthreads - 1) / nthreads : 0;
+        // (a shift: `nthreads` is a power of two -- envs_per_workgroup and rebuild_geo only ever halve 256 >> log2A -- and the
+        // division by a run-time value was thirty scalar instructions round a v_rcp_iflag_f32 / v_readfirstlane pair, a
+        // dependent chain every wave walked before it could issue its record loads)
+        const int rounds = stage_tables ? (n_vec + nthreads - 1) >> __builtin_ctz((unsigned)nthreads) : 0;
         u32x4 geo_stage0 = {0u, 0u, 0u, 0u};
         const int gtid = SPLIT ? ptid : tid;   // (the thread's own number: SPLIT's `tid` is the participant slot)
         if (rounds <= 1) {
@@ -1334,7 +1337,16 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         const double2* bnd = reinterpret_cast<const double2*>(s_geo + gl2.off_bnd);
         const double cx = (double)s_cxy[0][i], cy = (double)s_cxy[1][i];
         uint32_t bits = point_in_quad(load_quad_f32(xy + 2 * v0, n), cx, cy) ? 1u : 0u;   // 3 or 4 vertices (fans of quads)
-        bool cut = false;
+        // (`cut` is a word in a vector register, bit 1 = a piece meets the open pose.  As a bool it was a loop-carried LANE MASK
+        // in scalar registers, merged by three s_andn2 / s_and / s_or triples per trip of the piece loops below -- with the
+        // ballot's s_cmp / s_cselect / s_and twelve scalar instructions beside the trip's nineteen vector ones.  The exact test
+        // sits behind a plain divergent `if`: its saveexec + s_cbranch_execz IS the wave-uniform skip.)
+        // (Not in the launches with integrator waves only, PIPE = 1 -- the highway pool's chained form, whose lane stage hardly ever
+        // runs: with the word form its step measured 0.3 % slower than the parent's, five runs of five, so those instantiations keep
+        // the mask and the ballot: DESIGN.md 8.26.  Same verdicts either way.)
+        constexpr bool kCutWord = PIPE != 1;
+        [[maybe_unused]] uint32_t cut = 0u;
+        [[maybe_unused]] bool cut_mask = false;
         if (s_kind[i] == T2D_SHAPE_OBB) {
             // (c = the stored centre -- within 4.5e-13 m of the centre of the box the exact test sees, see RectEdges: inside the
             // margin's thousandfold.  The box is read whole once, ahead of the loop: in lane-dense envs some lane of the wave has
@@ -1347,8 +1359,10 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                 const double s1 = __builtin_fma(nx, cx - Pa.x, ny * (cy - Pa.y));
                 const double e2 = __builtin_fabs(__builtin_fma(nx, px, ny * py)) + __builtin_fabs(__builtin_fma(nx, qx, ny * qy));
                 const bool clear = __builtin_fabs(s1 + s1) > e2 + 2e-9 * (__builtin_fabs(nx) + __builtin_fabs(ny));
-                if (__ballot(!clear) != 0ull) {
-                    if (!clear) cut |= piece_meets_quad_interior(A, Pa.x, Pa.y, Pb.x, Pb.y);
+                if constexpr (kCutWord) {
+                    if (!clear) cut |= piece_meets_quad_interior(A, Pa.x, Pa.y, Pb.x, Pb.y) ? 2u : 0u;
+                } else if (__ballot(!clear) != 0ull) {
+                    if (!clear) cut_mask |= piece_meets_quad_interior(A, Pa.x, Pa.y, Pb.x, Pb.y);
                 }
             }
         } else {   // pedestrian: a piece inside the open disc.  The line AB further than R from the centre: so is the piece
@@ -1358,12 +1372,14 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                 const double nx = Pa.y - Pb.y, ny = Pb.x - Pa.x;
                 const double sn = __builtin_fma(nx, cx - Pa.x, ny * (cy - Pa.y));
                 const bool clear = sn * sn > R2 * __builtin_fma(nx, nx, ny * ny) * (1.0 + 1e-9);
-                if (__ballot(!clear) != 0ull) {
-                    if (!clear) cut |= seg_dist2(Pa.x, Pa.y, Pb.x, Pb.y, cx, cy) < R2;
+                if constexpr (kCutWord) {
+                    if (!clear) cut |= seg_dist2(Pa.x, Pa.y, Pb.x, Pb.y, cx, cy) < R2 ? 2u : 0u;
+                } else if (__ballot(!clear) != 0ull) {
+                    if (!clear) cut_mask |= seg_dist2(Pa.x, Pa.y, Pb.x, Pb.y, cx, cy) < R2;
                 }
             }
         }
-        if (cut) bits |= 2u;
+        if constexpr (kCutWord) bits |= cut; else if (cut_mask) bits |= 2u;
         if (bits) atomicOr(&s_flags[i], bits << kLaneShift);
     };
     int n_lane_polys = 0;
@@ -2032,6 +2048,7 @@ hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, in
                              hipStream_t s) {
     const int log2A = host::log2_pad(v.A);
     const int EPB = v.geo_layout.epb;
+    if (EPB <= 0 || (EPB & (EPB - 1))) return hipErrorInvalidValue;   // (the kernel stages its record in (EPB << log2A)-thread rounds counted by a SHIFT)
     if (cfg.check_no_action || cfg.check_arrival) return hipErrorInvalidValue;   // (see below)
     if (v.split_step) {   // small pool of 64-agent envs: one env per workgroup, chained per env
         const int padded = (v.n_env + 7) & ~7;
@@ -2101,6 +2118,7 @@ hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool 
                           int interval_ms, int fuse_variant, hipStream_t s) {
     const int log2A = host::log2_pad(v.A);   // (at least two lanes per env)
     const int EPB = v.geo_layout.epb;
+    if (EPB <= 0 || (EPB & (EPB - 1))) return hipErrorInvalidValue;   // (the kernel stages its record in (EPB << log2A)-thread rounds counted by a SHIFT)
     const dim3 grid((v.n_env + EPB - 1) / EPB), block(EPB << log2A);
     const size_t dyn = v.geo ? (size_t)v.geo_layout.stride * 4 : 0;
     const bool iou = cfg.check_no_action || cfg.check_arrival;
