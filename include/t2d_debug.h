@@ -8,7 +8,8 @@
  *
  * The -DT2D_DEBUG_HOOKS build differs from the product in exactly: these entry points, tactics2d_amd/csrc/t2d_loop.hip, the
  * math probe (tactics2d_amd/csrc/t2d_math_probe.hip and t2d_math_probe_table.hip, which compile t2d_math.h once more and touch
- * no product kernel), the geometry probe (t2d_geom_probe.hip: t2d_geom_dev.h once more, likewise), and two reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
+ * no product kernel), the geometry probe (t2d_geom_probe.hip: t2d_geom_dev.h once more, likewise), the wave-scan probe (a one-wave
+ * kernel at the end of t2d_collide.hip that calls the step kernel's wave_excl_scan), and two reads inside the step kernel (the placement map of a single launch, the fault word of a chained one).
  */
 #ifndef T2D_DEBUG_H_
 #define T2D_DEBUG_H_
@@ -93,6 +94,16 @@ enum {
 #define T2D_MATH_MAX_N 16777216
 int t2d_debug_math(int32_t device_id, int32_t fn, int32_t table, int64_t n, const double* a_host, const double* b_host,
                    double* out_host);
+
+/* ---- the step kernel's slot hand-out (wave_excl_scan, tactics2d_amd/csrc/t2d_collide.hip; tests/test_gpu_wave_scan.py) -----------
+ * compact_and_process gives every lane of a wave its first queue slot as the exclusive prefix sum of the lanes' candidate counts,
+ * computed in registers.  This runs that very function on n_waves waves, one per vector of 64 counts: cnt_host = int32
+ * [n_waves][64] (lane l of wave w holds cnt_host[64 w + l]); off_host = int32 [n_waves][64], the sum of the lanes below; total_host
+ * = int32 [n_waves], the sum of all 64.  Synchronous; uses the device's default stream.
+ * Errors (the text: t2d_last_error(NULL)): T2D_ERR_INVALID for n_waves outside [1, T2D_WAVE_SCAN_MAX_WAVES], a null array, an
+ * unknown device; T2D_ERR_HIP for a failing runtime call.                                                                     */
+#define T2D_WAVE_SCAN_MAX_WAVES 65536
+int t2d_debug_wave_scan(int32_t device_id, int32_t n_waves, const int32_t* cnt_host, int32_t* off_host, int32_t* total_host);
 
 /* ---- the device geometry predicates, one at a time (tactics2d_amd/csrc/t2d_geom_probe.hip; tests/test_gpu_geom.py) --------------
  * Evaluates ONE predicate of tactics2d_amd/csrc/t2d_geom_dev.h over host arrays on device `device_id`, compiled with the product's

@@ -126,6 +126,9 @@ res = dict(
     per_simd_mean_wave_life_us=dict(min=float(per_simd_busy.min()), mean=float(per_simd_busy.mean()), max=float(per_simd_busy.max()),
                                     std=float(per_simd_busy.std())),
     attribution_per_slot_and_step=table, attribution_sum_us=total,
+    compaction_rounds_per_wave_and_step=dict(mean=float((rec[S][..., 21] & np.uint64(0xffff)).mean()),
+                                             past_capacity_mean=float((rec[S][..., 21] >> np.uint64(16)).mean()),
+                                             max=int((rec[S][..., 21] & np.uint64(0xffff)).max())),
     by_env_kind=by_kind,
     timeline_us=timeline,
     note="timing build: the stamps cost ~ +10 % wave cycles (MI355X_MICROARCH.md); read shares, not absolutes, against the product's time",

@@ -1718,6 +1718,31 @@ int t2d_gather_wait(t2d_pool* p, void* hip_stream, int32_t block_host) {
 // test hook: the next CHAIN launches of the pool break one hand-off on purpose (include/t2d.h)
 #ifdef T2D_DEBUG_HOOKS   // include/t2d_debug.h: libt2d_hip_debug.so only
 const char* t2d_debug_last_step_kernel(void) { return t2d::last_collide_form(); }
+
+// the step kernel's slot hand-out, one wave per vector of 64 counts (include/t2d_debug.h)
+int t2d_debug_wave_scan(int32_t device_id, int32_t n_waves, const int32_t* cnt_host, int32_t* off_host, int32_t* total_host) {
+    if (n_waves < 1 || n_waves > T2D_WAVE_SCAN_MAX_WAVES)
+        return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_wave_scan: n_waves must be in [1, T2D_WAVE_SCAN_MAX_WAVES]");
+    if (!cnt_host || !off_host || !total_host) return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_wave_scan: a null array");
+    int n_dev = 0;
+    T2D_HIP(nullptr, hipGetDeviceCount(&n_dev));
+    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, T2D_ERR_INVALID, "t2d_debug_wave_scan: no such device");
+    T2D_HIP(nullptr, hipSetDevice(device_id));
+    t2d::DevBuf<int32_t> cnt, out;   // (freed on every way out)
+    T2D_HIP(nullptr, cnt.alloc((size_t)n_waves * 64));
+    T2D_HIP(nullptr, out.alloc((size_t)n_waves * 65));
+    T2D_HIP(nullptr, hipMemcpy(cnt, cnt_host, (size_t)n_waves * 64 * sizeof(int32_t), hipMemcpyHostToDevice));
+    T2D_HIP(nullptr, hipMemset(out, 0xff, (size_t)n_waves * 65 * sizeof(int32_t)));   // (-1: a word the kernel did not write shows)
+    T2D_HIP(nullptr, t2d::launch_wave_scan_probe(cnt, out, n_waves));
+    T2D_HIP(nullptr, hipDeviceSynchronize());
+    std::vector<int32_t> h((size_t)n_waves * 65);
+    T2D_HIP(nullptr, hipMemcpy(h.data(), out, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int w = 0; w < n_waves; ++w) {
+        for (int l = 0; l < 64; ++l) off_host[64 * w + l] = h[65 * (size_t)w + l];
+        total_host[w] = h[65 * (size_t)w + 64];
+    }
+    return T2D_OK;
+}
 #endif
 #ifdef T2D_DEBUG_HOOKS   // include/t2d_debug.h: libt2d_hip_debug.so only
 int t2d_debug_chain_fault(t2d_pool* p, int32_t kind) {

@@ -29,7 +29,7 @@
 //          so each unordered pair is tested once; larger envs walk an LDS spatial-hash grid (cell >=
 //          largest circum-diameter, atomicExch-built linked lists).
 //        * polygons: a branch-free box sweep over the env's polygons in the LDS record (same packed / sign-bit form).
-//      Survivors are compacted (one LDS atomic per lane) into a per-wave LDS queue and processed
+//      Survivors are compacted (slots from a prefix sum over the wave's lanes, in registers) into a per-wave LDS queue and processed
 //      one entry per lane -- dense lanes instead of per-lane divergent loops, and no register-
 //      resident per-participant state, which keeps the kernel at 4 waves / SIMD.  Odd waves visit the
 //      polygon stages before the pair stage so that a SIMD's waves are not in the same kind of stretch together.
@@ -54,6 +54,11 @@
 // s_sleep between two polls of a PIPE progress word, in units of 64 cycles.  A waiting wave shares its SIMD with the wave it
 // waits for: measured on cfg3 / cfg4 / cfg5 / cfg2 (us per step) 0: 8.9 / 6.4 / 9.4 / -; 1: 8.8 / 6.4 / 9.2 / 4.9; 4: 8.6 / 6.5 /
 // 8.7 / 4.9; 8: 8.6 / 6.6 / 8.6 / 4.9; 16: 8.5 / 6.9 / 8.7; 32: 8.6 / 7.6 / 9.1.
+// -DT2D_RESTORE_VIA_LDS=1: a measurement build in which the scalar epilogue hands its verdict to the auto-reset restore through
+// s_done again, every wave fetching the restore's pointers and meeting at a sync in every step (the form before DESIGN.md 8.27)
+#ifndef T2D_RESTORE_VIA_LDS
+#define T2D_RESTORE_VIA_LDS 0
+#endif
 #ifndef T2D_POLL_SLEEP
 #define T2D_POLL_SLEEP 4
 #endif
@@ -236,14 +241,33 @@ T2D_DEV void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// Exclusive prefix sum of `cnt` over the 64 lanes of the wave, in registers: returns the sum of the lanes below this one,
+// `total` = the sum of all 64 (wave-uniform, a scalar).  Six data-parallel-primitive additions -- row_shr 1, 2, 4, 8 scan
+// each row of 16 lanes, row_bcast:15 adds row r's sum to row r + 1 (rows 1 and 3), row_bcast:31 the lower half's to the
+// upper half -- and one v_readlane of lane 63: no LDS access, nothing to wait for.  A lane that a step gives no source
+// (the row's first lanes, the rows a broadcast skips) adds 0.  Must be called by all 64 lanes of the wave.
+T2D_DEV int wave_excl_scan(int cnt, int& total) {
+    int v = cnt;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2 and 3
+    total = __builtin_amdgcn_readlane(v, 63);
+    return v - cnt;
+}
+
 // Compact the set bits of every lane's `mask` into the wave's LDS queue (entry = tid | id << 8,
 // id = id_base + bit index) and run `process(entry)` densely, one entry per lane; repeats in
-// rounds of kQueueCap entries.  Slots are handed out by one LDS atomic per lane on the wave's
-// counter (cheaper than a 6-step shuffle scan; the order of entries is irrelevant).  Must be
-// called by all 64 lanes of the wave (mask 0 for idle lanes).
+// rounds of kQueueCap entries.  Slots are handed out by a prefix sum of the lanes' counts kept in
+// registers (wave_excl_scan); the order of entries is irrelevant.  Until DESIGN.md 8.27 the slots came
+// from one returning LDS atomic per lane on a per-wave counter, which lane 0 cleared first: a clear, up to
+// 64 atomics on one address and a read-back of the total per round, each an LDS round trip of its own with
+// nothing behind it to hide it.  Must be called by all 64 lanes of the wave (mask 0 for idle lanes).
 template <bool SWAP, bool RING = false, class F>
-T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_id, uint32_t* queue, int* qcount,
-                                 int lane, F process, bool narrow = false) {
+T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_id, uint32_t* queue,
+                                 int lane, F process, bool narrow = false, [[maybe_unused]] unsigned* tally = nullptr) {
     // entry = participant | other << 8.  SWAP = false: this lane is the participant (own_id = tid)
     // and the bits name the other object (id_base + bit); SWAP = true: this lane owns the other
     // object (own_id = polygon index) and the bits name participants (id_base + bit).
@@ -258,9 +282,12 @@ T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_i
     for (;;) {
         const int cnt = narrow ? __popc((uint32_t)mask) : __popcll(mask);
         if (__ballot(cnt > 0) == 0ull) break;
-        if (lane == 0) *qcount = 0;   // (one lane, on purpose: DESIGN.md 8.26 (c))
-        wave_sync();
-        const int off = cnt > 0 ? atomicAdd(qcount, cnt) : kQueueCap;
+        int total;
+        const int below = wave_excl_scan(cnt, total);
+#ifdef T2D_TIMING
+        if (tally) *tally += 1u + (total > kQueueCap ? 1u << 16 : 0u);   // (rounds | rounds that left entries behind << 16)
+#endif
+        const int off = cnt > 0 ? below : kQueueCap;   // (idle lanes emit nothing)
         const int room = kQueueCap - off;
         const int n_emit = room <= 0 ? 0 : (cnt < room ? cnt : room);
         if (narrow) {
@@ -279,10 +306,10 @@ T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_i
             }
         }
         wave_sync();
-        const int total = *qcount;
         const int n_round = total < kQueueCap ? total : kQueueCap;
         for (int k = lane; k < n_round; k += 64) process(queue[k]);
         wave_sync();
+        if (total <= kQueueCap) break;   // (every lane emitted all it had: no second look at the masks)
     }
 }
 
@@ -293,8 +320,10 @@ T2D_DEV void compact_and_process(unsigned long long mask, int id_base, int own_i
         if (lane == 0) { if (LOOP && !(CHAIN && step_k == step_first)) pv.dbg[wave_slot_ + k] += now_ - t_prev_; else pv.dbg[wave_slot_ + k] = now_ - t_prev_; } \
         t_prev_ = now_;                                                                 \
     } while (0)
+#define T2D_TALLY , &t_rounds_
 #else
 #define T2D_MARK(k)
+#define T2D_TALLY
 #endif
 
 // collide_kernel<WITH_STATUS, FUSE, IOU, CHAIN, LOOP, SPLIT, PIPE, IDMF>: ONE step body, instantiated in these forms (the flags
@@ -410,7 +439,6 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     __shared__ uint32_t s_flags[kBlock];
     __shared__ uint32_t s_env_or[kBlock / 2];  // per env of the workgroup (an env has at least 2 lanes)
     __shared__ uint32_t s_queue[PIPE == 2 ? 2 * kWaves : kWaves][kQueueCap];   // (PIPE = 2: the lane waves have queues of their own)
-    __shared__ int s_qcount[PIPE == 2 ? 2 * kWaves : kWaves];
     // the spatial-hash lists (envs wider than a wave only) live in the queue storage: they are dead
     // before the polygon stages start using the queues (workgroup barrier in between)
     static_assert(kMaxHeads + kBlock <= kWaves * kQueueCap, "hash grid must fit in the queue storage");
@@ -500,9 +528,9 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     const bool use_hash_grid = log2A > 6;  // envs larger than a wave use the LDS spatial hash
     const int H = 2 * A_pad;               // buckets per env (power of two)
     [[maybe_unused]] uint32_t* const queue = s_queue[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
-    [[maybe_unused]] int* const qcount = &s_qcount[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
 
 #ifdef T2D_TIMING
+    unsigned t_rounds_ = 0;   // rounds of compact_and_process this wave ran (word 21 of a CHAIN record; << 16: those past the capacity)
     unsigned long long t_prev_ = __builtin_readcyclecounter();
     // CHAIN: one record of 32 words per wave AND step (scripts/chain_timing.py): words 0-15 as below, 16 / 17 = the constant
     // 100 MHz clock (s_memrealtime) at the wave's start / end, 18 = cycles waiting for the hand-off, 19 = cycles of the tail
@@ -838,7 +866,6 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     const bool valid = env < a_n_env && agent < a_A;
     const int idx = valid ? env * a_A + agent : 0;
     uint32_t* const queue = s_queue[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
-    int* const qcount = &s_qcount[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
     if constexpr (LOOP) {
         pvp = late_args();
         cfgp = (const __attribute__((address_space(4))) t2d_status_config*)((const __attribute__((address_space(4))) char*)late_args() + kCfgArgOffset);
@@ -1493,7 +1520,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         }
         T2D_MARK(3);
         if (!active || (T2D_PROBE_SKIP & 2)) cand = 0ull;
-        compact_and_process<false, true>(cand, slot0, tid, queue, qcount, lane, process_ring, true);
+        compact_and_process<false, true>(cand, slot0, tid, queue, lane, process_ring, true T2D_TALLY);
     } else {
         // spatial-hash walk; pairs go straight to the narrow phase (i < j de-duplicates)
         if (active) {
@@ -1573,7 +1600,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                     unsigned long long m = box_sweep(bb, lo + c0, cn, ox, oy);
                     if (!want) m = 0ull;
                     T2D_MARK(mark);
-                    compact_and_process<false>(m, lo + c0, tid, queue, qcount, lane, process, cn <= 32);
+                    compact_and_process<false>(m, lo + c0, tid, queue, lane, process, cn <= 32 T2D_TALLY);
                     T2D_MARK(mark + 1);
                 }
             } else {
@@ -1583,7 +1610,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                     const int cn = left < 64 ? left : 64;
                     const unsigned long long m = cn > 0 ? box_sweep(bb, lo + c0, cn, ox, oy) : 0ull;
                     T2D_MARK(mark);
-                    compact_and_process<false>(m, lo + c0, tid, queue, qcount, lane, process);
+                    compact_and_process<false>(m, lo + c0, tid, queue, lane, process, false T2D_TALLY);
                     T2D_MARK(mark + 1);
                 }
             }
@@ -1735,16 +1762,27 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     }
     // One env per wave (64-participant envs) without IoU events, shaped reward or the tanh fall-back: everything the status
     // epilogue works on is ONE value per wave.  Made wave-uniform by v_readfirstlane, the ordered early-return logic of
-    // check_status, the reward table and the counters compile to SCALAR instructions -- the scalar pipe has slack (4.2
-    // cycles per instruction beside the VALU work of other waves, profiles/valu_issue_cycles.json) while the VALU is what
-    // bounds the launch: the wave issued ~100 VALU instructions here for the sake of one lane, now ~20 (the stores' data).
+    // check_status, the reward table and the counters compile to SCALAR instructions: the wave issued ~100 VALU instructions
+    // here for the sake of one lane, now ~20 (the stores' data).  (Round 4 took the scalar pipe to have slack -- 4.2 cycles per
+    // instruction beside the VALU work of other waves, profiles/valu_issue_cycles.json.  Measured since, DESIGN.md 8.26: it has
+    // none to give away -- a scalar instruction costs its issue slot like a vector one, the step's time moved by 0.6 of the
+    // scalar instructions taken out -- and the epilogue's 152 scalar instructions per wave are a cost, not a free ride.)
     // Same decisions, same bits: the generic path below, instruction for instruction, on the same inputs.
     bool epilogue_done = false;
+    // (wave-uniform) done_known: the scalar epilogue ran in this wave and left its env's verdict in done_s -- the restore then
+    // needs neither s_done nor a sync; false: the verdict is per env in s_done (envs narrower or wider than a wave, IOU, SPLIT)
+    bool done_known = false, done_s = false;
     if constexpr (WITH_STATUS && !IOU && !SPLIT) {
 #ifndef T2D_NO_SCALAR_EPILOGUE
         if (log2A == 6 && !cfg.shaped_reward && (cfg.max_step <= 0 || e_time_penalty) && !(T2D_PROBE_SKIP & 128)) {
             epilogue_done = true;
-            if (valid && agent == 0 && !role_b) {
+            // The verdict is worked out by the WHOLE wave, outside the branch of the lane that stores it: every input is a
+            // v_readfirstlane value (lane 0 = agent 0 fetched pre_cnt / pre_frame / pre_tp; the LDS words are one address), so
+            // scen .. done stay in scalar registers past the join and the restore below sits behind ONE scalar branch.  Inside
+            // the branch `done` would come out of it as a lane mask.  A wave whose env is past the pool works on zeros here,
+            // stores nothing (`lead` is false in every lane) and restores nothing (done_s).
+            const bool lead = valid && agent == 0 && !role_b;
+            {
                 const int env_s = __builtin_amdgcn_readfirstlane(env);
                 const uint32_t env_or = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_env_or[env_local]);
                 const uint32_t ef = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flags[slot0 + cfg.ego_index]);
@@ -1776,6 +1814,11 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                 const bool truncated = !terminated && (scen != T2D_SCENARIO_NORMAL || traf != T2D_TRAFFIC_NORMAL);
                 const uint32_t st = (uint32_t)scen | (uint32_t)traf << 8 | (uint32_t)terminated << 16 | (uint32_t)truncated << 24;
                 const bool done = e_auto_reset && (terminated || truncated);
+                if constexpr (!PIPE && !T2D_RESTORE_VIA_LDS) {
+                    done_known = true;
+                    done_s = done && __builtin_amdgcn_readfirstlane((int)valid) != 0;
+                }
+                if (lead) {   // (the stores: agent 0's lane of a wave that owns an env)
                 e_env_flags[env_s] = env_or;
                 e_cnt_step[env_s] = done ? 0 : cnt;
                 e_frame_ms[env_s] = done ? 0 : frame;
@@ -1790,8 +1833,8 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                 if (MULTI) ((T2D_GLOBAL unsigned long long*)e_record_ring)[(size_t)((e_record_slot0 + step_k) & (T2D_RECORD_RING - 1)) * (size_t)e_n_env + env_s] = rec;
                 else ((T2D_GLOBAL unsigned long long*)e_record)[env_s] = rec;
                 if (e_auto_reset) {
-                    s_done[env_local] = done;
-                    if (PIPE) s_dec[env_local] = done;   // (the integrator wave reads it before it commits the next step)
+                    if (PIPE || T2D_RESTORE_VIA_LDS) s_done[env_local] = done;
+                    if (PIPE) s_dec[env_local] = done;   // (the integrator wave restores: it reads s_dec before it commits the next step)
                     if (done) {  // ParkingEnv.reset: detector state back to the episode start (the counters: above)
                         e_last_valid[env_s] = 0;
                         e_cnt_na[env_s] = 0;
@@ -1799,6 +1842,7 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                         e_min_dist[env_s] = e_snap_min_dist[env_s];
                     }
                 }
+                }   // (lead)
             }
         }
 #endif
@@ -1916,6 +1960,9 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         // (the restore's eighteen pointers are requested here, in one scalar round trip, not with the epilogue's above: 36
         // more scalar registers held through the reduce and the status code pushed the kernel into scalar spills -- two
         // v_readlane / v_writelane per spilled value, ~300 VALU instructions per wave)
+        // ... and only by a wave that may have something to restore: with the scalar verdict that is one scalar branch, taken
+        // by the few waves whose env is over; the others go straight to the end of the step
+        if (!done_known || done_s) {
         const KernargView rp = late_args();
         auto e_snap0 = as_global(rp->snap[0]);
         auto e_snap1 = as_global(rp->snap[1]);
@@ -1936,8 +1983,10 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
         auto e_omega_f = as_global(rp->omega_f);
         auto e_omega_r = as_global(rp->omega_r);
         asm volatile("" : "+s"(e_snap0), "+s"(e_snap1), "+s"(e_snap2), "+s"(e_snap3), "+s"(e_snap4), "+s"(e_snap5), "+s"(e_snap_ids), "+s"(e_snap_omega0), "+s"(e_snap_omega1), "+s"(e_x), "+s"(e_y), "+s"(e_heading), "+s"(e_speed), "+s"(e_vx), "+s"(e_vy), "+s"(e_ids), "+s"(e_omega_f), "+s"(e_omega_r));
-        if (log2A <= 6) wave_sync(); else __syncthreads();
-        if (valid && s_done[env_local]) {
+        if (!done_known) {   // (the verdicts of the workgroup's envs are in s_done)
+            if (log2A <= 6) wave_sync(); else __syncthreads();
+        }
+        if (valid && (done_known || s_done[env_local])) {
             // every snapshot value first, then the stores: written as load / store pairs, each pair waits for its own
             // memory round trip (a store may alias the next load as far as the compiler knows) -- seven in a row at
             // the very end of the wave, where nothing is left to hide them
@@ -1965,9 +2014,15 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
                 e_omega_r[idx] = w1;
             }
         }
+        }   // (a wave that may have something to restore)
     }
     }   // (wave 0 of a SPLIT workgroup)
     T2D_MARK(12);
+#ifdef T2D_TIMING
+    if constexpr (CHAIN && !LOOP) {
+        if (lane == 0) pv.dbg[wave_slot_ + 21] = t_rounds_;
+    }
+#endif
     if (!LOOP) break;
     // LOOP: nothing is read back from memory (see `carried`); what the next trip clears in LDS is the wave's own when an env
     // fits a wave, else the workgroup meets first
@@ -2152,6 +2207,23 @@ hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool 
 
 #ifdef T2D_DEBUG_HOOKS
 const char* last_collide_form() { return g_last_collide_form; }
+
+// t2d_debug_wave_scan (include/t2d_debug.h; tests/test_gpu_wave_scan.py): wave_excl_scan as compact_and_process calls it -- all
+// 64 lanes of a wave, one count each -- on wave w's counts cnt[64 w ..]; out[65 w + lane] = the lane's offset, out[65 w + 64] =
+// the total.  One wave per workgroup.
+namespace {
+__global__ __launch_bounds__(64) void wave_scan_probe_kernel(const int32_t* __restrict__ cnt, int32_t* __restrict__ out) {
+    const int lane = (int)threadIdx.x, w = (int)blockIdx.x;
+    int total;
+    const int off = wave_excl_scan(cnt[64 * w + lane], total);
+    out[65 * w + lane] = off;
+    if (lane == 0) out[65 * w + 64] = total;
+}
+}  // namespace
+hipError_t launch_wave_scan_probe(const int32_t* cnt_dev, int32_t* out_dev, int n_waves) {
+    hipLaunchKernelGGL(wave_scan_probe_kernel, dim3((unsigned)n_waves), dim3(64), 0, 0, cnt_dev, out_dev);
+    return hipGetLastError();
+}
 #endif
 
 }  // namespace t2d

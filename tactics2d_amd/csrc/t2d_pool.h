@@ -700,6 +700,8 @@ size_t map_segment_bytes(int n_participants);   // the walk -> decisions hand-ov
 hipError_t launch_map_events(const PoolView& v, const MapGridView& mg, void* segments, uint32_t* out, hipStream_t s);
 #ifdef T2D_DEBUG_HOOKS
 const char* last_collide_form();   // template arguments of the collide_kernel instantiation the last launch took (t2d_collide.hip)
+// the step kernel's wave_excl_scan on n_waves waves of 64 counts each (t2d_collide.hip): out_dev = per wave 64 offsets + the total
+hipError_t launch_wave_scan_probe(const int32_t* cnt_dev, int32_t* out_dev, int n_waves);
 #endif
 hipError_t launch_frame_pack(const PoolView& v, const FrameView& fv, hipStream_t s);
 // note that work of this pool was enqueued on `s` by code outside t2d_api.hip (a replayed graph): t2d_sync waits for it

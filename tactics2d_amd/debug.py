@@ -14,6 +14,7 @@ libt2d_hip.so exports no t2d_debug_* symbol.
     env_groups(scene, G) / ClosedLoop policy kernel -> t2d_step per env group, enqueued by one C call
     math(fn, a, b=None, table=False)  one device function of csrc/t2d_math.h over arrays (tests/test_gpu_math.py)
     geom(fn, a, b=None)               one device predicate of csrc/t2d_geom_dev.h over arrays (tests/test_gpu_geom.py)
+    wave_scan(counts)                 the step kernel's prefix sum of 64 candidate counts (tests/test_gpu_wave_scan.py)
 """
 import ctypes as C
 import os
@@ -40,6 +41,7 @@ DEBUG_SYMBOLS = {
     "t2d_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "t2d_debug_geom": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "t2d_debug_memory": (C.c_int, [C.POINTER(C.c_int64)]),
+    "t2d_debug_wave_scan": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp]),
 }
 
 _debug_lib = None
@@ -154,6 +156,20 @@ def geom(fn, a, b=None, device_id=0):
     rc = lib().t2d_debug_geom(int(device_id), code, n, a.ctypes.data, b.ctypes.data if nb else None, out.ctypes.data)
     _ffi.check(rc, None, lib())
     return out[0] if nout == 1 else out
+
+
+def wave_scan(counts, device_id=0):
+    """t2d_debug_wave_scan: the step kernel's wave_excl_scan (csrc/t2d_collide.hip) on one wave per row of `counts` (int32
+    [n_waves, 64], or [64]).  Returns (offsets int32 like counts, totals int32 [n_waves] -- a scalar for one row)."""
+    c = np.ascontiguousarray(counts, np.int32)
+    if c.ndim not in (1, 2) or c.shape[-1] != 64:
+        raise ValueError("counts must be [64] or [n_waves, 64]")
+    c2 = c.reshape(-1, 64)
+    off = np.empty_like(c2)
+    total = np.empty(c2.shape[0], np.int32)
+    rc = lib().t2d_debug_wave_scan(int(device_id), c2.shape[0], c2.ctypes.data, off.ctypes.data, total.ctypes.data)
+    _ffi.check(rc, None, lib())
+    return (off[0], int(total[0])) if c.ndim == 1 else (off, total)
 
 
 class ClosedLoop:
