@@ -49,6 +49,7 @@
  *   t2d_curve_routes         Circle.get_arc  geometry/circle.py:106-139 (the curve written into the routes above)
  *   t2d_spline_curves /   <- Bezier.get_curve / BSpline.get_curve / CubicSpline.get_curve  interpolator/bezier.py, b_spline.py,
  *   t2d_spline_routes        cubic_spline.py over interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp
+ *   t2d_grid_dijkstra     <- Dijkstra.plan / plan_graph  search/dijkstra.py:24-394 over grid_to_csr  search/graph_utils.py:10-150
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -1156,6 +1157,43 @@ int t2d_planview_lines(int32_t device_id, int32_t n, const void* rec_dev, const 
                        int32_t max_points, double* xy_dev, double* s_dev, double* kappa_dev, int32_t* count_dev, void* hip_stream);
 int t2d_planview_routes(t2d_pool* pool, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule, int32_t stride,
                         int32_t route, int32_t* count_dev, void* hip_stream);
+
+/* Shortest paths over weighted obstacle grids on the device -- search/dijkstra.py (Dijkstra.plan, Dijkstra.plan_graph) over the
+ * graph of search/graph_utils.py: grid_to_csr, for n independent grids in ONE launch, asynchronous on hip_stream, no pool
+ * (tests/grid_search_ref.py).  One workgroup solves one grid with its weights and its field in LDS.
+ *   weight_dev  f64 [n][max_cells]: grid e is its first H * W entries, row-major; +inf or NaN marks an obstacle
+ *   hw_dev      i32 [n][2]: H and W of grid e (a ragged batch); source_dev / target_dev i32 [n]: cells row * W + col;
+ *               target -1 asks for the field alone
+ *   connectivity 4 or 8; diagonal_cost_multiplier: finite, >= 0
+ *   edges       never stored: between two neighbouring free cells (w[a] + w[b]) / 2.0, times the multiplier for a diagonal, fp64,
+ *               one rounding per operation -- grid_to_csr's expression.  An edge of weight EXACTLY 0 is no edge: the reference
+ *               walks graph[i].nonzero(), which drops stored zeros (two neighbouring cells of cost 0 are not connected).
+ *   g_dev       f64 [n][max_cells]: the cost-to-go field from the source, +inf in obstacles and unreached cells; BIT-EQUAL to the
+ *               reference's g_score where that has closed the cell (it is the fixed point of g[v] = min_u fl(g[u] + e(u, v))
+ *               whatever the order of relaxation).  Entries past H * W are not written.
+ *   path_dev    i32 [n][max_path]: the cells from source to target, -1 past the end; path_len_dev i32 [n]: the path's FULL
+ *               length in cells (> max_path: T2D_GRID_TRUNCATED, the first max_path cells are written); the reference's path in
+ *               every case: the predecessor of v is the neighbour u with fl(g[u] + e(u, v)) == g[v] and the smallest (g[u], u),
+ *               which is the order the reference's heap of (g, index) tuples closes nodes in.
+ *   status_dev  i32 [n]: T2D_GRID_*; sweeps_dev i32 [n]: the relaxation rounds the grid took.
+ * BUILD-DEFINED, per row, touching only that row: T2D_GRID_INVALID (field +inf over H * W, no path, 0 sweeps) where H or W is
+ * not positive or H * W is above max_cells, where source or target is out of range or an obstacle (also when
+ * target == source, where the reference returns the one-point path before it looks at the grid), or where a weight is negative.  max_iter is not modelled:
+ * the kernel always finishes, after at most H * W rounds.  Where a sum absorbs an edge (fl(g + e) == g) the candidates are
+ * further restricted to (g[u], u) < (g[v], v), and a chain that does not reach the source gives T2D_GRID_NO_PATH.
+ * T2D_ERR_GEOMETRY, nothing launched: max_cells above T2D_GRID_MAX_CELLS, the cap of the LDS form (two fp64 planes of 32 KiB,
+ * two workgroups per CU).  T2D_ERR_INVALID, nothing launched: n < 0, max_cells < 1, max_path < 0, another connectivity, a
+ * multiplier that is negative or not finite, a null or misaligned pointer (path_dev may be NULL when max_path is 0).          */
+#define T2D_GRID_FOUND 0
+#define T2D_GRID_NO_PATH 1
+#define T2D_GRID_TRUNCATED 2
+#define T2D_GRID_INVALID 3
+#define T2D_GRID_FIELD_ONLY 4
+#define T2D_GRID_MAX_CELLS 4096
+int t2d_grid_dijkstra(int32_t device_id, int32_t n, const double* weight_dev, const int32_t* hw_dev, const int32_t* source_dev,
+                      const int32_t* target_dev, int32_t max_cells, int32_t connectivity, double diagonal_cost_multiplier,
+                      int32_t max_path, double* g_dev, int32_t* path_dev, int32_t* path_len_dev, int32_t* status_dev,
+                      int32_t* sweeps_dev, void* hip_stream);
 
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes

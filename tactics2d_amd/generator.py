@@ -335,3 +335,41 @@ class TrackBatch:
     start_line: np.ndarray      # (n, 2, 2) f32
     boundary: np.ndarray        # (n, 4) f32 xmin, xmax, ymin, ymax
     flags: np.ndarray           # (n,) uint32 TRACK_CAPPED | TRACK_OVERFLOW
+
+
+class GridMapGenerator:
+    """Host restatement of map/generator/generate_grid_map.py: GridMapGenerator -- a random cost grid with obstacles (+inf), a
+    start and a goal cell, drawn from NUMPY'S GLOBAL STREAM draw for draw (random_seed reseeds it in the constructor, as the
+    reference does): the same seed gives the reference's grid, start and goal bit for bit.  Not a hot path; the grids go to the
+    device through tactics2d_amd.search."""
+
+    def __init__(self, size, min_cost=0, max_cost=5, obstacle_proportion=0.1, random_seed=None):
+        self.size = size
+        self.min_cost = min_cost
+        self.max_cost = max_cost
+        self.obstacle_proportion = obstacle_proportion
+        if random_seed is not None:
+            np.random.seed(random_seed)
+
+    def generate(self):
+        """(grid float64 [H, W], start (row, col), goal (row, col)); start and goal are free cells and differ"""
+        h, w = self.size
+        grid = np.random.randint(self.min_cost, self.max_cost + 1, size=self.size).astype(float)
+        obstacles = np.random.choice(h * w, int(h * w * self.obstacle_proportion), replace=False)
+        grid[obstacles // w, obstacles % w] = np.inf
+        while True:
+            start = (np.random.randint(0, h), np.random.randint(0, w))
+            if grid[start] != np.inf:
+                break
+        while True:
+            goal = (np.random.randint(0, h), np.random.randint(0, w))
+            if grid[goal] != np.inf and goal != start:
+                break
+        return grid, start, goal
+
+    def generate_batch(self, n):
+        """n consecutive generate() calls, stacked: grids float64 [n, H, W], starts int32 [n, 2], goals int32 [n, 2] (row, col)"""
+        out = [self.generate() for _ in range(int(n))]
+        h, w = self.size
+        return (np.stack([g for g, _, _ in out]) if out else np.zeros((0, h, w)),
+                np.asarray([s for _, s, _ in out], np.int32).reshape(-1, 2), np.asarray([t for _, _, t in out], np.int32).reshape(-1, 2))

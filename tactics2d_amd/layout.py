@@ -86,6 +86,9 @@ PLANVIEW_RECORD_BYTES = 112
 PLANVIEW_MAX_GEOM, PLANVIEW_MAX_RAW = 64, 1 << 20
 ROAD_CURVES_PER_BLOCK = 4
 PROFILE_PLANVIEW_ROUTES = 19
+# Grid shortest paths (t2d_grid_dijkstra): the status of a row, the cap on the cells of one grid (two fp64 planes in LDS)
+GRID_FOUND, GRID_NO_PATH, GRID_TRUNCATED, GRID_INVALID, GRID_FIELD_ONLY = range(5)
+GRID_MAX_CELLS = 4096
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),
