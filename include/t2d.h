@@ -1013,7 +1013,9 @@ int t2d_rs_plan_buffers(t2d_pool* pool, void** dev_ptr, size_t* nbytes);
  *                     c > capacity: the first `capacity` points.  count_dev i32 [n_env] (may be NULL) = c in every case.
  *                     t2d_off_route, t2d_pid_actions and t2d_pursuit_actions see the curve in their next launch on the stream.
  *                     Offsets, assignment and thresholds are untouched.  T2D_ERR_STATE unless route sets are the installed
- *                     kind, no two envs share a set and every env's set has a route `route`; T2D_ERR_INVALID as above.
+ *                     kind, no two envs share a set and every env's set has a route `route`; T2D_ERR_INVALID as above, for
+ *                     route < 0 and for a count_dev that is not 4-byte aligned (every INVALID before every STATE; the three
+ *                     route writers share these checks and their order): nothing is launched.
  *                     kernel_id T2D_PROFILE_CURVE_ROUTES in t2d_profile_read.
  *   t2d_route_vertices  the installed route sets' vertex storage, f32 [n_vertices][2] in the order of t2d_set_routes' verts_xy
  *                     (what t2d_curve_routes writes into and the three consumers read); valid until the routes are replaced or

@@ -333,6 +333,29 @@ int record_event(t2d_pool* p, int kernel_id, hipStream_t s, bool begin) {
     return T2D_OK;
 }
 
+// What t2d_curve_routes, t2d_spline_routes and t2d_planview_routes ask after their family's own argument check, and the bracket
+// around their launch: count_dev and route are arguments, the installed route sets state (route_slot in t2d_route_write_dev.h
+// relies on it).  launch(s) is the family's launch_*_routes line under T2D_HIP, so that a launch error names the call.
+template <class Launch>
+int write_routes(t2d_pool* p, const std::string& who, int profile_id, int32_t route, const int32_t* count_dev, void* hip_stream,
+                 Launch launch) {
+    if (reinterpret_cast<uintptr_t>(count_dev) & 3u) return fail(p, T2D_ERR_INVALID, who + ": misaligned count_dev");
+    if (route < 0) return fail(p, T2D_ERR_INVALID, who + ": route must be >= 0");
+    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, who + " writes into route sets: t2d_set_routes must precede it");
+    if (!p->route_sets_distinct)
+        return fail(p, T2D_ERR_STATE, who + ": two envs share a route set; install one set per env (set_of_env)");
+    if (route >= p->route_min_limit)
+        return fail(p, T2D_ERR_STATE, who + ": route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
+                                          std::to_string(p->route_min_limit) + " routes)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    touch(p, s);
+    int rc;
+    if ((rc = record_event(p, profile_id, s, true))) return rc;
+    if ((rc = launch(s))) return rc;
+    return record_event(p, profile_id, s, false);
+}
+
 }  // namespace
 
 
@@ -3154,20 +3177,10 @@ int t2d_curve_routes(t2d_pool* p, const void* words_dev, const double* start_dev
     if (!(radius > 0.0) || !std::isfinite(radius) || !(step_size > 0.0) || !std::isfinite(step_size))
         return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: radius and step_size must be positive and finite");
     if (rule != T2D_CURVE_DUBINS && rule != T2D_CURVE_RS) return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: rule must be T2D_CURVE_DUBINS or T2D_CURVE_RS");
-    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_curve_routes: route must be >= 0");
-    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_curve_routes writes into route sets: t2d_set_routes must precede it");
-    if (!p->route_sets_distinct)
-        return fail(p, T2D_ERR_STATE, "t2d_curve_routes: two envs share a route set; install one set per env (set_of_env)");
-    if (route >= p->route_min_limit)
-        return fail(p, T2D_ERR_STATE, "t2d_curve_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
-                                          std::to_string(p->route_min_limit) + " routes)");
-    hipStream_t s = (hipStream_t)hip_stream;
-    T2D_HIP(p, hipSetDevice(p->device));
-    touch(p, s);
-    int rc;
-    if ((rc = record_event(p, T2D_PROFILE_CURVE_ROUTES, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_curve_routes(p->v, p->route, words_dev, start_dev, radius, step_size, rule, route, count_dev, s));
-    return record_event(p, T2D_PROFILE_CURVE_ROUTES, s, false);
+    return write_routes(p, "t2d_curve_routes", T2D_PROFILE_CURVE_ROUTES, route, count_dev, hip_stream, [&](hipStream_t s) {
+        T2D_HIP(p, t2d::launch_curve_routes(p->v, p->route, words_dev, start_dev, radius, step_size, rule, route, count_dev, s));
+        return T2D_OK;
+    });
 }
 
 int t2d_spline_routes(t2d_pool* p, int32_t kind, const double* ctrl_dev, const int32_t* n_ctrl_dev, int32_t max_ctrl,
@@ -3177,22 +3190,11 @@ int t2d_spline_routes(t2d_pool* p, int32_t kind, const double* ctrl_dev, const i
     if (const char* why = t2d::spline_args_error(kind, ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev, boundary_type,
                                                  derivs_dev))
         return fail(p, T2D_ERR_INVALID, std::string("t2d_spline_routes: ") + why);
-    if (reinterpret_cast<uintptr_t>(count_dev) & 3u) return fail(p, T2D_ERR_INVALID, "t2d_spline_routes: misaligned count_dev");
-    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_spline_routes: route must be >= 0");
-    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_spline_routes writes into route sets: t2d_set_routes must precede it");
-    if (!p->route_sets_distinct)
-        return fail(p, T2D_ERR_STATE, "t2d_spline_routes: two envs share a route set; install one set per env (set_of_env)");
-    if (route >= p->route_min_limit)
-        return fail(p, T2D_ERR_STATE, "t2d_spline_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
-                                          std::to_string(p->route_min_limit) + " routes)");
-    hipStream_t s = (hipStream_t)hip_stream;
-    T2D_HIP(p, hipSetDevice(p->device));
-    touch(p, s);
-    int rc;
-    if ((rc = record_event(p, T2D_PROFILE_SPLINE_ROUTES, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_spline_routes(p->v, p->route, kind, ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev,
-                                         boundary_type, derivs_dev, route, count_dev, s));
-    return record_event(p, T2D_PROFILE_SPLINE_ROUTES, s, false);
+    return write_routes(p, "t2d_spline_routes", T2D_PROFILE_SPLINE_ROUTES, route, count_dev, hip_stream, [&](hipStream_t s) {
+        T2D_HIP(p, t2d::launch_spline_routes(p->v, p->route, kind, ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev,
+                                             boundary_type, derivs_dev, route, count_dev, s));
+        return T2D_OK;
+    });
 }
 
 int t2d_planview_routes(t2d_pool* p, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule, int32_t stride,
@@ -3201,21 +3203,10 @@ int t2d_planview_routes(t2d_pool* p, const void* rec_dev, const int32_t* n_geom_
     if (const char* why = t2d::planview_args_error(rec_dev, n_geom_dev, max_geom, rule))
         return fail(p, T2D_ERR_INVALID, std::string("t2d_planview_routes: ") + why);
     if (stride < 1) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: stride must be >= 1");
-    if (reinterpret_cast<uintptr_t>(count_dev) & 3u) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: misaligned count_dev");
-    if (route < 0) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: route must be >= 0");
-    if (p->route.kind != 1) return fail(p, T2D_ERR_STATE, "t2d_planview_routes writes into route sets: t2d_set_routes must precede it");
-    if (!p->route_sets_distinct)
-        return fail(p, T2D_ERR_STATE, "t2d_planview_routes: two envs share a route set; install one set per env (set_of_env)");
-    if (route >= p->route_min_limit)
-        return fail(p, T2D_ERR_STATE, "t2d_planview_routes: route " + std::to_string(route) + " does not exist in every env's set (the smallest set has " +
-                                          std::to_string(p->route_min_limit) + " routes)");
-    hipStream_t s = (hipStream_t)hip_stream;
-    T2D_HIP(p, hipSetDevice(p->device));
-    touch(p, s);
-    int rc;
-    if ((rc = record_event(p, T2D_PROFILE_PLANVIEW_ROUTES, s, true))) return rc;
-    T2D_HIP(p, t2d::launch_planview_routes(p->v, p->route, rec_dev, n_geom_dev, max_geom, rule, stride, route, count_dev, s));
-    return record_event(p, T2D_PROFILE_PLANVIEW_ROUTES, s, false);
+    return write_routes(p, "t2d_planview_routes", T2D_PROFILE_PLANVIEW_ROUTES, route, count_dev, hip_stream, [&](hipStream_t s) {
+        T2D_HIP(p, t2d::launch_planview_routes(p->v, p->route, rec_dev, n_geom_dev, max_geom, rule, stride, route, count_dev, s));
+        return T2D_OK;
+    });
 }
 
 int t2d_route_vertices(t2d_pool* p, void** verts_dev, size_t* n_vertices) {

@@ -1,9 +1,10 @@
 // t2d_curve.hip -- Dubins candidates for a batch of queries (dubins_paths_kernel), the sampled curve line of one Dubins or
 // Reeds-Shepp word per curve (curve_lines_kernel), and the same sampler writing fp32 vertices into the installed route sets
-// (curve_routes_kernel).  The formulas are t2d_curve_dev.h; what they restate is interpolator/dubins.py,
-// interpolator/reeds_shepp.py:46-139 and geometry/circle.py:106-139.  DESIGN.md 4.18.
+// (curve_routes_kernel), whose slot and fill are t2d_route_write_dev.h.  The formulas are t2d_curve_dev.h; what they restate is
+// interpolator/dubins.py, interpolator/reeds_shepp.py:46-139 and geometry/circle.py:106-139.  DESIGN.md 4.18, 4.18a.
 #include "t2d_pool.h"
 #include "t2d_curve_dev.h"
+#include "t2d_route_write_dev.h"
 
 namespace t2d {
 namespace {
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(kCurveBlock) void curve_lines_kernel(const CurveWor
         const bool ok = curve_plan(words[e], start[3 * (size_t)e], start[3 * (size_t)e + 1], start[3 * (size_t)e + 2], radius, step,
                                    rule, s_plan, total);
         s_total = total;
-        count[e] = total > 2147483647ll ? 2147483647 : (int32_t)total;
+        count[e] = point_count(total);
         if (ok) {
             end[3 * (size_t)e] = s_plan.end[0];
             end[3 * (size_t)e + 1] = s_plan.end[1];
@@ -85,38 +86,27 @@ __global__ __launch_bounds__(kCurveBlock) void curve_lines_kernel(const CurveWor
     }
 }
 
-// The same sampler, curve e into route `route` of env e's own set: vertex k < count is point k rounded to fp32, vertex k >= count
-// the curve's end point; a curve without points leaves the route as it is.  The host has checked that no two envs share a set
-// and that every env's set has the route.
+// The same sampler, curve e into route `route` of env e's own set (t2d_route_write_dev.h): the tail is the curve's end point; a
+// curve without points leaves the route as it is.  The plan stage is curve_lines_kernel's without `end`, and stays written out
+// in both: moved into a function the two call, the lines kernel came out 0.33 us slower.
 __global__ __launch_bounds__(kCurveBlock) void curve_routes_kernel(RouteView rv, const CurveWord* __restrict__ words,
                                                                    const double* __restrict__ start, double radius, double step,
                                                                    int rule, int route, int32_t* __restrict__ count) {
     __shared__ CurvePlan s_plan;
     __shared__ long long s_total;
-    const int e = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) {
+    const int e = blockIdx.x;
+    if (threadIdx.x == 0) {
         long long total;
         curve_plan(words[e], start[3 * (size_t)e], start[3 * (size_t)e + 1], start[3 * (size_t)e + 2], radius, step, rule, s_plan,
                    total);
         s_total = total;
-        if (count) count[e] = total > 2147483647ll ? 2147483647 : (int32_t)total;
+        if (count) count[e] = point_count(total);
     }
     __syncthreads();
     const long long total = s_total;
     if (total == 0) return;
-    const int r = rv.set_route_start[rv.set_of_env[e]] + route;
-    const int v0 = rv.route_vert_off[r], cap = rv.route_vert_off[r + 1] - v0;
-    float2* out = reinterpret_cast<float2*>(const_cast<float*>(rv.verts)) + v0;
-    const float2 tail = make_float2((float)s_plan.end[0], (float)s_plan.end[1]);
-    for (int k = tid; k < cap; k += kCurveBlock) {
-        float2 v = tail;
-        if (k < total) {
-            double x, y, h;
-            curve_point(s_plan, radius, k, x, y, h);
-            v = make_float2((float)x, (float)y);
-        }
-        out[k] = v;
-    }
+    route_fill(route_slot(rv, e, route), threadIdx.x, kCurveBlock, total, make_float2((float)s_plan.end[0], (float)s_plan.end[1]),
+               [&](int k, double& x, double& y) { double h; curve_point(s_plan, radius, k, x, y, h); });
 }
 
 }  // namespace

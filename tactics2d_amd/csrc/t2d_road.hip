@@ -1,9 +1,10 @@
 // t2d_road.hip -- Spiral and ParamPoly3 curves for a batch of parameter rows (spiral_curves_kernel, param_poly3_curves_kernel), the
 // reference line of a batch of OpenDRIVE plan views (planview_kernel<false>) and the same chain writing fp32 vertices into the
-// installed route sets (planview_kernel<true>).  The formulas are t2d_road_dev.h; what they restate is interpolator/spiral.py,
-// interpolator/param_poly3.py and map/parser/parse_xodr.py:256-474, 773-809.  DESIGN.md 4.20.
+// installed route sets (planview_kernel<true>, whose slot is t2d_route_write_dev.h's).  The formulas are t2d_road_dev.h; what they
+// restate is interpolator/spiral.py, interpolator/param_poly3.py and map/parser/parse_xodr.py:256-474, 773-809.  DESIGN.md 4.20, 4.18a.
 #include "t2d_pool.h"
 #include "t2d_road_dev.h"
+#include "t2d_route_write_dev.h"
 
 namespace t2d {
 
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kRoadBlock) void param_poly3_curves_kernel(int n, c
 //   ROUTES = false: kept point q -> xy / s / kappa [e][q], q < max_points; count = kept points, 0 where fewer than 2.
 //   ROUTES = true:  kept points 0, stride, 2 stride, ... and the last one -> the fp32 vertices of route `route` of env e's set;
 //                   count = the number of such vertices V; V < capacity: the rest repeats the last kept point; V > capacity: the
-//                   first `capacity`.  The host has checked that no two envs share a set and that every env's set has the route.
+//                   first `capacity`.  The slot is route_slot's (t2d_route_write_dev.h); the strided store pattern is this kernel's.
 template <bool ROUTES>
 __global__ __launch_bounds__(kRoadBlock) void planview_kernel(RouteView rv, int n, const PlanviewRecord* __restrict__ rec,
                                                               const int32_t* __restrict__ n_geom, int max_geom, int rule, int stride,
@@ -83,11 +84,9 @@ __global__ __launch_bounds__(kRoadBlock) void planview_kernel(RouteView rv, int 
     RoadPoint head, tail;
     int kept = 0;
     if constexpr (ROUTES) {
-        const int r = rv.set_route_start[rv.set_of_env[e]] + route;
-        const int v0 = rv.route_vert_off[r], cap = rv.route_vert_off[r + 1] - v0;
-        float2* out = reinterpret_cast<float2*>(const_cast<float*>(rv.verts)) + v0;
+        const RouteSlot slot = route_slot(rv, e, route);
         kept = road_walk(w, rule, lane, head, tail, [&](int q, const RoadPoint& p) {
-            if (q % stride == 0 && q / stride < cap) out[q / stride] = make_float2((float)p.x, (float)p.y);
+            if (q % stride == 0 && q / stride < slot.cap) slot.out[q / stride] = make_float2((float)p.x, (float)p.y);
         });
         if (kept < 2) {
             if (lane == 0 && count) count[e] = 0;
@@ -98,10 +97,10 @@ __global__ __launch_bounds__(kRoadBlock) void planview_kernel(RouteView rv, int 
         const float2 last = make_float2((float)tail.x, (float)tail.y);
         if (lane == 0) {
             if (count) count[e] = V;
-            if (cap > 0) out[0] = make_float2((float)head.x, (float)head.y);
-            if (extra && V - 1 < cap) out[V - 1] = last;
+            if (slot.cap > 0) slot.out[0] = make_float2((float)head.x, (float)head.y);
+            if (extra && V - 1 < slot.cap) slot.out[V - 1] = last;
         }
-        for (int k = V + lane; k < cap; k += kRoadWave) out[k] = last;
+        for (int k = V + lane; k < slot.cap; k += kRoadWave) slot.out[k] = last;
     } else {
         double2* oxy = xy + (size_t)e * max_points;
         double* os = s_out ? s_out + (size_t)e * max_points : nullptr;

@@ -1,8 +1,13 @@
 // t2d_spline.hip -- Bezier, B-spline and cubic spline curves for a batch of control polygons (spline_curves_kernel) and the same
-// sampler writing fp32 vertices into the installed route sets (spline_routes_kernel).  The formulas are t2d_spline_dev.h; what
-// they restate is interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp.  DESIGN.md 4.19.
+// sampler writing fp32 vertices into the installed route sets (spline_routes_kernel); the two share their prologue
+// (spline_prologue) and the kind -> instantiation choice (for_spline_kind), and the route form's slot and fill are
+// t2d_route_write_dev.h.  The formulas are t2d_spline_dev.h; what they restate is
+// interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp.  DESIGN.md 4.19, 4.18a.
+#include <type_traits>
+
 #include "t2d_pool.h"
 #include "t2d_spline_dev.h"
+#include "t2d_route_write_dev.h"
 
 namespace t2d {
 
@@ -17,7 +22,19 @@ namespace {
 // lanes store consecutive 16-byte points, whole cache lines per wave.  A wave past the batch's end only keeps the barriers.
 constexpr int kSplineWave = 64, kSplineCurvesPerBlock = T2D_SPLINE_CURVES_PER_BLOCK, kSplineBlock = kSplineWave * kSplineCurvesPerBlock;
 
-T2D_DEV int32_t spline_count(long long total) { return total > 2147483647ll ? 2147483647 : (int32_t)total; }
+// What both kernels start with: the wave's lanes load row e, lane 0 sets the curve up and reports its count (ROUTES: count may be
+// null), then w.total is the number of points of the whole curve.  A wave past the batch's end passes both barriers and is told so.
+template <bool ROUTES, int KIND>
+T2D_DEV bool spline_prologue(SplineWork<KIND>& w, const SplineArgs& a, int n, int e, int lane, int32_t* count) {
+    if (e < n) spline_load(w, a, e, lane);
+    __syncthreads();
+    if (e < n && lane == 0) {
+        spline_setup(w, a, e);
+        if (!ROUTES || count) count[e] = point_count(w.total);
+    }
+    __syncthreads();
+    return e < n;
+}
 
 template <int KIND>
 __global__ __launch_bounds__(kSplineBlock) void spline_curves_kernel(SplineArgs a, int n, int max_points, double2* __restrict__ xy,
@@ -26,14 +43,7 @@ __global__ __launch_bounds__(kSplineBlock) void spline_curves_kernel(SplineArgs 
     const int wave = threadIdx.x / kSplineWave, lane = threadIdx.x % kSplineWave;
     const int e = blockIdx.x * kSplineCurvesPerBlock + wave;
     SplineWork<KIND>& w = s_work[wave];
-    if (e < n) spline_load(w, a, e, lane);
-    __syncthreads();
-    if (e < n && lane == 0) {
-        spline_setup(w, a, e);
-        count[e] = spline_count(w.total);
-    }
-    __syncthreads();
-    if (e >= n) return;
+    if (!spline_prologue<false>(w, a, n, e, lane, count)) return;
     const long long total = w.total;
     const int m = total < (long long)max_points ? (int)total : max_points;
     double2* out = xy + (size_t)e * max_points;
@@ -44,9 +54,9 @@ __global__ __launch_bounds__(kSplineBlock) void spline_curves_kernel(SplineArgs 
     }
 }
 
-// The same sampler, curve e into route `route` of env e's own set: vertex k < count is point k rounded to fp32, vertex k >= count
-// the curve's last point (for a B-spline its last SAMPLE); a row without a curve leaves the route as it is.  The host has checked
-// that no two envs share a set and that every env's set has the route.
+// The same sampler, curve e into route `route` of env e's own set (t2d_route_write_dev.h): the tail is the curve's last point (for
+// a B-spline its last SAMPLE), computed only where the route is longer than the curve; a row without a curve leaves the route as
+// it is.
 template <int KIND>
 __global__ __launch_bounds__(kSplineBlock) void spline_routes_kernel(RouteView rv, SplineArgs a, int n, int route,
                                                                      int32_t* __restrict__ count) {
@@ -54,34 +64,26 @@ __global__ __launch_bounds__(kSplineBlock) void spline_routes_kernel(RouteView r
     const int wave = threadIdx.x / kSplineWave, lane = threadIdx.x % kSplineWave;
     const int e = blockIdx.x * kSplineCurvesPerBlock + wave;
     SplineWork<KIND>& w = s_work[wave];
-    if (e < n) spline_load(w, a, e, lane);
-    __syncthreads();
-    if (e < n && lane == 0) {
-        spline_setup(w, a, e);
-        if (count) count[e] = spline_count(w.total);
-    }
-    __syncthreads();
-    if (e >= n) return;
+    if (!spline_prologue<true>(w, a, n, e, lane, count)) return;
     const long long total = w.total;
     if (total == 0) return;
-    const int r = rv.set_route_start[rv.set_of_env[e]] + route;
-    const int v0 = rv.route_vert_off[r], cap = rv.route_vert_off[r + 1] - v0;
-    float2* out = reinterpret_cast<float2*>(const_cast<float*>(rv.verts)) + v0;
+    const RouteSlot slot = route_slot(rv, e, route);
+    auto point = [&](long long k, double& x, double& y) { spline_point(w, a, k, x, y); };
     float2 tail = make_float2(0.f, 0.f);
-    if (total < cap) {
+    if (total < slot.cap) {
         double x, y;
-        spline_point(w, a, total - 1, x, y);
+        point(total - 1, x, y);
         tail = make_float2((float)x, (float)y);
     }
-    for (int k = lane; k < cap; k += kSplineWave) {
-        float2 v = tail;
-        if (k < total) {
-            double x, y;
-            spline_point(w, a, k, x, y);
-            v = make_float2((float)x, (float)y);
-        }
-        out[k] = v;
-    }
+    route_fill(slot, lane, kSplineWave, total, tail, point);
+}
+
+// the kernel instantiation of a kind that spline_args_error has passed: f(std::integral_constant<int, KIND>)
+template <class F>
+void for_spline_kind(int kind, F f) {
+    if (kind == SPLINE_BEZIER) f(std::integral_constant<int, SPLINE_BEZIER>{});
+    else if (kind == SPLINE_BSPLINE) f(std::integral_constant<int, SPLINE_BSPLINE>{});
+    else f(std::integral_constant<int, SPLINE_CUBIC>{});
 }
 
 SplineArgs spline_args(const double* ctrl, const int32_t* n_ctrl, int max_ctrl, int n_interp, int degree, const double* knots,
@@ -118,10 +120,9 @@ hipError_t launch_spline_routes(const PoolView& v, const RouteView& rv, int kind
                                 int max_ctrl, int n_interp, int degree, const double* knots, int boundary, const double* derivs,
                                 int route, int32_t* count, hipStream_t s) {
     const SplineArgs a = spline_args(ctrl, n_ctrl, max_ctrl, n_interp, degree, knots, boundary, derivs);
-    const dim3 grid(spline_blocks(v.n_env)), block(kSplineBlock);
-    if (kind == SPLINE_BEZIER) hipLaunchKernelGGL(spline_routes_kernel<SPLINE_BEZIER>, grid, block, 0, s, rv, a, v.n_env, route, count);
-    else if (kind == SPLINE_BSPLINE) hipLaunchKernelGGL(spline_routes_kernel<SPLINE_BSPLINE>, grid, block, 0, s, rv, a, v.n_env, route, count);
-    else hipLaunchKernelGGL(spline_routes_kernel<SPLINE_CUBIC>, grid, block, 0, s, rv, a, v.n_env, route, count);
+    for_spline_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL(spline_routes_kernel<decltype(k)::value>, dim3(spline_blocks(v.n_env)), dim3(kSplineBlock), 0, s, rv, a, v.n_env, route, count);
+    });
     return hipGetLastError();
 }
 
@@ -139,11 +140,9 @@ extern "C" int t2d_spline_curves(int32_t device_id, int32_t n, int32_t kind, con
     if (n == 0) return T2D_OK;
     if (hipSetDevice(device_id) != hipSuccess) return T2D_ERR_HIP;
     const SplineArgs a = spline_args(ctrl_dev, n_ctrl_dev, max_ctrl, n_interpolation, degree, knots_dev, boundary_type, derivs_dev);
-    const dim3 grid(spline_blocks(n)), block(kSplineBlock);
-    hipStream_t s = (hipStream_t)hip_stream;
-    double2* xy = reinterpret_cast<double2*>(xy_dev);
-    if (kind == SPLINE_BEZIER) hipLaunchKernelGGL(spline_curves_kernel<SPLINE_BEZIER>, grid, block, 0, s, a, n, max_points, xy, count_dev);
-    else if (kind == SPLINE_BSPLINE) hipLaunchKernelGGL(spline_curves_kernel<SPLINE_BSPLINE>, grid, block, 0, s, a, n, max_points, xy, count_dev);
-    else hipLaunchKernelGGL(spline_curves_kernel<SPLINE_CUBIC>, grid, block, 0, s, a, n, max_points, xy, count_dev);
+    for_spline_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL(spline_curves_kernel<decltype(k)::value>, dim3(spline_blocks(n)), dim3(kSplineBlock), 0, (hipStream_t)hip_stream, a, n,
+                           max_points, reinterpret_cast<double2*>(xy_dev), count_dev);
+    });
     return hipGetLastError() == hipSuccess ? T2D_OK : T2D_ERR_HIP;
 }

@@ -3,6 +3,7 @@
 Host logic only: argument marshalling and error translation.  All compute happens in the
 HIP kernels behind libt2d_hip.so.
 """
+import contextlib
 import ctypes as C
 import sys
 
@@ -533,6 +534,19 @@ class ParticipantPool:
         off_route_all()).  Asynchronous on `stream`; reads the pool's current state, changes nothing in it."""
         self._ck(self._lib.t2d_off_route(self._h, dist_ptr, off_ptr, stream))
 
+    @contextlib.contextmanager
+    def _route_writer(self, count, stream):
+        """What curve_routes / spline_routes / planview_routes start with: the pool's device, the launch stream (`stream`, or
+        torch's current one) and the int32 [n_env] count tensor (`count` checked, or a new one), inside a torch stream context
+        of the launch stream, so that uploads and conversions made in it run ahead of the launch."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous()):
+            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):
+            yield dev, st, torch.zeros(self.n_env, dtype=torch.int32, device=dev) if count is None else count
+
     def curve_routes(self, words, starts, radius, step_size, rule, route=0, count=None, stream=None):
         """t2d_curve_routes: sample one curve per env (interpolator.pack_words records, float64 CUDA tensor [n_env, 6]; starts float64
         CUDA tensor [n_env, 3]; rule layout.CURVE_DUBINS / CURVE_RS or "dubins" / "rs") into route `route` of each env's own route
@@ -541,19 +555,14 @@ class ParticipantPool:
         env.  off_route / pid_actions / pursuit_actions see the curve in their next launch on `stream`.  Returns the int32 CUDA
         tensor [n_env] of the curves' full point counts (`count`, or a new one).  Asynchronous."""
         import torch
-        dev = torch.device("cuda", self.device_id)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         rule = {"dubins": L.CURVE_DUBINS, "rs": L.CURVE_RS}.get(rule, rule)
         if words.dtype != torch.float64 or tuple(words.shape) != (self.n_env, L.CURVE_WORD_BYTES // 8) or not words.is_contiguous():
             raise ValueError(f"words must be a contiguous float64 [{self.n_env}, 6] tensor (interpolator.pack_words)")
         if starts.dtype != torch.float64 or tuple(starts.shape) != (self.n_env, 3) or not starts.is_contiguous():
             raise ValueError(f"starts must be a contiguous float64 [{self.n_env}, 3] tensor")
-        if count is None:
-            count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
-        elif count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous():
-            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
-        self._ck(self._lib.t2d_curve_routes(self._h, words.data_ptr(), starts.data_ptr(), float(radius), float(step_size), int(rule),
-                                            int(route), count.data_ptr(), st))
+        with self._route_writer(count, stream) as (_, st, count):
+            self._ck(self._lib.t2d_curve_routes(self._h, words.data_ptr(), starts.data_ptr(), float(radius), float(step_size),
+                                                int(rule), int(route), count.data_ptr(), st))
         self._curve_inputs = (words, starts)   # (kept alive until the launch has run)
         return count
 
@@ -565,19 +574,12 @@ class ParticipantPool:
         the route's vertex count is the capacity, vertices past the curve's points repeat its last point (for a B-spline its last
         sample, not the curve's end), a row without a curve leaves the route as it is.  Needs set_routes with one set per env.
         Returns the int32 CUDA tensor [n_env] of the curves' full point counts (`count`, or a new one).  Asynchronous."""
-        import torch
         from . import interpolator as I
         kind, n, m, n_interpolation, degree, boundary_type, _ = I.spline_check(kind, control_points, n_ctrl, n_interpolation, degree,
                                                                                knot_vectors, boundary_type, first_derivatives)
         if n != self.n_env:
             raise ValueError(f"control_points must hold one control polygon per env: [{self.n_env}, m, 2]")
-        dev = torch.device("cuda", self.device_id)
-        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous()):
-            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):   # (uploads and conversions ahead of the launch, on its stream)
-            if count is None:
-                count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
+        with self._route_writer(count, stream) as (dev, st, count):
             inputs = I.spline_inputs(dev, n, m, control_points, n_ctrl, knot_vectors, first_derivatives)
         ctrl, n_ctrl, knots, derivs = inputs
         self._ck(self._lib.t2d_spline_routes(self._h, kind, ctrl.data_ptr(), n_ctrl.data_ptr(), m, n_interpolation, degree,
@@ -595,18 +597,11 @@ class ParticipantPool:
         last point, a line of more vertices than the capacity writes the first `capacity`, a road without a line leaves the
         route as it is.  Needs set_routes with one set per env.  Returns the int32 CUDA tensor [n_env] of the lines' vertex
         counts (`count`, or a new one).  Asynchronous."""
-        import torch
         from . import interpolator as I
         rule = I._rule(rule)
-        dev = torch.device("cuda", self.device_id)
-        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.n_env,) or not count.is_contiguous()):
-            raise ValueError(f"count must be a contiguous int32 [{self.n_env}] tensor")
-        if hasattr(records, "shape") and len(records.shape) and records.shape[0] != self.n_env:
-            raise ValueError(f"records must hold one road per env: [{self.n_env}, max_geom, {L.PLANVIEW_RECORD_BYTES // 8}]")
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):   # (uploads ahead of the launch, on its stream)
-            if count is None:
-                count = torch.zeros(self.n_env, dtype=torch.int32, device=dev)
+        with self._route_writer(count, stream) as (dev, st, count):
+            if hasattr(records, "shape") and len(records.shape) and records.shape[0] != self.n_env:
+                raise ValueError(f"records must hold one road per env: [{self.n_env}, max_geom, {L.PLANVIEW_RECORD_BYTES // 8}]")
             inputs = I.planview_inputs(dev, records, n_geom)
         self._ck(self._lib.t2d_planview_routes(self._h, inputs[0].data_ptr(), inputs[1].data_ptr(), inputs[0].shape[1], rule, int(stride),
                                                int(route), count.data_ptr(), st))

@@ -13,6 +13,7 @@ import curve_ref as CR
 import pid_scenes as PS
 import pursuit_scenes as US
 import rs_scenes as S
+from route_writers import A, N_ENV, placeholder, route_pool as _route_pool
 from test_dubins import TOL, fixture, spec_curve
 
 pytestmark = pytest.mark.gpu
@@ -307,25 +308,11 @@ def test_curve_lines_error_paths(torch):
 
 
 # ---- curves as routes ------------------------------------------------------------------------------------------------------------
-N_ENV, A, CAP = 8, 4, 96
+CAP = 96
 
 
-def _route_pool(x, y, heading, speed):
-    from tactics2d_amd.participant import VEHICLE_TEMPLATE, full_type_table
-    from tactics2d_amd.pool import ParticipantPool
-    rows, names = full_type_table()
-    ty = names.index(list(VEHICLE_TEMPLATE)[0] + ":kin")
-    pool = ParticipantPool(N_ENV, A)
-    pool.set_param_table(rows)
-    pool.set_status_config(max_step=100000)
-    pool.reset(x, y, heading, speed, np.full(N_ENV * A, ty, np.uint8))
-    return pool
-
-
-def _placeholder(e):
-    """96 vertices on a line that lies nowhere near the curves"""
-    t = np.linspace(0.0, 95.0, CAP, dtype=np.float32)
-    return np.stack([200.0 + t, 300.0 + 10.0 * e + 0.0 * t], 1).astype(np.float32)
+def _placeholder(e, cap=CAP):
+    return placeholder(cap, e, 200.0)
 
 
 def _consumers(torch, pool):
@@ -468,6 +455,51 @@ def test_curve_routes_error_paths(torch):
             off += 4
     pool.clear_routes()
     assert state_error() == _ffi.ERR_STATE
+    pool.close()
+
+
+def test_curve_routes_into_a_route_wider_than_the_workgroup(torch):
+    """A route of 300 vertices takes the 256 lanes of a curve's workgroup a second round: straight words whose points end in the
+    first round (201: the padding crosses the round's boundary), in the second (280), on the capacity (300) and past it (401),
+    a word of 0 segments and three Dubins paths.  The straights run along the diagonal from (-53, -53), so every vertex stays
+    below 64 m and the tolerance is the one fp32 ulp of the module's docstring."""
+    from tactics2d_amd.interpolator import Dubins, pack_words
+    n_env, cap, radius, step = 8, 300, 4.0, 0.5
+    lengths, points = (100.1, 139.9, 149.9, 200.1), (201, 280, 300, 401)
+    rng = np.random.default_rng(7)
+    start = np.concatenate([rng.uniform(-10, 10, (n_env, 2)), rng.uniform(-3, 3, (n_env, 1))], 1)
+    goal = np.concatenate([start[:, :2] + rng.uniform(-12, 12, (n_env, 2)), rng.uniform(-3, 3, (n_env, 1))], 1)
+    start[:4] = [-53.0, -53.0, np.pi / 4]
+    path = Dubins(radius, "standard").get_path(start[:, :2], start[:, 2], goal[:, :2], goal[:, 2])
+    seg, letters, n_seg = path.segments.cpu().numpy().copy(), path.steer.cpu().numpy().copy(), path.n_seg.cpu().numpy().copy()
+    for e, length in enumerate(lengths):                          # envs 0 .. 3: one straight segment
+        seg[e], letters[e], n_seg[e] = [length / radius, 0.0, 0.0], 0, 1
+    n_seg[4] = 0                                                  # env 4: a word of 0 segments; envs 5 .. 7: Dubins paths
+    pad = np.zeros((n_env, 2))
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dt), device="cuda")
+    words = pack_words(t(np.concatenate([seg, pad], 1), np.float64), t(np.concatenate([letters, pad], 1), np.int8), t(n_seg, np.int32))
+    z = np.zeros(n_env, np.float32)
+    pool = _route_pool(z, z, z, z, n_env, 1)
+    pool.set_routes([[_placeholder(e, cap)] for e in range(n_env)], np.arange(n_env), 0, 1.5)
+    before = pool.route_vertices().cpu().numpy().copy().reshape(n_env, cap, 2)
+    count = pool.curve_routes(words, t(start, np.float64), radius, step, "dubins", 0)
+    pool.sync()
+    count = count.cpu().numpy()
+    verts = pool.route_vertices().cpu().numpy().reshape(n_env, cap, 2)
+    want = np.zeros_like(verts)
+    for e in range(n_env):
+        word = (seg[e, :n_seg[e]], letters[e, :n_seg[e]], start[e], radius, step, CR.DUBINS)
+        xy, _, end, _ = CR.curve_line(*word)
+        assert n_seg[e] == 0 or CR.stable_count(*word), e
+        assert count[e] == len(xy), e
+        want[e] = CR.route_vertices(xy, end, cap, before[e])
+    assert tuple(count[:4]) == points and count[4] == 0 and ((count[5:] > 0) & (count[5:] < cap)).all()
+    assert np.abs(np.delete(want, 4, 0)).max() < 64.0
+    assert np.array_equal(verts[4], before[4])                    # the 0-segment word's route is unchanged, bit for bit
+    bit_equal, total = int((verts == want).sum()), verts.size
+    print("vertices bit-equal to the fp32 rounding of the specification:", bit_equal, "of", total,
+          "largest difference", np.abs(verts.astype(np.float64) - want).max())
+    assert np.abs(verts.astype(np.float64) - want.astype(np.float64)).max() <= ULP32 and bit_equal >= 0.99 * total
     pool.close()
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import road_ref as R
+from route_writers import A, N_ENV, off_route as _off_route, placeholder as _placeholder, route_pool as _route_pool
 from test_dubins import TOL
 from test_road import fresnel_grid, largest_error, mp_fresnel
 
@@ -443,52 +444,29 @@ def test_the_classes_on_a_side_stream_and_with_their_defaults(torch):
 
 
 # ---- roads as routes ----------------------------------------------------------------------------------------------------------------
-N_ENV, A = 8, 4
-
-
-def _route_pool(x, y, heading, speed):
-    from tactics2d_amd.participant import VEHICLE_TEMPLATE, full_type_table
-    from tactics2d_amd.pool import ParticipantPool
-    rows, names = full_type_table()
-    ty = names.index(list(VEHICLE_TEMPLATE)[0] + ":kin")
-    pool = ParticipantPool(N_ENV, A)
-    pool.set_param_table(rows)
-    pool.set_status_config(max_step=100000)
-    pool.reset(x, y, heading, speed, np.full(N_ENV * A, ty, np.uint8))
-    return pool
-
-
-def _placeholder(cap, e):
-    t = np.linspace(0.0, 95.0, cap, dtype=np.float32)
-    return np.stack([500.0 + t, 300.0 + 10.0 * e + 0.0 * t], 1).astype(np.float32)
-
-
-def _off_route(pool):
-    dist, _ = pool.off_route_host()
-    return dist.copy(), pool.off_route_all()[1].copy()
-
-
-@pytest.mark.parametrize("stride", [7, 1])
-def test_planview_routes_against_the_specification_and_a_twin_pool(torch, stride):
+def _routes_against_the_specification_and_a_twin_pool(torch, stride, n_env, no_line, make_caps):
+    """one road per env of a pool of n_env envs; env `no_line` (None: no env) has a road without a line; make_caps(counts) gives
+    the route capacities from the vertex counts of the lines"""
     from tactics2d_amd import layout as L
     rng = np.random.default_rng(41)
-    roads = [_chain(rng, [R.LINE, R.SPIRAL, R.ARC, R.POLY3][:1 + e % 4] + [R.LINE], rng.uniform(5.03, 7.97, 5).tolist(), R.STANDARD) for e in range(N_ENV)]
+    roads = [_chain(rng, [R.LINE, R.SPIRAL, R.ARC, R.POLY3][:1 + e % 4] + [R.LINE], rng.uniform(5.03, 7.97, 5).tolist(), R.STANDARD) for e in range(n_env)]
     for r in roads:                                          # near the origin, where the cars are
         dx, dy = r[0]["x"], r[0]["y"]
         for g in r:
             g["x"], g["y"] = g["x"] - dx, g["y"] - dy
-    roads[5] = [dict(kind=R.SPIRAL, s=0.0, x=0.0, y=0.0, hdg=0.0, length=1.5, curvStart=0.0, curvEnd=0.01, pRange=0)]   # one kept point: no line
+    if no_line is not None:
+        roads[no_line] = [dict(kind=R.SPIRAL, s=0.0, x=0.0, y=0.0, hdg=0.0, length=1.5, curvStart=0.0, curvEnd=0.01, pRange=0)]   # one kept point: no line
     assert _stable(roads, R.STANDARD)
     lines = [R.planview(r, R.STANDARD) for r in roads]
     counts = [R.route_vertices(l["xy"], stride, 1 << 20)[1] for l in lines]
-    assert counts[5] == 0 and min(c for e, c in enumerate(counts) if e != 5) > 12
-    caps = [counts[0] - 5, counts[1], counts[2] + 9, counts[3] + 70, 2, 33, counts[6] - 1, counts[7] + 1]     # below, equal, above
+    assert (no_line is None or counts[no_line] == 0) and min(c for e, c in enumerate(counts) if e != no_line) > 12
+    caps = make_caps(counts)
     rec, n_geom = _records(roads, 5)
-    x = np.repeat(np.linspace(0.0, 9.0, A)[None], N_ENV, 0).astype(np.float32).ravel()
-    y = rng.uniform(-5.0, 5.0, N_ENV * A).astype(np.float32)
-    z = np.zeros(N_ENV * A, np.float32)
-    pool = _route_pool(x, y, z, z)
-    pool.set_routes([[_placeholder(caps[e], e)] for e in range(N_ENV)], np.arange(N_ENV), 0, 1.5)
+    x = np.repeat(np.linspace(0.0, 9.0, A)[None], n_env, 0).astype(np.float32).ravel()
+    y = rng.uniform(-5.0, 5.0, n_env * A).astype(np.float32)
+    z = np.zeros(n_env * A, np.float32)
+    pool = _route_pool(x, y, z, z, n_env)
+    pool.set_routes([[_placeholder(caps[e], e)] for e in range(n_env)], np.arange(n_env), 0, 1.5)
     before = pool.route_vertices().cpu().numpy().copy()
     pool.profile_enable(True)
     count = pool.planview_routes(torch.as_tensor(rec), torch.as_tensor(n_geom), stride=stride, route=0, rule="standard")
@@ -499,10 +477,10 @@ def test_planview_routes_against_the_specification_and_a_twin_pool(torch, stride
     verts = pool.route_vertices().cpu().numpy()
     off = np.concatenate([[0], np.cumsum(caps)])
     equal = total = 0
-    for e in range(N_ENV):
+    for e in range(n_env):
         got = verts[off[e]:off[e + 1]]
         want, c = R.route_vertices(lines[e]["xy"], stride, caps[e])
-        if e == 5:
+        if e == no_line:
             assert want is None and np.array_equal(got, before[off[e]:off[e + 1]])                  # untouched, bit for bit
             continue
         equal, total = equal + int((got == want).sum()), total + got.size
@@ -512,15 +490,29 @@ def test_planview_routes_against_the_specification_and_a_twin_pool(torch, stride
             assert np.array_equal(got, lines[e]["xy"][::stride][:caps[e]].astype(np.float32)), e
     on_stride = sum(1 for l in lines if l["count"] and (l["count"] - 1) % stride == 0)
     print(f"stride {stride}: plan-view route vertices bit-equal to the fp32 rounding of the specification: {equal} of {total}; "
-          f"{on_stride} of 7 lines end on the stride")
+          f"{on_stride} of {sum(1 for c in counts if c)} lines end on the stride")
     assert equal == total
     got = _off_route(pool)
-    twin = _route_pool(x, y, z, z)
-    twin.set_routes([[verts[off[e]:off[e + 1]]] for e in range(N_ENV)], np.arange(N_ENV), 0, 1.5)
+    twin = _route_pool(x, y, z, z, n_env)
+    twin.set_routes([[verts[off[e]:off[e + 1]]] for e in range(n_env)], np.arange(n_env), 0, 1.5)
     ref = _off_route(twin)
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and np.isfinite(got[0]).all()
     pool.close()
     twin.close()
+
+
+@pytest.mark.parametrize("stride", [7, 1])
+def test_planview_routes_against_the_specification_and_a_twin_pool(torch, stride):
+    _routes_against_the_specification_and_a_twin_pool(torch, stride, N_ENV, 5, lambda c: [c[0] - 5, c[1], c[2] + 9, c[3] + 70, 2, 33, c[6] - 1, c[7] + 1])     # below, equal, above
+
+
+@pytest.mark.parametrize("no_line", [None, 4], ids=["env4_alone", "no_writer"])
+def test_planview_routes_of_a_pool_that_ends_inside_a_workgroup(torch, no_line):
+    """5 envs, four roads to a workgroup: env 4 is the only live wave of the last workgroup (a route longer than its line: the head,
+    the last kept point and the padding are all its own stores); without a line in env 4 that workgroup has no writer at all.
+    The capacities are those of the 8-env test's envs 0 .. 3, and its env 7's or (no line) env 5's for env 4."""
+    _routes_against_the_specification_and_a_twin_pool(torch, 7, 5, no_line,
+                                                      lambda c: [c[0] - 5, c[1], c[2] + 9, c[3] + 70, 33 if no_line == 4 else c[4] + 1])
 
 
 def test_planview_routes_error_paths(torch):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import spline_ref as S
+from route_writers import A, N_ENV, off_route as _off_route, placeholder, route_pool as _route_pool
 from test_dubins import TOL
 from test_splines import fixture, fixture_curve
 
@@ -303,53 +304,33 @@ def test_the_classes_on_a_side_stream_and_with_their_defaults(torch):
 
 
 # ---- curves as routes --------------------------------------------------------------------------------------------------------------
-N_ENV, A = 8, 4
 CAPS = (40, 61, 61, 90, 61, 61, 33, 120)     # route capacities below, equal to and above the 61 points of a curve
 
 
-def _route_pool(x, y, heading, speed):
-    from tactics2d_amd.participant import VEHICLE_TEMPLATE, full_type_table
-    from tactics2d_amd.pool import ParticipantPool
-    rows, names = full_type_table()
-    ty = names.index(list(VEHICLE_TEMPLATE)[0] + ":kin")
-    pool = ParticipantPool(N_ENV, A)
-    pool.set_param_table(rows)
-    pool.set_status_config(max_step=100000)
-    pool.reset(x, y, heading, speed, np.full(N_ENV * A, ty, np.uint8))
-    return pool
-
-
-def _placeholder(e):
-    t = np.linspace(0.0, 95.0, CAPS[e], dtype=np.float32)
-    return np.stack([500.0 + t, 300.0 + 10.0 * e + 0.0 * t], 1).astype(np.float32)
-
-
-def _off_route(pool):
-    dist, _ = pool.off_route_host()
-    return dist.copy(), pool.off_route_all()[1].copy()
-
-
-@pytest.mark.parametrize("kind", [S.BEZIER, S.BSPLINE, S.CUBIC], ids=["bezier", "bspline", "cubic"])
-def test_spline_routes_against_the_specification_and_a_twin_pool(torch, kind):
+def _routes_against_the_specification_and_a_twin_pool(kind, caps, no_curve):
+    """one curve per env of a pool of len(caps) envs into routes of these capacities; env `no_curve` (None: no env) has no curve"""
     from tactics2d_amd import layout as L
+    n_env = len(caps)
     rng = np.random.default_rng(40 + kind)
     m = 5
     ni = 15 if kind == S.CUBIC else 61                                    # 61 points per curve either way
-    rows, ctrl, n_ctrl = _fresh(rng, kind, N_ENV, m, m)
+    rows, ctrl, n_ctrl = _fresh(rng, kind, n_env, m, m)
     for r in rows:                                                        # roads of some tens of metres near the origin
         r[:, 0] = np.linspace(-20.0, 20.0, m) + rng.uniform(-2.0, 2.0, m)
         r[:, 1] = rng.uniform(-6.0, 6.0, m)
     ctrl = np.stack(rows)
-    n_ctrl = np.full(N_ENV, m, np.int32)
-    n_ctrl[5] = 1 if kind != S.BSPLINE else 2                             # env 5: no curve
-    kw = dict(n_interpolation=ni, degree=3, boundary_type=S.CLAMPED, first_derivatives=np.tile([0.3, -0.2], (N_ENV, 1)))
-    want_xy = [None if e == 5 else S.curve(kind, rows[e], ni, 3, None, S.CLAMPED, (0.3, -0.2)) for e in range(N_ENV)]
-    x = np.repeat(np.linspace(-15.0, 15.0, A)[None], N_ENV, 0).astype(np.float32).ravel()
-    y = rng.uniform(-5.0, 5.0, N_ENV * A).astype(np.float32)
-    z = np.zeros(N_ENV * A, np.float32)
-    sets = [[_placeholder(e)] for e in range(N_ENV)]
-    pool = _route_pool(x, y, z, z)
-    pool.set_routes(sets, np.arange(N_ENV), 0, 1.5)
+    n_ctrl = np.full(n_env, m, np.int32)
+    if no_curve is not None:
+        n_ctrl[no_curve] = 1 if kind != S.BSPLINE else 2
+    live = [e for e in range(n_env) if e != no_curve]
+    kw = dict(n_interpolation=ni, degree=3, boundary_type=S.CLAMPED, first_derivatives=np.tile([0.3, -0.2], (n_env, 1)))
+    want_xy = [None if e == no_curve else S.curve(kind, rows[e], ni, 3, None, S.CLAMPED, (0.3, -0.2)) for e in range(n_env)]
+    x = np.repeat(np.linspace(-15.0, 15.0, A)[None], n_env, 0).astype(np.float32).ravel()
+    y = rng.uniform(-5.0, 5.0, n_env * A).astype(np.float32)
+    z = np.zeros(n_env * A, np.float32)
+    sets = [[placeholder(caps[e], e)] for e in range(n_env)]
+    pool = _route_pool(x, y, z, z, n_env)
+    pool.set_routes(sets, np.arange(n_env), 0, 1.5)
     before = pool.route_vertices().cpu().numpy().copy()
     pool.profile_enable(True)
     count = pool.spline_routes(kind, ctrl, n_ctrl, route=0, **kw)
@@ -358,30 +339,43 @@ def test_spline_routes_against_the_specification_and_a_twin_pool(torch, kind):
     pool.profile_enable(False)
     count = count.cpu().numpy()
     verts = pool.route_vertices().cpu().numpy()
-    off = np.concatenate([[0], np.cumsum(CAPS)])
+    off = np.concatenate([[0], np.cumsum(caps)])
     equal = total = 0
-    for e in range(N_ENV):
+    for e in range(n_env):
         got = verts[off[e]:off[e + 1]]
-        if e == 5:
+        if e == no_curve:
             assert count[e] == 0 and np.array_equal(got, before[off[e]:off[e + 1]])         # untouched, bit for bit
             continue
         assert count[e] == 61, e
-        want = S.route_vertices(want_xy[e], CAPS[e])
+        want = S.route_vertices(want_xy[e], caps[e])
         equal, total = equal + int((got == want).sum()), total + got.size
         assert np.abs(got.astype(np.float64) - want).max() <= 2.0 ** -18, e               # one fp32 ulp below 32 m
-        if CAPS[e] > 61:                                                                  # the padding rule: the last written point
+        if caps[e] > 61:                                                                  # the padding rule: the last written point
             assert (got[61:] == got[60]).all(), e
     print(f"{NAMES[kind]}: route vertices bit-equal to the fp32 rounding of the specification: {equal} of {total}")
     assert equal == total
     got = _off_route(pool)
-    twin = _route_pool(x, y, z, z)
-    twin.set_routes([[verts[off[e]:off[e + 1]]] for e in range(N_ENV)], np.arange(N_ENV), 0, 1.5)
+    twin = _route_pool(x, y, z, z, n_env)
+    twin.set_routes([[verts[off[e]:off[e + 1]]] for e in range(n_env)], np.arange(n_env), 0, 1.5)
     ref = _off_route(twin)
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    d = got[0].reshape(N_ENV, A)
-    assert np.isfinite(d).all() and (d[[0, 1, 2, 3, 4, 6, 7]] < 30.0).all() and (d[5] > 100.0).all()
+    d = got[0].reshape(n_env, A)
+    assert np.isfinite(d).all() and (d[live] < 30.0).all() and (no_curve is None or (d[no_curve] > 100.0).all())
     pool.close()
     twin.close()
+
+
+@pytest.mark.parametrize("kind", [S.BEZIER, S.BSPLINE, S.CUBIC], ids=["bezier", "bspline", "cubic"])
+def test_spline_routes_against_the_specification_and_a_twin_pool(torch, kind):
+    _routes_against_the_specification_and_a_twin_pool(kind, CAPS, 5)
+
+
+@pytest.mark.parametrize("no_curve", [None, 4], ids=["env4_alone", "no_writer"])
+@pytest.mark.parametrize("kind", [S.BEZIER, S.BSPLINE, S.CUBIC], ids=["bezier", "bspline", "cubic"])
+def test_spline_routes_of_a_pool_that_ends_inside_a_workgroup(torch, kind, no_curve):
+    """5 envs, four curves to a workgroup: env 4 is the only live wave of the last workgroup, whose three idle waves keep the
+    barriers; without a curve in env 4 that workgroup has no writer at all"""
+    _routes_against_the_specification_and_a_twin_pool(kind, (40, 61, 90, 33, 120), no_curve)
 
 
 def test_spline_routes_error_paths(torch):
@@ -396,9 +390,9 @@ def test_spline_routes_error_paths(torch):
         return lib.t2d_spline_routes(h, kind, c, nc, m, ni, degree, None, boundary, None, route, None, None)
 
     assert code() == _ffi.ERR_STATE                                                   # no routes installed
-    pool.set_routes([[_placeholder(0)]], None, 0, 1.0)                                # one set shared by every env
+    pool.set_routes([[placeholder(CAPS[0], 0)]], None, 0, 1.0)                        # one set shared by every env
     assert code() == _ffi.ERR_STATE
-    sets = [[_placeholder(e)] + ([_placeholder(e)[:4]] if e != 3 else []) for e in range(N_ENV)]
+    sets = [[placeholder(CAPS[e], e)] + ([placeholder(CAPS[e], e)[:4]] if e != 3 else []) for e in range(N_ENV)]
     pool.set_routes(sets, np.arange(N_ENV), 0, 1.0)
     before = pool.route_vertices().cpu().numpy().copy()
     assert code(route=1) == _ffi.ERR_STATE and code(route=2) == _ffi.ERR_STATE        # env 3's set has no route 1
