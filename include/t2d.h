@@ -50,6 +50,7 @@
  *   t2d_spline_curves /   <- Bezier.get_curve / BSpline.get_curve / CubicSpline.get_curve  interpolator/bezier.py, b_spline.py,
  *   t2d_spline_routes        cubic_spline.py over interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp
  *   t2d_grid_dijkstra     <- Dijkstra.plan / plan_graph  search/dijkstra.py:24-394 over grid_to_csr  search/graph_utils.py:10-150
+ *   t2d_hybrid_astar      <- HybridAStar.plan  search/hybrid_a_star.py:58-172 with create_grid_collision_checker  tests/test_search.py:128-191
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -1196,6 +1197,59 @@ int t2d_grid_dijkstra(int32_t device_id, int32_t n, const double* weight_dev, co
                       const int32_t* target_dev, int32_t max_cells, int32_t connectivity, double diagonal_cost_multiplier,
                       int32_t max_path, double* g_dev, int32_t* path_dev, int32_t* path_len_dev, int32_t* status_dev,
                       int32_t* sweeps_dev, void* hip_stream);
+
+/* Hybrid A* on the device -- search/hybrid_a_star.py: HybridAStar.plan (:58-172) for n independent queries in ONE launch,
+ * asynchronous on hip_stream, no pool (tests/hybrid_astar_ref.py).  One wave runs one query: the pops are the
+ * reference's (the smallest (f, node index) of the open entries, every pop expands, no closed set), the primitives are taken in
+ * the order of `delta`, the prune against the cost grid is sequential (an earlier primitive of the same expansion wins its cell).
+ *   weight_dev   f64 [n][max_cells], hw_dev i32 [n][2]: the obstacle grids in t2d_grid_dijkstra's layout; a cell that is +inf or
+ *                NaN is an obstacle: the CLOSED square of side cell_size centred at origin + (col, row) * cell_size.  A segment
+ *                collides when the slab test of the reference's own checker (tests/test_search.py: create_grid_collision_checker,
+ *                its 1e-9 degenerate-axis branches, its divisions and its t_min <= t_max) passes for an obstacle; it is evaluated
+ *                over the cells whose centre lies in the segment's bounding box grown by 1.5 cells, which gives the full loop's answer.
+ *   start_dev / target_dev f64 [n][3]: x, y, heading; boundary_dev f64 [n][4]: x_min, x_max, y_min, y_max
+ *   delta_dev    f64 [n_steer]: tan(steer) / wheelbase * step_size per steering angle, computed by the CALLER with its libm (tan
+ *                never runs on the device); n_steer 1 .. T2D_HYBRID_MAX_STEER
+ *   step_size    xy_res = step_size * 0.5, heading_res = pi / 8 (16 heading cells), x_cells = int((x_max - x_min) / xy_res) + 1;
+ *                state_to_grid truncates, its heading is heading mod 2 pi as Python computes it, its index clamped to 15
+ *   max_iter     pops before T2D_HYBRID_MAX_ITER; max_nodes: the nodes a query may append (its share of the workspace)
+ *   workspace_dev, workspace_bytes: at least t2d_hybrid_astar_workspace_bytes(n, max_nodes) bytes, 16-byte aligned, contents
+ *                irrelevant before and after: per query the nodes (40 bytes each) and the cost grid (1 MiB)
+ *   path_dev     f64 [n][max_path][3]: the states from start to goal, NaN past the end (all NaN without a path); headings are NOT
+ *                reduced to [0, 2 pi) -- neither are the reference's; path_len_dev i32 [n]: the FULL length (0 without a path)
+ *   status_dev   i32 [n]: T2D_HYBRID_*; iterations_dev i32 [n]: the pops; nodes_dev i32 [n]: the nodes appended, the start included
+ * cos / sin are the deterministic sincos of this library (the reference's libm differs in the last bit of some results): the
+ * kernel equals tests/hybrid_astar_ref.py bit for bit, and that equals the reference on its recorded fixture.
+ * The goal test is the reference's: |x - tx| < xy_res, |y - ty| < xy_res, |heading - t_heading| < heading_res, strict, on the
+ * UNNORMALISED heading (a state that has turned through a full circle is not at the goal).  The start is neither
+ * collision-checked nor bounds-checked, as there.  velocity is unused there and absent here.
+ * BUILD-DEFINED, per row, touching only that row: T2D_HYBRID_INVALID where a pose, the boundary or a delta is not finite (x, y and
+ * the boundary above 1e150, a heading or a delta above 1e9 in magnitude count as not finite), where x_min >= x_max or
+ * y_min >= y_max, where the start's state_to_grid cell lies outside the cost grid (the reference raises IndexError or wraps a
+ * negative index), where H or W is not positive or H * W is above max_cells.  T2D_HYBRID_OVERFLOW -- no path reported, never a
+ * wrong one -- where an expansion would need more than max_nodes nodes, more than T2D_HYBRID_MAX_OPEN open entries (LDS), a depth
+ * of 65535 (the cost grid holds a node's depth in 16 bits: g is the running sum of `depth` copies of step_size, strictly
+ * increasing, so the comparison of depths is the comparison of costs), or where x_cells * y_cells is above
+ * T2D_HYBRID_MAX_XY_CELLS.  T2D_HYBRID_TRUNCATED: the path is longer than max_path, its first max_path states are written.
+ * T2D_ERR_INVALID, nothing launched: n < 0, max_cells < 1, max_path < 0, max_nodes < 1, n_steer outside 1 .. 16, step_size or
+ * cell_size not in 1e-150 .. 1e150 (so <= 0, NaN and inf), an origin that is not finite, a null or misaligned pointer (path_dev
+ * may be NULL when max_path is 0), a workspace smaller than t2d_hybrid_astar_workspace_bytes (which returns -1 for n < 0 or
+ * max_nodes < 1).                                                                                                             */
+#define T2D_HYBRID_FOUND 0
+#define T2D_HYBRID_NO_PATH 1
+#define T2D_HYBRID_MAX_ITER 2
+#define T2D_HYBRID_TRUNCATED 3
+#define T2D_HYBRID_OVERFLOW 4
+#define T2D_HYBRID_INVALID 5
+#define T2D_HYBRID_MAX_OPEN 2048
+#define T2D_HYBRID_MAX_XY_CELLS 32768
+#define T2D_HYBRID_MAX_STEER 16
+int64_t t2d_hybrid_astar_workspace_bytes(int32_t n, int32_t max_nodes);
+int t2d_hybrid_astar(int32_t device_id, int32_t n, const double* weight_dev, const int32_t* hw_dev, int32_t max_cells,
+                     const double* start_dev, const double* target_dev, const double* boundary_dev, const double* delta_dev,
+                     int32_t n_steer, double step_size, double cell_size, double origin_x, double origin_y, int32_t max_iter,
+                     int32_t max_nodes, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
+                     int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream);
 
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes

@@ -89,6 +89,12 @@ PROFILE_PLANVIEW_ROUTES = 19
 # Grid shortest paths (t2d_grid_dijkstra): the status of a row, the cap on the cells of one grid (two fp64 planes in LDS)
 GRID_FOUND, GRID_NO_PATH, GRID_TRUNCATED, GRID_INVALID, GRID_FIELD_ONLY = range(5)
 GRID_MAX_CELLS = 4096
+# Hybrid A* (t2d_hybrid_astar): the status of a row; the caps of one query: open entries (LDS), x_cells * y_cells of its cost grid
+# (16 headings of 2 bytes each in the workspace), steering angles
+HYBRID_FOUND, HYBRID_NO_PATH, HYBRID_MAX_ITER, HYBRID_TRUNCATED, HYBRID_OVERFLOW, HYBRID_INVALID = range(6)
+HYBRID_MAX_OPEN = 2048
+HYBRID_MAX_XY_CELLS = 32768
+HYBRID_MAX_STEER = 16
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),

@@ -7,7 +7,17 @@
 
 The device takes the GRID: `grid_to_csr` is not rebuilt, its edge weights are evaluated in flight.  The field equals the
 reference's g_score bit for bit and the path is the reference's path (an edge of weight exactly 0 is no edge there and here).
-A* (`a_star.py`), D*, the sampling planners and hybrid A* are not part of this package.  There is no CPU fallback.
+
+Hybrid A* on the device: the reference's `tactics2d.search.HybridAStar.plan` for n queries in ONE launch of t2d_hybrid_astar
+(DESIGN.md 4.22), with the grid collision checker the reference's tests pair with it fixed in the kernel:
+
+    out = HybridAStar.plan_batch(starts, targets, boundaries, weight_grids)     # out.path, out.path_len, out.status, ...: device tensors
+    states = HybridAStar.plan(start, target, boundary, weight_grid, grid_collide)   # one query with the reference's signature
+
+The obstacles are the +inf / NaN cells of the SAME weight grids `cost_to_go` takes.  The kernel equals tests/hybrid_astar_ref.py bit
+for bit; that specification equals the reference on its recorded fixture (cos / sin are this library's deterministic ones).
+
+A* (`a_star.py`, Dijkstra's cost), D* and the sampling planners are not part of this package.  There is no CPU fallback.
 """
 import math
 
@@ -177,3 +187,166 @@ def world_path(cells, width, boundary, grid_resolution):
     path[:, 0] = path[:, 0] * grid_resolution + boundary[0]
     path[:, 1] = path[:, 1] * grid_resolution + boundary[2]
     return path
+
+
+# ---- hybrid A* ---------------------------------------------------------------------------------------------------------------------
+HYBRID_FOUND, HYBRID_NO_PATH, HYBRID_MAX_ITER = L.HYBRID_FOUND, L.HYBRID_NO_PATH, L.HYBRID_MAX_ITER
+HYBRID_TRUNCATED, HYBRID_OVERFLOW, HYBRID_INVALID = L.HYBRID_TRUNCATED, L.HYBRID_OVERFLOW, L.HYBRID_INVALID
+
+
+def grid_collide(p1, p2, obstacles):
+    """The collision function HybridAStar.plan runs on the device, as a marker to pass for `collide_fn` -- and, called, the same test
+    on the host: does the segment p1 -> p2 touch the closed unit square of an obstacle cell (+inf or NaN) of the weight grid
+    `obstacles`, the cell (row, col) being centred at (x, y) = (col, row)?  It is create_grid_collision_checker of the reference's
+    tests/test_search.py over the grid instead of a list of centres."""
+    grid = np.asarray(obstacles, np.float64)
+    x1, y1 = float(p1[0]), float(p1[1])
+    x2, y2 = float(p2[0]), float(p2[1])
+    dx, dy = x2 - x1, y2 - y1
+    for row, col in zip(*np.nonzero(np.isnan(grid) | (grid == np.inf))):
+        ox_min, ox_max, oy_min, oy_max = col - 0.5, col + 0.5, row - 0.5, row + 0.5
+        if abs(dx) < 1e-9:
+            if not (ox_min <= x1 <= ox_max):
+                continue
+            tx_min, tx_max = -math.inf, math.inf
+        else:
+            tx1, tx2 = (ox_min - x1) / dx, (ox_max - x1) / dx
+            tx_min, tx_max = min(tx1, tx2), max(tx1, tx2)
+        if abs(dy) < 1e-9:
+            if not (oy_min <= y1 <= oy_max):
+                continue
+            ty_min, ty_max = -math.inf, math.inf
+        else:
+            ty1, ty2 = (oy_min - y1) / dy, (oy_max - y1) / dy
+            ty_min, ty_max = min(ty1, ty2), max(ty1, ty2)
+        if max(tx_min, ty_min, 0.0) <= min(tx_max, ty_max, 1.0):
+            return True
+    return False
+
+
+class HybridPaths:
+    """What HybridAStar.plan_batch returns: device tensors, one row per query.  path float64 [n, max_path, 3] (x, y, heading from
+    start to goal, NaN past the end; headings are not reduced to [0, 2 pi)), path_len int32 [n] (the FULL length; > max_path:
+    HYBRID_TRUNCATED; 0 without a path), status int32 [n] (HYBRID_FOUND, _NO_PATH, _MAX_ITER, _TRUNCATED, _OVERFLOW, _INVALID),
+    iterations int32 [n] (pops), nodes int32 [n]."""
+
+    def __init__(self, path, path_len, status, iterations, nodes):
+        self.path, self.path_len, self.status, self.iterations, self.nodes = path, path_len, status, iterations, nodes
+
+
+def _f64(x, dev, shape):
+    import torch
+    t = x.to(dev, torch.float64) if _is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, np.float64)).to(dev)
+    return t.reshape(shape).contiguous()
+
+
+def steer_deltas(steering_angles, wheelbase, step_size):
+    """delta_heading of each motion primitive (hybrid_a_star.py:121-122), on the host with libm's tan as the reference has it"""
+    return [math.tan(float(s)) / wheelbase * step_size for s in steering_angles]
+
+
+def hybrid_plan_batch(starts, targets, boundaries, weight_grids, hw=None, step_size=1.0, max_iter=50000, steering_angles=(-0.5, 0, 0.5),
+                      wheelbase=2.5, cell_size=1.0, origin=(0.0, 0.0), max_path=256, max_nodes=65536, device_id=0, stream=None):
+    """t2d_hybrid_astar: n hybrid A* queries in one launch, asynchronous on `stream`.  starts / targets [n, 3] (x, y, heading),
+    boundaries [n, 4] (x_min, x_max, y_min, y_max) or [4] for all rows, weight_grids [n, H_max, W_max] (or [H, W]) with hw as
+    plan_batch takes them: numpy, or float64 CUDA tensors (contiguous ones are read in place).  A cell that is +inf or NaN is an
+    obstacle: a closed square of side cell_size centred at origin + (col, row) * cell_size.  max_path: the rows of `path`;
+    max_nodes: the nodes one query may append (40 bytes each in the launch's workspace, beside 1 MiB of cost grid per query).
+    Returns HybridPaths.  ValueError: no or more than 16 steering angles, a step_size or cell_size that is not positive and
+    finite, a wheelbase of 0, shapes that disagree."""
+    import torch
+    if not _is_tensor(weight_grids):
+        weight_grids = np.asarray(weight_grids, np.float64)
+    shape = tuple(weight_grids.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1] * shape[2] < 1:
+        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
+    n, h_max, w_max = shape
+    stride = h_max * w_max
+    step_size, cell_size, wheelbase = float(step_size), float(cell_size), float(wheelbase)
+    if not (1e-150 <= step_size <= 1e150):
+        raise ValueError(f"step_size must be positive and finite, got {step_size}")
+    if not (1e-150 <= cell_size <= 1e150):
+        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    if wheelbase == 0 or wheelbase != wheelbase:
+        raise ValueError(f"wheelbase must not be 0, got {wheelbase}")
+    steering_angles = list(steering_angles)
+    if not 1 <= len(steering_angles) <= L.HYBRID_MAX_STEER:
+        raise ValueError(f"1 .. {L.HYBRID_MAX_STEER} steering angles, got {len(steering_angles)}")
+    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
+        raise ValueError(f"origin must be two finite numbers, got {origin}")
+    max_path, max_nodes, max_iter = int(max_path), int(max_nodes), int(max_iter)
+    if max_path < 0 or max_nodes < 1:
+        raise ValueError(f"max_path must not be negative and max_nodes at least 1, got {max_path} and {max_nodes}")
+    max_iter = max(min(max_iter, 2 ** 31 - 1), 0)
+    deltas = steer_deltas(steering_angles, wheelbase, step_size)
+    for what, x, cols in (("starts", starts, 3), ("targets", targets, 3)):
+        if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, cols), (cols,) if n == 1 else (n, cols)):
+            raise ValueError(f"{what} must have shape ({n}, {cols}), got {tuple(np.shape(x))}")
+    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
+        boundaries = np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
+    lib = _ffi.lib()
+    dev, st = _stream_of(device_id, stream)
+    with torch.cuda.stream(st):
+        if _is_tensor(weight_grids):
+            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
+        else:
+            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
+        hw_t = _i32(np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else hw, dev, (n, 2))
+        s_t, t_t, b_t = _f64(starts, dev, (n, 3)), _f64(targets, dev, (n, 3)), _f64(boundaries, dev, (n, 4))
+        d_t = _f64(np.float64(deltas), dev, (len(deltas),))
+        need = int(lib.t2d_hybrid_astar_workspace_bytes(n, max_nodes))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        path = torch.empty((n, max_path, 3), dtype=torch.float64, device=dev)
+        path_len, status, iterations, nodes = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+        _ffi.check(lib.t2d_hybrid_astar(device_id, n, w.data_ptr(), hw_t.data_ptr(), stride, s_t.data_ptr(), t_t.data_ptr(), b_t.data_ptr(),
+                                        d_t.data_ptr(), len(deltas), step_size, cell_size, float(origin[0]), float(origin[1]), max_iter,
+                                        max_nodes, max_path, ws.data_ptr(), need, path.data_ptr() if max_path else None,
+                                        path_len.data_ptr(), status.data_ptr(), iterations.data_ptr(), nodes.data_ptr(), st.cuda_stream),
+                   None, lib)
+    out = HybridPaths(path, path_len, status, iterations, nodes)
+    out._inputs = (w, hw_t, s_t, t_t, b_t, d_t)   # (kept alive with the result)
+    return out
+
+
+class HybridAStar:
+    """HybridAStar (search/hybrid_a_star.py) over a weight grid, with the grid collision checker of the reference's tests."""
+
+    plan_batch = staticmethod(hybrid_plan_batch)
+
+    @staticmethod
+    def plan(start, target, boundary, obstacles, collide_fn=None, step_size=1.0, max_iter=50000, steering_angles=(-0.5, 0, 0.5),
+             velocity=1.0, wheelbase=2.5, device_id=0):
+        """HybridAStar.plan (hybrid_a_star.py:27-157) with the reference's argument order and defaults.  `obstacles` is the weight
+        grid [H, W] (+inf or NaN: an obstacle cell, a unit square centred at (col, row)); `collide_fn` must be None or
+        `search.grid_collide`, the checker the device runs -- a Python callable cannot run in a kernel, so any other raises
+        TypeError.  `velocity` is unused, as in the reference.  Returns the reference's list of [x, y, heading] from start to
+        target, [] when there is no path and when max_iter stopped the search.  RuntimeError when the search outgrew the device's
+        caps (HYBRID_OVERFLOW): that is not "no path".  ValueError for a row the device calls INVALID.  Synchronous."""
+        if collide_fn is not None and collide_fn is not grid_collide:
+            raise TypeError("HybridAStar.plan runs on the device, where a Python callable cannot be called: collide_fn must be None or "
+                            "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
+                            f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+        grid = np.asarray(obstacles, np.float64)
+        if grid.ndim != 2:
+            raise ValueError(f"obstacles must be a 2D weight grid, got shape {grid.shape}")
+        max_path = 256
+        while True:
+            out = hybrid_plan_batch(np.float64([list(start)[:3]]), np.float64([list(target)[:3]]), np.float64([list(boundary)]), grid[None],
+                                    None, step_size, max_iter, steering_angles, wheelbase, max_path=max_path, max_nodes=1 << 18,
+                                    device_id=device_id)
+            status, length = int(out.status[0]), int(out.path_len[0])
+            if status != HYBRID_TRUNCATED:
+                break
+            max_path = length   # (a path longer than the first buffer: once more with its length)
+        if status == HYBRID_OVERFLOW:
+            raise RuntimeError(f"hybrid A* outgrew the device's caps after {int(out.iterations[0])} pops and {int(out.nodes[0])} nodes "
+                               f"(at most {1 << 18} nodes, {L.HYBRID_MAX_OPEN} open entries, {L.HYBRID_MAX_XY_CELLS} x-y cells): "
+                               "the search was not finished, which is not the same as no path")
+        if status == HYBRID_INVALID:
+            raise ValueError(f"start {list(start)}, target {list(target)} or boundary {list(boundary)} is not finite, the boundary is "
+                             "empty, or the start lies outside the boundary's cost grid")
+        if status != HYBRID_FOUND:
+            return []
+        return [[float(v) for v in row] for row in out.path[0, :length].cpu().numpy()]
