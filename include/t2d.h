@@ -1447,7 +1447,10 @@ int t2d_pid_buffers(t2d_pool* pool, void** records_dev, size_t* nbytes);
  *   cruise   :73-93    accel = (target_speed - speed) / kp   -- it DIVIDES by kp --;  accel = clip(accel, accel_last -
  *       accel_change_rate * delta_t, accel_last + accel_change_rate * delta_t); accel = clip(accel, min_accel, max_accel).
  *       accel_last = ego_state.accel = T2D_F_APPLIED0 of the participant, which is 0.0 after a reset (the reference's State
- *       holds None there and its arithmetic raises).
+ *       holds None there and its arithmetic raises).  A reset is every episode start: t2d_reset (the selected envs) and
+ *       t2d_restore write 0.0 into T2D_F_APPLIED0 / 1; after a step that restarts finished envs in its own launch
+ *       (t2d_set_auto_reset, regenerated scenes) the column is left as it is and the call reads 0.0 for an env whose
+ *       T2D_F_CNT_STEP is 0, until t2d_upload(T2D_F_APPLIED0) or t2d_integrate writes the column again.
  *       NOT the reference's State.accel property as it stands: that returns the NORM of the acceleration vector (accel *
  *       cos(heading), accel * sin(heading)) and is never negative, although both laws clip around it and down to min_accel < 0.
  *       Here accel_last and front.accel are the signed scalars the pool stores, and the fixture that pins the laws

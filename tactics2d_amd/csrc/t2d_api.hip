@@ -374,6 +374,7 @@ __global__ __launch_bounds__(256) void restore_kernel(PoolView pv, SnapPtrs sp, 
     pv.speed[i] = sp.f[3][i]; pv.vx[i] = sp.f[4][i]; pv.vy[i] = sp.f[5][i];
     pv.ids[i] = sp.ids[i];
     pv.flags[i] = 0;
+    pv.applied0[i] = 0.f; pv.applied1[i] = 0.f;   // nothing applied yet in the new episode (State.accel of a reset)
     if (pv.snap_omega[0]) {
         pv.omega_f[i] = pv.snap_omega[0][i];
         pv.omega_r[i] = pv.snap_omega[1][i];
@@ -876,9 +877,10 @@ int t2d_reset(t2d_pool* p, const uint8_t* env_mask, const float* x, const float*
     T2D_HIP(p, hipMemcpy(p->v.frame_ms, hframe.data(), 4 * (size_t)E, hipMemcpyHostToDevice));
     T2D_HIP(p, hipMemcpy(p->v.status, hstat.data(), 4 * (size_t)E, hipMemcpyHostToDevice));
     T2D_HIP(p, hipMemcpy(p->v.reward, hrew.data(), 4 * (size_t)E, hipMemcpyHostToDevice));
-    {  // SingleTrackDrift wheel speeds start at rest (the reference's callers pass omega = 0 for a new episode)
+    {  // SingleTrackDrift wheel speeds start at rest (the reference's callers pass omega = 0 for a new episode), and nothing
+       // has been applied yet: T2D_F_APPLIED0 / 1 are 0.0 (what the cruise / ACC law reads as accel_last)
         std::vector<float> ho(N, 0.0f);
-        for (int f : {T2D_F_OMEGA_F, T2D_F_OMEGA_R}) {
+        for (int f : {T2D_F_OMEGA_F, T2D_F_OMEGA_R, T2D_F_APPLIED0, T2D_F_APPLIED1}) {
             if (partial) {
                 T2D_HIP(p, hipMemcpy(ho.data(), p->field_ptr[f], 4 * (size_t)N, hipMemcpyDeviceToHost));
                 for (int e = 0; e < E; ++e)
@@ -1100,6 +1102,7 @@ int t2d_integrate(t2d_pool* p, int32_t interval_ms, void* hip_stream) {
             only_model = only_model == -1 || only_model == m ? m : -2;
         }
     T2D_HIP(p, t2d::launch_integrate(p->v, interval_ms, p->integrator_variant, wide, only_model, s));
+    p->applied_spans_restart = false;   // (every active participant's T2D_F_APPLIED0 is this call's)
     return record_event(p, 0, s, false);
 }
 
@@ -1112,10 +1115,15 @@ static void fill_idm(t2d::PoolView& v, t2d_pool* p) {
     v.idm_act1_own = (float*)p->field_ptr[T2D_F_ACT1];
 }
 
+// Every launch with a status epilogue goes through here (collide_impl with_status, the multi-step launches of t2d_step_n): the
+// epilogue may restart finished envs (auto-reset, regenerated scenes) and leaves T2D_F_APPLIED0 of the ended episode behind
+static void status_step_enqueued(t2d_pool* p) { p->applied_spans_restart = p->auto_reset || p->scene_regen; }
+
 // events (and status) of the poses as they are -- or, `step` = the plan of a fused one-launch step, the whole step
 static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStream_t s, const StepPlan* step = nullptr) {
     int rc;
     touch(p, s);
+    if (with_status) status_step_enqueued(p);
     const int fuse_variant = step ? p->integrator_variant : -1;
     const int kid = fuse_variant >= 0 ? 2 : 1;
     if ((rc = record_event(p, kid, s, true))) return rc;
@@ -1264,6 +1272,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
     }
     touch(p, s);
     if ((rc = prepare_interval(p, interval_ms, s))) return rc;
+    status_step_enqueued(p);
     for (int done = 0; done < n_steps && rc == T2D_OK;) {
         // one launch covers at most a ring of record slots (and a gather that still reads any of them is waited for first)
         int n = std::min(n_steps - done, (int)T2D_RECORD_RING);
@@ -1868,6 +1877,7 @@ int t2d_upload(t2d_pool* p, int32_t f, const void* host_src, size_t nbytes) {
     // an ids column written by the caller: which types are in use is no longer known -- every row of the table counts (the
     // integrator's single-model / four-per-lane instantiations are chosen from this set: t2d_integrate)
     if (f == T2D_F_IDS) p->types_used = ~0u;
+    if (f == T2D_F_APPLIED0) p->applied_spans_restart = false;   // (the caller's accel_last for t2d_pursuit_actions, as written)
     // actions uploaded into the pool's own fields are the actions from now on: a binding to caller-owned device memory
     // (t2d_bind_actions) ends here, or the kernels would keep reading the caller's stale tensors
     if (f == T2D_F_ACT0 || f == T2D_F_ACT1) {
@@ -2623,7 +2633,7 @@ int t2d_set_pursuit(t2d_pool* p, const double* ctrl_rows, int32_t n_ctrl, int32_
     f.ctrl_host.assign(ctrl_id, ctrl_id + N);
     f.any_lat = any_lat;
     f.any_last = any_last;
-    f.view = t2d::PursuitView{f.d_rows, f.d_ctrl, f.d_target, n_ctrl, any_acc};
+    f.view = t2d::PursuitView{f.d_rows, f.d_ctrl, f.d_target, n_ctrl, any_acc, 0};
     f.on = true;
     p->pursuit = std::move(f);
     return T2D_OK;
@@ -2639,6 +2649,7 @@ int t2d_pursuit_actions(t2d_pool* p, const float* act_in_dev, float* act_out_dev
     hipStream_t s = (hipStream_t)hip_stream;
     touch(p, s);
     if ((rc = record_event(p, T2D_PROFILE_PURSUIT, s, true))) return rc;
+    p->pursuit.view.episode_gate = p->applied_spans_restart ? 1 : 0;
     T2D_HIP(p, t2d::launch_pursuit(p->v, p->pursuit.view, p->route, act_in_dev, act_out_dev,
                                    record_dev ? record_dev : p->pursuit.d_rec.get(), s));
     return record_event(p, T2D_PROFILE_PURSUIT, s, false);

@@ -366,6 +366,7 @@ struct PursuitView {
     const float* target_speed;   // [N]
     int32_t n_ctrl;
     int32_t stage_xy;            // some row has lon_mode 1: the env's (x, y, speed, applied accel) go through LDS for the leader
+    int32_t episode_gate;        // a step that restarts finished envs wrote T2D_F_APPLIED0 last: an env at cnt_step 0 reads 0.0
 };
 
 // What one family of scripted action sources keeps in the pool: whether it is installed, the view its launch takes, the owners
@@ -542,6 +543,9 @@ struct t2d_pool {
     t2d::DevBuf<uint32_t> d_wgmap;   // step-launch placement (t2d_debug_set_step_placement)
     bool have_snapshot = false;
     bool auto_reset = false;
+    // A status step that may have restarted envs in its epilogue (auto-reset, regenerated scenes) wrote T2D_F_APPLIED0 last:
+    // the column of an env at cnt_step 0 is then the ended episode's.  t2d_upload of the column and t2d_integrate end it.
+    bool applied_spans_restart = false;
     // generated parking scenes (row f4): capacity-layout geometry owned by the device
     bool scene_mode = false, scene_regen = false;
     t2d::SceneView scene{};

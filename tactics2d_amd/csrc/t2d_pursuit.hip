@@ -49,7 +49,9 @@ __global__ __launch_bounds__(kScriptedBlock) void pursuit_kernel(PoolView pv, Pu
     const bool active = ln.active;
     const int i = ln.i, ctrl = ln.ctrl;
     const uint32_t ids = ln.ids;
-    const float fx = ln.x, fy = ln.y, fh = ln.heading, fv = ln.speed, fa = ln.also;
+    // an env that a step's own epilogue has just restarted still holds the ended episode's column: nothing is applied yet
+    const bool restarted = cv.episode_gate && pv.cnt_step[e] == 0;
+    const float fx = ln.x, fy = ln.y, fh = ln.heading, fv = ln.speed, fa = restarted ? 0.f : ln.also;
     const double qnan = __builtin_nan("");
     if (cv.stage_xy) {
         s_xy[a] = scripted_xy(ln);
