@@ -42,6 +42,12 @@ int t2d_debug_delay_gather(t2d_pool* pool, int32_t microseconds);
  * tests/test_gpu_forms.py drives one recipe per launch site and holds the set it sees against the list in the source file
  * (DESIGN.md 4.2c).  Not thread-safe; a static string.                                                                    */
 const char* t2d_debug_last_step_kernel(void);
+/* ... and its SHAPE: 64 = the twin of that form with envs of 64 participants, four per workgroup, compiled in (the plain step and
+ * the plain chained step of such pools take it: DESIGN.md 4.2c), 0 = the generic instantiation, which reads its shape from the
+ * launch.  t2d_debug_set_step_shape64(pool, 0) keeps a pool on the generic instantiations (1: back to the default), so that tests
+ * and measurements can hold the two against each other on one pool: same results, bit for bit (tests/test_gpu_shape64.py). */
+int t2d_debug_last_step_shape(void);
+int t2d_debug_set_step_shape64(t2d_pool* pool, int32_t on);
 
 /* ---- the closed loop (measurement / test helpers; tactics2d_amd/csrc/t2d_loop.hip) -----------------------------------------
  * The reference's callers run  action = policy(obs); obs, reward, ... = env.step(action)  (envs/parking.py:219-256 inside the

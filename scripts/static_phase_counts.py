@@ -2,14 +2,16 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math --cuda-device-only -S -g1 \
           -Rpass-analysis=kernel-resource-usage tactics2d_amd/csrc/t2d_collide.hip -o step.s 2> step.remarks
-    python scripts/static_phase_counts.py step.s [--kernel ILb1ELi1ELb0ELb1ELb0ELb0ELi0ELb0E] [--remarks step.remarks] [--json out.json] [--csrc DIR]
+    python scripts/static_phase_counts.py step.s [--kernel ILb1ELi1ELb0ELb1ELb0ELb0ELi0ELb0ELb1EE] [--remarks step.remarks] [--json out.json] [--csrc DIR]
 
 -g1 makes the assembler text carry one `.loc` per change of source position, with the chain of inlined call sites behind it
 (`; t2d_geom_dev.h:88:5 @[ t2d_collide.hip:1351:40 @[ ... ] ]`).  An instruction belongs to the innermost position of that
 chain that lies in one of the step's named functions (process_lane, compact_and_process, box_sweep, an integrator model, ...);
 when none does, to the phase of the kernel body its outermost position lies in.  The phase borders are found by text in
-the sources, not by line numbers, so the tool follows edits.  The default kernel is the chained fast instantiation
-<1, 1, 0, CHAIN> (what `bench.py` times).  Counts are STATIC (instructions in the text), not what a wave executes.
+the sources, not by line numbers, so the tool follows edits.  The default kernel is the chained fast instantiation with the
+shape of 64-wide envs compiled in, <1, 1, 0, CHAIN, 0, 0, 0, 0, W64> (what `bench.py` times; its generic twin, and the name in
+a tree from before the ninth template parameter: --kernel ...ELb0ELb0EE / ...ELb0EE).  Counts are STATIC (instructions in the
+text), not what a wave executes.
 """
 import argparse
 import collections
@@ -160,7 +162,7 @@ def resources(remarks, kernel):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm")
-    ap.add_argument("--kernel", default="collide_kernelILb1ELi1ELb0ELb1ELb0ELb0ELi0ELb0E")
+    ap.add_argument("--kernel", default="collide_kernelILb1ELi1ELb0ELb1ELb0ELb0ELi0ELb0ELb1EE")
     ap.add_argument("--remarks")
     ap.add_argument("--json")
     ap.add_argument("--csrc", default=CSRC, help="the sources the assembly was compiled from (another commit's: a copy of its csrc/)")

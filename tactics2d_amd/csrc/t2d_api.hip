@@ -1057,6 +1057,7 @@ static StepFacts step_facts(const t2d_pool* p) {
     f.chain_pipe2 = p->chain_pipe2;
     f.split_steps = p->split_steps;
     f.chain_depth = p->chain_depth;
+    f.shape64 = p->shape64;
     return f;
 }
 
@@ -1144,7 +1145,7 @@ static int collide_impl(t2d_pool* p, bool with_status, int interval_ms, hipStrea
         t2d::PoolView v = p->v;
         v.split_step = step && step->split;
         if (step && step->idm_fused) fill_idm(v, p);
-        T2D_HIP(p, t2d::launch_collide(v, p->status_cfg, with_status, interval_ms, fuse_variant, s));
+        T2D_HIP(p, t2d::launch_collide(v, p->status_cfg, with_status, interval_ms, fuse_variant, s, step && step->w64));
     }
     return record_event(p, kid, s, false);
 }
@@ -1331,7 +1332,7 @@ int t2d_step_n(t2d_pool* p, int32_t interval_ms, int32_t n_steps, int64_t act_st
         p->ckpt_armed = chain_form && (p->chain_used ? p->ckpt_armed : true);
         if ((rc = record_event(p, 7, s, true))) return rc;
         if (plan.ego) T2D_HIP(p, t2d::launch_ego_step(v, p->status_cfg, interval_ms, p->integrator_variant, s));
-        else T2D_HIP(p, t2d::launch_step_chain(v, p->status_cfg, interval_ms, p->integrator_variant, n, s));
+        else T2D_HIP(p, t2d::launch_step_chain(v, p->status_cfg, interval_ms, p->integrator_variant, n, s, plan.w64));
         if ((rc = record_event(p, 7, s, false))) return rc;
         if (chain_form) p->chain_count += (uint32_t)n;   // (only these launches move the counters)
         p->chain_used = true;
@@ -1750,6 +1751,12 @@ int t2d_gather_wait(t2d_pool* p, void* hip_stream, int32_t block_host) {
 // test hook: the next CHAIN launches of the pool break one hand-off on purpose (include/t2d.h)
 #ifdef T2D_DEBUG_HOOKS   // include/t2d_debug.h: libt2d_hip_debug.so only
 const char* t2d_debug_last_step_kernel(void) { return t2d::last_collide_form(); }
+int t2d_debug_last_step_shape(void) { return t2d::last_collide_shape(); }
+int t2d_debug_set_step_shape64(t2d_pool* p, int32_t on) {
+    if (!p) return T2D_ERR_INVALID;
+    p->shape64 = on != 0;
+    return T2D_OK;
+}
 
 // the step kernel's slot hand-out, one wave per vector of 64 counts (include/t2d_debug.h)
 int t2d_debug_wave_scan(int32_t device_id, int32_t n_waves, const int32_t* cnt_host, int32_t* off_host, int32_t* total_host) {

@@ -406,9 +406,23 @@ constexpr int kPipeSpinLimit = 1 << 17;   // polls (s_sleep 1 between them) befo
 // through the integrator waves' own LDS table, every controlled lane sweeps it for its leader and evaluates the law
 // (t2d_idm_dev.h: the kernel's own functions), its acceleration goes to the pool's action field and into the integrator; a
 // lane whose env was reset does it again on the restored positions.  Same leaders, same accelerations, same states.
-template <bool WITH_STATUS, int FUSE, bool IOU = true, bool CHAIN = false, bool LOOP = false, bool SPLIT = false, int PIPE = 0, bool IDMF = false>
+// W64 = true (the plain step and the plain chained step of pools of 64-participant envs, four envs per workgroup -- the metric
+// pool): the launch's shape is compiled in.  log2A = 6, four envs per workgroup, A = A_pad = 64 and 256 threads are constants, so
+// the hash-grid paths, the narrowed-workgroup staging, the choice between wave_sync and __syncthreads and the `agent < A` masks
+// are not in the text at all.  A wave IS an env there, and in the chained form (SENV below) its env number, `valid` and the env's
+// base index are scalar values (one v_readfirstlane): `if (valid)` is a scalar branch and a participant's address a scalar base +
+// the lane.  Measured: that is worth 0.3 % in long fragments and costs 0.3 % with one launch per step, which
+// keeps its lane values; the env's place in the workgroup's LDS tables (env_local, slot0) stays a lane value in both -- as scalars
+// they turn the box sweeps' list walks into scalar loops: 4 % slower than the generic form.  State that an earlier step of the same launch
+// stored is still read with ld_state<MULTI> (an atomic load is never selected as a scalar one: the scalar cache is not coherent
+// with those stores); every store is a vector store.  Same arithmetic, same bits as the generic form (tests/test_gpu_shape64.py
+// holds the two against each other).  plan_step decides (StepPlan::w64).
+template <bool WITH_STATUS, int FUSE, bool IOU = true, bool CHAIN = false, bool LOOP = false, bool SPLIT = false, int PIPE = 0, bool IDMF = false, bool W64 = false>
 __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAIN) ? T2D_LOOP_WAVES : T2D_COLLIDE_WAVES) void collide_kernel(PoolView pv_arg, t2d_status_config cfg_arg,
-                                                                                                                   int interval_ms, int log2A) {
+                                                                                                                   int interval_ms, int log2A_arg) {
+    static_assert(!W64 || (WITH_STATUS && FUSE >= 0 && !IOU && !LOOP && !SPLIT && !PIPE && !IDMF), "W64 = the plain step or the plain chained step");
+    const int log2A = W64 ? 6 : log2A_arg;
+    constexpr bool SENV = W64 && CHAIN;   // env, valid and the env's base index in scalar registers
     static_assert(!LOOP || (FUSE >= 0 && WITH_STATUS), "LOOP = the fused step");
     static_assert(!(CHAIN && LOOP) || (!PIPE && !SPLIT && !IDMF && !IOU), "CHAIN + LOOP = the plain chained form whose workgroups take several steps each");
     static_assert(!PIPE || (LOOP && !IOU && !SPLIT), "PIPE = a LOOP launch with integrator waves");
@@ -483,6 +497,10 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     // dropping them and fetching the same arguments again behind the next branch)
     asm volatile("" : "+s"(a_ids), "+s"(a_x), "+s"(a_y), "+s"(a_h), "+s"(a_v), "+s"(a_act0), "+s"(a_act1), "+s"(a_idm),
                       "+s"(a_params), "+s"(a_geo), "+s"(a_n_env), "+s"(a_A), "+s"(a_stride), "+s"(a_epb), "+s"(a_act_stride));
+    if constexpr (W64) {   // (the launchers refuse any other pool: launch_collide / launch_step_chain)
+        a_A = 64;
+        a_epb = 4;
+    }
     // Placement of the step launch (t2d_debug_set_step_placement): which logical workgroup -- which EPB envs -- this physical
     // workgroup steps, and by how many waves its lane -> participant map is rotated.  Results do not depend on it; the
     // hardware places workgroup b on XCD b mod 8 and its waves on fixed SIMDs, so the map decides which envs share a SIMD.
@@ -515,16 +533,17 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     const bool role_b = PIPE == 2 && (int)threadIdx.x >= (a_epb << log2A);
     const int tid = SPLIT ? (int)(threadIdx.x & 63u)
                   : PIPE == 2 ? (int)threadIdx.x - (role_b ? (a_epb << log2A) : 0)
-                          : (blockDim.x == kBlock ? (int)((threadIdx.x + 64u * (unsigned)wave_rot) & (kBlock - 1u)) : (int)threadIdx.x);
+                          : ((W64 || blockDim.x == kBlock) ? (int)((threadIdx.x + 64u * (unsigned)wave_rot) & (kBlock - 1u)) : (int)threadIdx.x);
     [[maybe_unused]] const int lane = tid & 63;   // (the step body derives its own lane coordinates: see the loop below)
     const int A_pad = 1 << log2A;
     const int EPB = a_epb;
     const int nthreads = SPLIT ? kBlock : EPB << log2A;   // (SPLIT: four waves per env whatever the record holds)
+    // (SENV: a wave is an env -- its number and whether the pool holds it are scalar values)
     const int env_local = SPLIT ? unit % EPB : tid >> log2A;   // the env's place in its geometry record
     const int agent = tid & (A_pad - 1);
-    const int env = SPLIT ? unit : wg * EPB + env_local;
+    const int env = SPLIT ? unit : SENV ? wg * EPB + __builtin_amdgcn_readfirstlane(tid >> 6) : wg * EPB + env_local;
     const bool valid = env < a_n_env && agent < a_A;
-    [[maybe_unused]] const int idx = valid ? env * a_A + agent : 0;
+    [[maybe_unused]] const int idx = SENV ? (valid ? env * 64 : 0) + agent : valid ? env * a_A + agent : 0;
     const bool use_hash_grid = log2A > 6;  // envs larger than a wave use the LDS spatial hash
     const int H = 2 * A_pad;               // buckets per env (power of two)
     [[maybe_unused]] uint32_t* const queue = s_queue[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
@@ -862,9 +881,9 @@ __global__ __launch_bounds__((1 + PIPE) * kBlock, PIPE == 2 ? 3 : (LOOP && !CHAI
     const int env_local = SPLIT ? unit % EPB : tid >> log2A;
     const int slot0 = SPLIT ? 0 : env_local << log2A;   // first LDS slot of the lane's env
     const int agent = tid & (A_pad - 1);
-    const int env = SPLIT ? unit : wg * EPB + env_local;
+    const int env = SPLIT ? unit : SENV ? wg * EPB + __builtin_amdgcn_readfirstlane(tid >> 6) : wg * EPB + env_local;
     const bool valid = env < a_n_env && agent < a_A;
-    const int idx = valid ? env * a_A + agent : 0;
+    const int idx = SENV ? (valid ? env * 64 : 0) + agent : valid ? env * a_A + agent : 0;   // (SENV: a scalar base + the lane)
     uint32_t* const queue = s_queue[SPLIT ? role : (tid >> 6) + (role_b ? kWaves : 0)];
     if constexpr (LOOP) {
         pvp = late_args();
@@ -2080,10 +2099,39 @@ const char* g_last_collide_form = "";
 #define T2D_NOTE_FORM(str) ((void)0)
 #endif
 #define T2D_UNPAREN(...) __VA_ARGS__
+// The shape of a launch site's form: the site's own template arguments, with W64 on top where the form has a W64 twin (the plain
+// step and the plain chained step) and the plan asked for it (`shape64`: StepPlan::w64).  The sites and the strings they note
+// stay one per form; which shape the last launch took is noted beside the form (t2d_debug_last_step_shape).
+namespace {
+template <bool WITH_STATUS, int FUSE, bool IOU = true, bool CHAIN = false, bool LOOP = false, bool SPLIT = false, int PIPE = 0, bool IDMF = false>
+struct CollideForm {
+    static constexpr bool has_w64 = WITH_STATUS && FUSE >= 0 && !IOU && !LOOP && !SPLIT && !PIPE && !IDMF;
+    template <bool W64>
+    static void launch(dim3 grid, dim3 block, size_t dyn, hipStream_t s, const PoolView& v, const t2d_status_config& cfg, int interval_ms, int log2A) {
+        hipLaunchKernelGGL((collide_kernel<WITH_STATUS, FUSE, IOU, CHAIN, LOOP, SPLIT, PIPE, IDMF, W64 && has_w64>), grid, block, dyn, s, v, cfg,
+                           interval_ms, log2A);
+    }
+};
+// what the W64 instantiations have compiled in: envs of 64 participants, four to a workgroup of 256 threads
+bool shape64_fits(const PoolView& v, dim3 block) { return v.A == 64 && v.geo_layout.epb == 4 && block.x == (unsigned)kBlock; }
+}  // namespace
+#ifdef T2D_DEBUG_HOOKS
+int g_last_collide_shape = 0;
+#define T2D_NOTE_SHAPE(w) (g_last_collide_shape = (w))
+#else
+#define T2D_NOTE_SHAPE(w) ((void)0)
+#endif
 #define T2D_LAUNCH_COLLIDE(ARGS, grid_, block_)                                                                              \
     do {                                                                                                                     \
         T2D_NOTE_FORM(#ARGS);                                                                                                \
-        hipLaunchKernelGGL((collide_kernel<T2D_UNPAREN ARGS>), grid_, block_, dyn, s, v, cfg, interval_ms, log2A);           \
+        if (shape64 && CollideForm<T2D_UNPAREN ARGS>::has_w64) {                                                             \
+            if (!shape64_fits(v, block_)) return hipErrorInvalidValue;                                                       \
+            T2D_NOTE_SHAPE(64);                                                                                              \
+            CollideForm<T2D_UNPAREN ARGS>::launch<true>(grid_, block_, dyn, s, v, cfg, interval_ms, log2A);                  \
+        } else {                                                                                                             \
+            T2D_NOTE_SHAPE(0);                                                                                               \
+            CollideForm<T2D_UNPAREN ARGS>::launch<false>(grid_, block_, dyn, s, v, cfg, interval_ms, log2A);                 \
+        }                                                                                                                    \
     } while (0)
 
 // resident workgroups per CU of the fused step kernel with this pool's geometry record (the metric scenes are sized
@@ -2100,7 +2148,7 @@ hipError_t step_occupancy(const PoolView& v, int* blocks_per_cu, size_t* lds_byt
 }
 
 hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, int interval_ms, int variant, int n_steps,
-                             hipStream_t s) {
+                             hipStream_t s, bool shape64) {
     const int log2A = host::log2_pad(v.A);
     const int EPB = v.geo_layout.epb;
     if (EPB <= 0 || (EPB & (EPB - 1))) return hipErrorInvalidValue;   // (the kernel stages its record in (EPB << log2A)-thread rounds counted by a SHIFT)
@@ -2170,7 +2218,7 @@ hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, in
 }
 
 hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool with_status,
-                          int interval_ms, int fuse_variant, hipStream_t s) {
+                          int interval_ms, int fuse_variant, hipStream_t s, bool shape64) {
     const int log2A = host::log2_pad(v.A);   // (at least two lanes per env)
     const int EPB = v.geo_layout.epb;
     if (EPB <= 0 || (EPB & (EPB - 1))) return hipErrorInvalidValue;   // (the kernel stages its record in (EPB << log2A)-thread rounds counted by a SHIFT)
@@ -2207,6 +2255,7 @@ hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool 
 
 #ifdef T2D_DEBUG_HOOKS
 const char* last_collide_form() { return g_last_collide_form; }
+int last_collide_shape() { return g_last_collide_shape; }
 
 // t2d_debug_wave_scan (include/t2d_debug.h; tests/test_gpu_wave_scan.py): wave_excl_scan as compact_and_process calls it -- all
 // 64 lanes of a wave, one count each -- on wave w's counts cnt[64 w ..]; out[65 w + lane] = the lane's offset, out[65 w + 64] =

@@ -582,6 +582,7 @@ struct t2d_pool {
     bool ckpt_armed = false;       // every multi-step launch since the last quiesce was a CHAIN launch with a checkpoint
     uint32_t chain_sig = 0;        // shape (workgroups, split) of the last CHAIN launch whose counters d_chain holds; 0 = none
     uint32_t chain_fault = 0;      // t2d_debug_chain_fault
+    bool shape64 = true;           // the plain forms may take their W64 twin (t2d_debug_set_step_shape64 turns it off)
     uint32_t types_used = 0;       // bit t: some active participant has type t (t2d_reset) -- or may have: every path that writes
                                    // ids on the device ORs in what it writes (t2d_restore, an armed auto-reset, t2d_parking_scenes)
     uint32_t snap_types = 0;       // bit t: some active participant of the snapshot has type t (t2d_snapshot, t2d_parking_scenes)
@@ -638,11 +639,12 @@ namespace t2d {
 hipError_t launch_integrate(const PoolView& v, int interval_ms, int variant, bool allow_wide, int only_model, hipStream_t s);
 // column T2D_P_SUBSTEPS of the device table for `interval_ms` (rows of the drift model keep their own column 23)
 hipError_t launch_derive(double* params, int n_types, int interval_ms, hipStream_t s);
+// (shape64: the plan's StepPlan::w64 -- the plain fused step takes its instantiation with the shape of 64-wide envs compiled in)
 hipError_t launch_collide(const PoolView& v, const t2d_status_config& cfg, bool with_status,
-                          int interval_ms, int fuse_variant, hipStream_t s);
+                          int interval_ms, int fuse_variant, hipStream_t s, bool shape64 = false);
 // n_steps fused steps in one launch (v.chain_* set by the caller); see PoolView::chain_done
 hipError_t launch_step_chain(const PoolView& v, const t2d_status_config& cfg, int interval_ms, int variant, int n_steps,
-                             hipStream_t s);
+                             hipStream_t s, bool shape64 = false);
 hipError_t launch_ego_step(const PoolView& v, const t2d_status_config& cfg, int interval_ms, int variant, hipStream_t s);
 hipError_t step_occupancy(const PoolView& v, int* blocks_per_cu, size_t* lds_bytes);
 hipError_t launch_lidar(const PoolView& v, const LidarView& lv, float* out, hipStream_t s);
@@ -703,6 +705,7 @@ hipError_t launch_spin(long long ticks_100mhz, hipStream_t s);
 size_t map_segment_bytes(int n_participants);   // the walk -> decisions hand-over buffer of launch_map_events
 hipError_t launch_map_events(const PoolView& v, const MapGridView& mg, void* segments, uint32_t* out, hipStream_t s);
 #ifdef T2D_DEBUG_HOOKS
+int last_collide_shape();           // 64: that launch took the W64 twin of its form (envs of 64, four per workgroup compiled in); 0: the generic one
 const char* last_collide_form();   // template arguments of the collide_kernel instantiation the last launch took (t2d_collide.hip)
 // the step kernel's wave_excl_scan on n_waves waves of 64 counts each (t2d_collide.hip): out_dev = per wave 64 offsets + the total
 hipError_t launch_wave_scan_probe(const int32_t* cnt_dev, int32_t* out_dev, int n_waves);

@@ -35,6 +35,7 @@ struct StepFacts {
     bool chain_steps, chain_loop, chain_pipe, chain_pipe2;   // t2d_set_step_chaining
     bool split_steps;        // t2d_set_split_step
     int chain_depth;         // -DT2D_EXPERIMENTS: steps per workgroup of the chained form (the product's is 1)
+    bool shape64;            // the plain forms may take their twin compiled for 64-wide envs (a pool's default; the debug library can turn it off)
 };
 
 struct StepPlan {
@@ -49,6 +50,7 @@ struct StepPlan {
     bool loop;         // the workgroups walk through the steps themselves (LOOP)
     int real_wgs;      // workgroups of the launch that own envs
     int chain_k;       // > 1: fragments are cut to multiples of it, and a plain chained launch takes that many steps per workgroup
+    bool w64;          // the launch takes the W64 twin of its form: envs of 64 participants, four per workgroup, compiled in
 };
 
 // one workgroup per CU is 64 .. 256 lanes of the general kernel, 16 envs of the single-ego kernel
@@ -126,6 +128,12 @@ inline StepPlan plan_step(const StepFacts& f, int n_steps) {
               : pl.split              ? T2D_FORM_CHAIN_SPLIT
               : pl.loop               ? T2D_FORM_LOOP
                                       : T2D_FORM_CHAIN;
+    // The shape of the launch (not a form of its own: t2d_step_form reports the same name).  The plain step and the plain chained
+    // step -- no IoU events, no controllers inside, not SPLIT / LOOP / PIPE, one step per workgroup -- have a twin with the shape of
+    // the metric pool compiled in: envs of exactly 64 participants, four of them per workgroup (a geometry record that narrows the
+    // workgroup, or envs of another width, keep the generic instantiation).
+    const bool plain = pl.form == T2D_FORM_STEP ? !f.iou && !pl.idm_fused : pl.form == T2D_FORM_CHAIN && !pl.idm_fused && pl.chain_k <= 1;
+    pl.w64 = f.shape64 && plain && f.A == 64 && f.epb == 4;
     return pl;
 }
 

@@ -9,6 +9,7 @@ libt2d_hip.so exports no t2d_debug_* symbol.
     pool(n_env, A)                    a ParticipantPool living in the debug library
     set_step_placement(pool, map)     which logical workgroup / wave rotation each physical workgroup of a step launch takes
     chain_fault(pool, kind)           break one hand-off of the chained t2d_step_n on purpose
+    set_step_shape64(pool, on)        keep the plain forms on their generic instantiations / last_step_shape() tells which ran
     delay_gather(pool, us)            hold the pool's gather stream (a slow peer)
     feedback_policy(pool, act, ...)   the stand-in policy kernel
     env_groups(scene, G) / ClosedLoop policy kernel -> t2d_step per env group, enqueued by one C call
@@ -38,6 +39,8 @@ DEBUG_SYMBOLS = {
     "t2d_debug_closed_loop_run": (C.c_int, [_vp, C.c_int32]),
     "t2d_debug_closed_loop_destroy": (C.c_int, [_vp]),
     "t2d_debug_last_step_kernel": (C.c_char_p, []),
+    "t2d_debug_last_step_shape": (C.c_int, []),
+    "t2d_debug_set_step_shape64": (C.c_int, [_vp, C.c_int32]),
     "t2d_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "t2d_debug_geom": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "t2d_debug_memory": (C.c_int, [C.POINTER(C.c_int64)]),
@@ -103,6 +106,17 @@ def memory():
 def last_step_kernel():
     """template arguments of the collide_kernel instantiation the last launch took, e.g. "(true, 1, false, true)\""""
     return lib().t2d_debug_last_step_kernel().decode()
+
+
+def last_step_shape():
+    """64: the last launch took the twin of its form compiled for envs of 64 participants, four per workgroup; 0: the generic one"""
+    return int(lib().t2d_debug_last_step_shape())
+
+
+def set_step_shape64(p, on):
+    """t2d_debug_set_step_shape64: False keeps the pool's plain step / chained step on the generic instantiations"""
+    _need(p)
+    p._ck(p._lib.t2d_debug_set_step_shape64(p._h, int(bool(on))))
 
 
 def feedback_policy(p, act_out_ptr, v_target, k_speed, k_steer, stream=None):
