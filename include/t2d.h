@@ -51,6 +51,8 @@
  *   t2d_spline_routes        cubic_spline.py over interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp
  *   t2d_grid_dijkstra     <- Dijkstra.plan / plan_graph  search/dijkstra.py:24-394 over grid_to_csr  search/graph_utils.py:10-150
  *   t2d_hybrid_astar      <- HybridAStar.plan  search/hybrid_a_star.py:58-172 with create_grid_collision_checker  tests/test_search.py:128-191
+ *   t2d_sample_plan       <- RRT.plan  search/rrt.py:74-164; RRTStar.plan / _choose_parent  search/rrt_star.py:22-201;
+ *                            RRTConnect.plan  search/rrt_connect.py:72-206, with the same collision checker
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -1161,6 +1163,21 @@ int t2d_planview_lines(int32_t device_id, int32_t n, const void* rec_dev, const 
 int t2d_planview_routes(t2d_pool* pool, const void* rec_dev, const int32_t* n_geom_dev, int32_t max_geom, int32_t rule, int32_t stride,
                         int32_t route, int32_t* count_dev, void* hip_stream);
 
+/* A polyline the caller already has on the device -- a planner's path -- as a route: the fourth writer beside t2d_curve_routes,
+ * t2d_spline_routes and t2d_planview_routes, under their rules (T2D_ERR_STATE unless route sets are the installed kind, no two envs
+ * share a set and every env's set has a route `route`; asynchronous on hip_stream).
+ *   points_dev  f64 [n_env][max_pts][cols], cols >= 2: x and y are the first two columns (t2d_hybrid_astar's path with its heading
+ *               column and t2d_sample_plan's path both go in as they are); counts_dev i32 [n_env]: a planner's path_len as it is
+ *   The used length is min(counts[e], max_pts).  Vertex k of the route is the fp32 rounding of point k; vertices past the used
+ *   length repeat the last used point; a route of fewer vertices than that takes the first `capacity` points.  A row whose count
+ *   is <= 0, or one with a coordinate among the points it would write that is not finite once rounded to fp32, leaves its route
+ *   as it is.  count_dev i32 [n_env] (may be NULL): the used length, 0 for a row left as it is.
+ * T2D_ERR_INVALID, nothing launched: a null or misaligned pointer, max_pts < 1, cols < 2, route < 0.  kernel_id
+ * T2D_PROFILE_POLYLINE_ROUTES in t2d_profile_read.                                                                              */
+enum { T2D_PROFILE_POLYLINE_ROUTES = 20 };
+int t2d_polyline_routes(t2d_pool* pool, const double* points_dev, const int32_t* counts_dev, int32_t max_pts, int32_t cols,
+                        int32_t route, int32_t* count_dev, void* hip_stream);
+
 /* Shortest paths over weighted obstacle grids on the device -- search/dijkstra.py (Dijkstra.plan, Dijkstra.plan_graph) over the
  * graph of search/graph_utils.py: grid_to_csr, for n independent grids in ONE launch, asynchronous on hip_stream, no pool
  * (tests/grid_search_ref.py).  One workgroup solves one grid with its weights and its field in LDS.
@@ -1250,6 +1267,65 @@ int t2d_hybrid_astar(int32_t device_id, int32_t n, const double* weight_dev, con
                      int32_t n_steer, double step_size, double cell_size, double origin_x, double origin_y, int32_t max_iter,
                      int32_t max_nodes, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
                      int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream);
+
+/* Sampling planners on the device -- search/rrt.py: RRT.plan (:74-164), search/rrt_star.py: RRTStar.plan (:88-201) with
+ * _choose_parent (:22-37), search/rrt_connect.py: RRTConnect.plan (:72-206) -- for n independent queries of ONE kind in ONE launch,
+ * asynchronous on hip_stream, no pool (tests/sample_plan_ref.py).  One wave runs one query.  Every iteration
+ * draws rx, ry, takes the tree's node nearest to them (the FIRST minimum of dx dx + dy dy), steers (the sample itself where
+ * sqrt(dx dx + dy dy) < extension_step, else nearest + extension_step * d / dist), goes on to the next iteration unless the new
+ * point lies in the closed boundary and the segment nearest -> new is free, and appends.  np.hypot and np.linalg.norm are
+ * sqrt(dx dx + dy dy) here; fp64, one rounding per operation.
+ *   T2D_SAMPLE_RRT          after an append: where sqrt(|new - target|^2) < extension_step and the segment new -> target is free,
+ *                           the target is appended and the search ends.  The path is the walk from the start to the LAST node
+ *                           appended IN EVERY CASE (rrt.py:147): when max_iter runs out it is not empty, whatever the docstring says.
+ *   T2D_SAMPLE_RRT_STAR     the parent is the smallest (cost, index) among the nodes within `radius` (d2 <= radius * radius) whose
+ *                           segment to the new point is free, taken only where its cost is STRICTLY below the nearest node's;
+ *                           every other node within the radius whose segment is free and whose cost exceeds the new node's cost
+ *                           plus the distance is given the new node as parent and that cost; its descendants KEEP their costs.
+ *                           The tree's coordinates are RRT's for the same draws.  The end and the path are RRT's.
+ *   T2D_SAMPLE_RRT_CONNECT  tree a from the start, tree b from the target; even iterations extend a, odd ones b (the draw is taken
+ *                           in both); after an append ONE segment, new -> the node of the other tree nearest to it, is tested: free,
+ *                           the path is a's walk followed by b's walk reversed.  max_iter: no path.
+ *   weight_dev, hw_dev, max_cells, cell_size, origin_x / origin_y: the obstacle grids and the collision test of t2d_hybrid_astar
+ *   start_dev / target_dev f64 [n][2]; boundary_dev f64 [n][4]: x_min, x_max, y_min, y_max
+ *   seed_dev     u64 [n]: draw k of query e is the top 53 bits of splitmix64's finaliser of seed[e] + (k + 1) * 0x9E3779B97F4A7C15
+ *                as a uniform u in [0, 1) (the stream of t2d_generate_tracks); iteration i takes rx = x_min + (x_max - x_min) * u
+ *                from draw 2 i and ry from draw 2 i + 1, whether or not it appends: np.random.uniform's formula on the build's stream
+ *   max_iter     iterations before T2D_SAMPLE_MAX_ITER; max_nodes: the nodes of a query, both trees of RRT-Connect together
+ *   workspace_dev, workspace_bytes: at least t2d_sample_plan_workspace_bytes(n, max_nodes) bytes, 16-byte aligned.  It holds the
+ *                TREES, an output: query e's row starts at e * (workspace bytes / n) and holds x, y f64 [max_nodes][2], then cost
+ *                f64 [max_nodes] (RRT* only, else not written), then parent i32 [max_nodes] (an index within the node's own tree,
+ *                -1 for a root).  Tree a's node i is entry i; RRT-Connect's tree b's node j is entry max_nodes - 1 - j.
+ *   path_dev     f64 [n][max_path][2], NaN past the end; path_len_dev i32 [n]: the FULL length
+ *   status_dev   i32 [n]: T2D_SAMPLE_*; iterations_dev i32 [n]: the loop iterations begun; nodes_dev i32 [n][2]: the nodes of tree a
+ *                and of tree b (0 for the other two kinds)
+ * The start is neither bounds- nor collision-checked, as in the reference.  callback is not modelled.
+ * BUILD-DEFINED, per row, touching only that row: T2D_SAMPLE_INVALID (no node, no path) where a coordinate of the start, the target
+ * or the boundary is not finite (above 1e150 in magnitude counts as not finite), where H or W is not positive or H * W is above
+ * max_cells.  A boundary with min > max is NOT invalid: as in the reference no new point lies in it, and the row ends with
+ * T2D_SAMPLE_MAX_ITER.  T2D_SAMPLE_OVERFLOW -- no path reported, never a wrong one -- where an append would exceed max_nodes.
+ * T2D_SAMPLE_TRUNCATED: a path was found and is longer than max_path, its first max_path points are written; the walk of a
+ * T2D_SAMPLE_MAX_ITER row is cut the same way and keeps its status (path_len > max_path tells).  The first
+ * T2D_SAMPLE_LDS_NODES nodes' coordinates are also kept in LDS (for RRT-Connect half of them per tree); nothing depends on it.
+ * T2D_ERR_INVALID, nothing launched: an unknown kind, n < 0, max_cells < 1, max_path < 0, max_nodes < 1, max_iter < 0,
+ * extension_step or cell_size not in 1e-150 .. 1e150 (so <= 0, NaN and inf), a radius that is negative or NaN, an origin that is
+ * not finite, a null or misaligned pointer (path_dev may be NULL when max_path is 0), a workspace smaller than
+ * t2d_sample_plan_workspace_bytes (which returns -1 for n < 0 or max_nodes < 1).                                               */
+#define T2D_SAMPLE_RRT 0
+#define T2D_SAMPLE_RRT_STAR 1
+#define T2D_SAMPLE_RRT_CONNECT 2
+#define T2D_SAMPLE_FOUND 0
+#define T2D_SAMPLE_MAX_ITER 1
+#define T2D_SAMPLE_TRUNCATED 2
+#define T2D_SAMPLE_OVERFLOW 3
+#define T2D_SAMPLE_INVALID 4
+#define T2D_SAMPLE_LDS_NODES 512
+int64_t t2d_sample_plan_workspace_bytes(int32_t n, int32_t max_nodes);
+int t2d_sample_plan(int32_t device_id, int32_t n, int32_t kind, const double* weight_dev, const int32_t* hw_dev, int32_t max_cells,
+                    const double* start_dev, const double* target_dev, const double* boundary_dev, const uint64_t* seed_dev,
+                    double extension_step, double radius, double cell_size, double origin_x, double origin_y, int32_t max_iter,
+                    int32_t max_nodes, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
+                    int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream);
 
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
@@ -1698,7 +1774,8 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * (t2d_tracks_regenerate), 13 = Reeds-Shepp planner (t2d_rs_plan), 14 = Reeds-Shepp path follower (t2d_rs_follow),
  * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions),
  * 17 = curve lines into the route sets (t2d_curve_routes), 18 = spline curves into the route sets (t2d_spline_routes),
- * 19 = plan-view reference lines into the route sets (t2d_planview_routes).  */
+ * 19 = plan-view reference lines into the route sets (t2d_planview_routes), 20 = a caller's polylines into the route sets
+ * (t2d_polyline_routes).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

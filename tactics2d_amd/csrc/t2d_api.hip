@@ -333,7 +333,7 @@ int record_event(t2d_pool* p, int kernel_id, hipStream_t s, bool begin) {
     return T2D_OK;
 }
 
-// What t2d_curve_routes, t2d_spline_routes and t2d_planview_routes ask after their family's own argument check, and the bracket
+// What t2d_curve_routes, t2d_spline_routes, t2d_planview_routes and t2d_polyline_routes ask after their family's own argument check, and the bracket
 // around their launch: count_dev and route are arguments, the installed route sets state (route_slot in t2d_route_write_dev.h
 // relies on it).  launch(s) is the family's launch_*_routes line under T2D_HIP, so that a launch error names the call.
 template <class Launch>
@@ -3223,6 +3223,18 @@ int t2d_planview_routes(t2d_pool* p, const void* rec_dev, const int32_t* n_geom_
     if (stride < 1) return fail(p, T2D_ERR_INVALID, "t2d_planview_routes: stride must be >= 1");
     return write_routes(p, "t2d_planview_routes", T2D_PROFILE_PLANVIEW_ROUTES, route, count_dev, hip_stream, [&](hipStream_t s) {
         T2D_HIP(p, t2d::launch_planview_routes(p->v, p->route, rec_dev, n_geom_dev, max_geom, rule, stride, route, count_dev, s));
+        return T2D_OK;
+    });
+}
+
+int t2d_polyline_routes(t2d_pool* p, const double* points_dev, const int32_t* counts_dev, int32_t max_pts, int32_t cols, int32_t route,
+                        int32_t* count_dev, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (!points_dev || !counts_dev || (reinterpret_cast<uintptr_t>(points_dev) & 7u) || (reinterpret_cast<uintptr_t>(counts_dev) & 3u))
+        return fail(p, T2D_ERR_INVALID, "t2d_polyline_routes: null or misaligned points_dev (8 bytes) / counts_dev (4 bytes)");
+    if (max_pts < 1 || cols < 2) return fail(p, T2D_ERR_INVALID, "t2d_polyline_routes: max_pts must be >= 1 and cols >= 2");
+    return write_routes(p, "t2d_polyline_routes", T2D_PROFILE_POLYLINE_ROUTES, route, count_dev, hip_stream, [&](hipStream_t s) {
+        T2D_HIP(p, t2d::launch_polyline_routes(p->v, p->route, points_dev, counts_dev, max_pts, cols, route, count_dev, s));
         return T2D_OK;
     });
 }

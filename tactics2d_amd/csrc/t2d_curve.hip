@@ -109,7 +109,37 @@ __global__ __launch_bounds__(kCurveBlock) void curve_routes_kernel(RouteView rv,
                [&](int k, double& x, double& y) { double h; curve_point(s_plan, radius, k, x, y, h); });
 }
 
+// A polyline the caller already has (a planner's path) into route `route` of env e's own set: point k of the first
+// min(counts[e], max_pts) rounded to fp32, the tail is the last of them.  A row without points, or with a coordinate among the ones
+// it would write that is not finite as fp32, leaves the route as it is (count 0).
+__global__ __launch_bounds__(kCurveBlock) void polyline_routes_kernel(RouteView rv, const double* __restrict__ points,
+                                                                      const int32_t* __restrict__ counts, int max_pts, int cols,
+                                                                      int route, int32_t* __restrict__ count) {
+    const int e = blockIdx.x;
+    const RouteSlot slot = route_slot(rv, e, route);
+    const double* p = points + (size_t)e * (size_t)max_pts * (size_t)cols;
+    const int given = counts[e], used = given < max_pts ? given : max_pts;
+    const int written = used < slot.cap ? used : slot.cap;
+    bool bad = false;
+    for (int k = threadIdx.x; k < written; k += kCurveBlock) {
+        const float x = (float)p[(size_t)k * cols], y = (float)p[(size_t)k * cols + 1];
+        bad = bad || !(__builtin_fabsf(x) < __builtin_huge_valf()) || !(__builtin_fabsf(y) < __builtin_huge_valf());
+    }
+    const bool leave = __syncthreads_or(bad) || used <= 0;
+    if (threadIdx.x == 0 && count) count[e] = leave ? 0 : used;
+    if (leave) return;
+    const double* last = p + (size_t)(used - 1) * cols;
+    route_fill(slot, threadIdx.x, kCurveBlock, used, make_float2((float)last[0], (float)last[1]),
+               [&](int k, double& x, double& y) { x = p[(size_t)k * cols]; y = p[(size_t)k * cols + 1]; });
+}
+
 }  // namespace
+
+hipError_t launch_polyline_routes(const PoolView& v, const RouteView& rv, const double* points, const int32_t* counts, int max_pts,
+                                  int cols, int route, int32_t* count, hipStream_t s) {
+    hipLaunchKernelGGL(polyline_routes_kernel, dim3(v.n_env), dim3(kCurveBlock), 0, s, rv, points, counts, max_pts, cols, route, count);
+    return hipGetLastError();
+}
 
 hipError_t launch_curve_routes(const PoolView& v, const RouteView& rv, const void* words, const double* start, double radius,
                                double step, int rule, int route, int32_t* count, hipStream_t s) {

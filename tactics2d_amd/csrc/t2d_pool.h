@@ -664,6 +664,9 @@ hipError_t launch_off_route(const PoolView& v, const RouteView& rv, float* dist,
 // curve lines into the route sets (t2d_curve.hip): curve e -> the fp32 vertices of route `route` of env e's set
 hipError_t launch_curve_routes(const PoolView& v, const RouteView& rv, const void* words, const double* start, double radius,
                                double step, int rule, int route, int32_t* count, hipStream_t s);
+// a caller's polyline per env (t2d_curve.hip): the first min(counts[e], max_pts) points [max_pts][cols] -> the same vertices
+hipError_t launch_polyline_routes(const PoolView& v, const RouteView& rv, const double* points, const int32_t* counts, int max_pts,
+                                  int cols, int route, int32_t* count, hipStream_t s);
 // spline curves (t2d_spline.hip): what is wrong with a launch's arguments (null: nothing), and curve e -> the fp32 vertices of
 // route `route` of env e's set
 const char* spline_args_error(int kind, const double* ctrl, const int32_t* n_ctrl, int max_ctrl, int n_interp, int degree,

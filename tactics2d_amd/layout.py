@@ -95,6 +95,14 @@ HYBRID_FOUND, HYBRID_NO_PATH, HYBRID_MAX_ITER, HYBRID_TRUNCATED, HYBRID_OVERFLOW
 HYBRID_MAX_OPEN = 2048
 HYBRID_MAX_XY_CELLS = 32768
 HYBRID_MAX_STEER = 16
+# Sampling planners (t2d_sample_plan): the kinds, the status of a row, the nodes whose coordinates a query keeps in LDS, the bytes
+# of one node in the workspace (x, y f64; cost f64; parent i32; a query's row is rounded up to 256 bytes); the kernel id of
+# t2d_polyline_routes
+SAMPLE_RRT, SAMPLE_RRT_STAR, SAMPLE_RRT_CONNECT = range(3)
+SAMPLE_FOUND, SAMPLE_MAX_ITER, SAMPLE_TRUNCATED, SAMPLE_OVERFLOW, SAMPLE_INVALID = range(5)
+SAMPLE_LDS_NODES = 512
+SAMPLE_NODE_BYTES = 28
+PROFILE_POLYLINE_ROUTES = 20
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),

@@ -536,7 +536,7 @@ class ParticipantPool:
 
     @contextlib.contextmanager
     def _route_writer(self, count, stream):
-        """What curve_routes / spline_routes / planview_routes start with: the pool's device, the launch stream (`stream`, or
+        """What curve_routes / spline_routes / planview_routes / polyline_routes start with: the pool's device, the launch stream (`stream`, or
         torch's current one) and the int32 [n_env] count tensor (`count` checked, or a new one), inside a torch stream context
         of the launch stream, so that uploads and conversions made in it run ahead of the launch."""
         import torch
@@ -606,6 +606,28 @@ class ParticipantPool:
         self._ck(self._lib.t2d_planview_routes(self._h, inputs[0].data_ptr(), inputs[1].data_ptr(), inputs[0].shape[1], rule, int(stride),
                                                int(route), count.data_ptr(), st))
         self._planview_inputs = inputs   # (kept alive until the launch has run)
+        return count
+
+    def polyline_routes(self, points, counts, route=0, count=None, stream=None):
+        """t2d_polyline_routes: a polyline per env that is already on the device -- a planner's path -- into route `route` of each
+        env's own route set, under the rules of curve_routes.  points: a contiguous float64 CUDA tensor [n_env, max_pts, C], C >= 2,
+        x and y first (search.SamplePaths.path and search.HybridPaths.path with its heading column go in as they are); counts: a
+        contiguous int32 CUDA tensor [n_env] (a planner's path_len as it is).  The used length is min(counts, max_pts); the vertices
+        are the fp32 roundings of the first points, vertices past the end repeat the last point, a route of fewer vertices takes
+        the first of them.  A row with counts <= 0, or with a coordinate among the points it would write that is not finite in
+        fp32, leaves the route as it is.  Needs set_routes with one set per env.  Returns the int32 CUDA tensor [n_env] of the
+        used lengths, 0 for a row left as it is (`count`, or a new one).  Asynchronous."""
+        import torch
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float64 or points.dim() != 3 or points.shape[0] != self.n_env \
+                or points.shape[1] < 1 or points.shape[2] < 2 or not points.is_contiguous():
+            raise ValueError(f"points must be a contiguous float64 [{self.n_env}, max_pts >= 1, C >= 2] tensor")
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or tuple(counts.shape) != (self.n_env,) \
+                or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int32 [{self.n_env}] tensor")
+        with self._route_writer(count, stream) as (_, st, count):
+            self._ck(self._lib.t2d_polyline_routes(self._h, points.data_ptr(), counts.data_ptr(), points.shape[1], points.shape[2],
+                                                   int(route), count.data_ptr(), st))
+        self._polyline_inputs = (points, counts)   # (kept alive until the launch has run)
         return count
 
     def route_vertices(self):
