@@ -1327,6 +1327,38 @@ int t2d_sample_plan(int32_t device_id, int32_t n, int32_t kind, const double* we
                     int32_t max_nodes, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
                     int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream);
 
+/* The occupancy grid of every env's CURRENT scene, in the layout t2d_grid_dijkstra, t2d_hybrid_astar and t2d_sample_plan read in
+ * place: ONE launch, asynchronous on hip_stream (enqueued behind a step on the same stream it sees that step).  The reference has no
+ * counterpart; the rule is build-defined (tests/occupancy_ref.py).
+ *   window      shared by the batch: H x W cells; cell (row, col) is the CLOSED square of side cell_size centred at
+ *               (origin_x + col * cell_size, origin_y + row * cell_size)
+ *   rule        a cell is OCCUPIED iff the Euclidean distance between it and some listed obstacle, as a closed filled set, is
+ *               <= inflate (0: touches or overlaps; containment either way counts).  fp64 on the fp32 scene data, no division; a cell
+ *               at a distance <= inflate is always occupied, an occupied cell lies within inflate + 2^-42 * (the largest
+ *               coordinate in play) -- rounding can only add cells.
+ *   listed      the env's static rings (t2d_set_static_geometry, undivided; the live quads of a generated scene) and, with
+ *               include_participants, every ACTIVE participant except slot exclude_slot (-1: none excepted): its oriented box
+ *               T2D_P_LENGTH x T2D_P_WIDTH about its pose, corners centre +- L/2 (c, s) +- W/2 (-s, c) with the library's deterministic
+ *               (s, c) of the heading, or, for T2D_SHAPE_CIRCLE, the disc of radius width / 2
+ *   weight_dev  f64 [n_env][H * W] row-major: free_weight (finite, >= 0) in free cells, +inf in occupied ones; mask_dev u8
+ *               [n_env][H][W]: 1 = occupied.  Either may be NULL, not both.  hw_dev i32 [n_env][2] (may be NULL): (H, W);
+ *               status_dev i32 [n_env] (may be NULL): T2D_OCC_*
+ *   format      0, or T2D_OCC_FORMAT_NAIVE: every cell tests every listed element (the measurement yardstick; the same grid)
+ * BUILD-DEFINED, per row, touching only that row: a listed participant whose x, y or heading is not finite makes the row
+ * T2D_OCC_INVALID and EVERY cell of it an obstacle; an inactive participant and a ring of fewer than 3 vertices are ignored.
+ * T2D_ERR_INVALID, nothing launched: H or W < 1 (or more tiles than a launch holds), cell_size outside 1e-150 .. 1e150, inflate
+ * outside 0 .. 1e150, an origin that is not finite, a free_weight that is negative or not finite, exclude_slot outside
+ * -1 .. max_agents - 1, an unknown format bit, both outputs NULL, weight_dev not 16-byte or another pointer not 4-byte aligned.
+ * T2D_ERR_STATE: include_participants before t2d_set_param_table and t2d_reset.  H * W is not capped by T2D_GRID_MAX_CELLS.
+ * kernel_id T2D_PROFILE_OCCUPANCY in t2d_profile_read.                                                                          */
+#define T2D_OCC_OK 0
+#define T2D_OCC_INVALID 1
+#define T2D_OCC_FORMAT_NAIVE 1
+enum { T2D_PROFILE_OCCUPANCY = 21 };
+int t2d_occupancy_grid(t2d_pool* pool, int32_t H, int32_t W, double cell_size, double origin_x, double origin_y, double inflate,
+                       int32_t include_participants, int32_t exclude_slot, double free_weight, double* weight_dev, uint8_t* mask_dev,
+                       int32_t* hw_dev, int32_t* status_dev, int32_t format, void* hip_stream);
+
 /* Following a Reeds-Shepp plan: the parking tutorial's RSAgent (docs/tutorial/train_parking_demo.ipynb cell 17) with the
  * PIDController and rear_center_coord of cell 14, for the ego of every env, in ONE launch in front of the step launch.  It takes
  * over the action row of an env while a path is being executed and leaves the policy's row alone otherwise.
@@ -1775,7 +1807,7 @@ int t2d_set_outputs(t2d_pool* pool, uint32_t mask);
  * 15 = lane-keeping PID controllers (t2d_pid_actions), 16 = pure pursuit and cruise / ACC controllers (t2d_pursuit_actions),
  * 17 = curve lines into the route sets (t2d_curve_routes), 18 = spline curves into the route sets (t2d_spline_routes),
  * 19 = plan-view reference lines into the route sets (t2d_planview_routes), 20 = a caller's polylines into the route sets
- * (t2d_polyline_routes).  */
+ * (t2d_polyline_routes), 21 = the occupancy grid of every env (t2d_occupancy_grid).  */
 int t2d_profile_enable(t2d_pool* pool, int32_t on);
 int t2d_profile_read(t2d_pool* pool, int32_t kernel_id, double* total_ms, int64_t* launches);
 

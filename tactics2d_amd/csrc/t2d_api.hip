@@ -3771,6 +3771,48 @@ int t2d_camera_buffers(t2d_pool* p, void** class_dev, void** rgb_dev, size_t* cl
     return T2D_OK;
 }
 
+// ---- occupancy grid (kernel: t2d_occupancy.hip) ---------------------------------------------------------------------------------
+int t2d_occupancy_grid(t2d_pool* p, int32_t H, int32_t W, double cell_size, double origin_x, double origin_y, double inflate,
+                       int32_t include_participants, int32_t exclude_slot, double free_weight, double* weight_dev, uint8_t* mask_dev,
+                       int32_t* hw_dev, int32_t* status_dev, int32_t format, void* hip_stream) {
+    if (!p) return T2D_ERR_INVALID;
+    if (H < 1 || W < 1) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: H and W must be at least 1");
+    if (!(cell_size >= 1e-150 && cell_size <= 1e150)) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: cell_size must be in 1e-150 .. 1e150");
+    if (!(inflate >= 0.0 && inflate <= 1e150)) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: inflate must be in 0 .. 1e150");
+    if (!__builtin_isfinite(origin_x) || !__builtin_isfinite(origin_y)) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: the origin must be finite");
+    if (!(free_weight >= 0.0) || !__builtin_isfinite(free_weight))
+        return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: free_weight must be finite and not negative");
+    if (exclude_slot < -1 || exclude_slot >= p->v.A)
+        return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: exclude_slot " + std::to_string(exclude_slot) + " outside -1 .. max_agents - 1");
+    if (format & ~(int32_t)T2D_OCC_FORMAT_NAIVE) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: unknown format bit");
+    if (!weight_dev && !mask_dev) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: weight_dev and mask_dev are both null");
+    if (((uintptr_t)weight_dev & 15) || (((uintptr_t)mask_dev | (uintptr_t)hw_dev | (uintptr_t)status_dev) & 3))
+        return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: weight_dev must be 16-byte, the other pointers 4-byte aligned");
+    const size_t tiles = (size_t)((W + 31) / 32) * (size_t)((H + 31) / 32);
+    if (tiles * (size_t)p->v.n_env > 0x7fffffffull) return fail(p, T2D_ERR_INVALID, "t2d_occupancy_grid: grids too large for one launch");
+    if (include_participants && (!p->have_params || !p->have_reset))
+        return fail(p, T2D_ERR_STATE, "t2d_set_param_table and t2d_reset must precede t2d_occupancy_grid with participants");
+    hipStream_t s = (hipStream_t)hip_stream;
+    T2D_HIP(p, hipSetDevice(p->device));
+    int rc;
+    if ((rc = camera_refresh_geo(p))) return rc;   // (the rings' device copy is the camera's)
+    t2d::OccView ov{};
+    ov.H = H; ov.W = W; ov.include_participants = include_participants != 0; ov.exclude_slot = exclude_slot;
+    ov.cell_size = cell_size; ov.origin_x = origin_x; ov.origin_y = origin_y; ov.inflate = inflate; ov.free_weight = free_weight;
+    // the window's magnitude (tests/occupancy_ref.py: window_magnitude, the same operations)
+    const double fx = origin_x + (double)(W - 1) * cell_size, fy = origin_y + (double)(H - 1) * cell_size;
+    ov.mwin = (fmax(fmax(fabs(origin_x), fabs(fx)), fmax(fabs(origin_y), fabs(fy))) + cell_size) + inflate;
+    if (p->scene_mode) {
+        ov.scene_quads = p->scene.live.quads; ov.scene_quad_id = p->scene.live.quad_id; ov.scene_n_quads = p->scene.live.n_quads;
+    } else {
+        ov.env_poly_off = p->camera.env_poly_off[0]; ov.poly_vert_off = p->camera.poly_vert_off[0]; ov.poly_xy = p->camera.poly_xy[0];
+    }
+    touch(p, s);
+    if ((rc = record_event(p, T2D_PROFILE_OCCUPANCY, s, true))) return rc;
+    T2D_HIP(p, t2d::launch_occupancy(p->v, ov, weight_dev, mask_dev, hw_dev, status_dev, (format & T2D_OCC_FORMAT_NAIVE) != 0, s));
+    return record_event(p, T2D_PROFILE_OCCUPANCY, s, false);
+}
+
 int t2d_set_outputs(t2d_pool* p, uint32_t mask) {
     if (!p) return T2D_ERR_INVALID;
     if (mask & ~T2D_OUT_ALL) return fail(p, T2D_ERR_INVALID, "unknown output bit");

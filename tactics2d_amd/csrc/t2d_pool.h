@@ -322,6 +322,19 @@ struct CameraView {
     uint8_t class_of_type[T2D_MAX_TYPES];
 };
 
+// Occupancy grid (t2d_occupancy.hip): the window shared by the batch and the listing of the static rings -- the camera's device
+// copy of the caller's rings (kind 0), or, in scene mode, the generated scenes' live quads.
+struct OccView {
+    int32_t H, W, include_participants, exclude_slot;
+    double cell_size, origin_x, origin_y, inflate, free_weight;
+    double mwin;                         // the window's magnitude: what the guard of an element is at least taken of
+    const int32_t* env_poly_off;         // [E + 1] or null
+    const int32_t* poly_vert_off;        // [P + 1]
+    const float* poly_xy;                // [V][2]
+    const float* scene_quads;            // scene mode: [E][T2D_GEN_MAX_QUADS][4][2], else null
+    const int32_t *scene_quad_id, *scene_n_quads;
+};
+
 // The Reeds-Shepp planner (t2d_rs.hip): the configuration of t2d_rs_config and where a plan launch reads the target from.
 struct RsPlanView {
     t2d_rs_params cfg;
@@ -686,6 +699,9 @@ hipError_t launch_track_install(const PoolView& v, const TrackGenView& g, const 
 // BEV camera (t2d_camera.hip): the class and / or RGB image of every env (null: not written); naive = every pixel tests every element
 hipError_t launch_camera(const PoolView& v, const CameraView& cv, const TrackView& tv, uint8_t* out_class, uint8_t* out_rgb, int naive,
                          hipStream_t s);
+// occupancy grid (t2d_occupancy.hip): weights and / or mask of every env (null: not written); naive = every cell tests every element
+hipError_t launch_occupancy(const PoolView& v, const OccView& ov, double* weight, uint8_t* mask, int32_t* hw, int32_t* status, int naive,
+                            hipStream_t s);
 // Reeds-Shepp planner (t2d_rs.hip): one plan record per env from the scan [n_env][n_beams]
 hipError_t launch_rs_plan(const PoolView& v, const RsPlanView& rv, const float* scan, t2d_rs_plan_record* out, hipStream_t s);
 // Reeds-Shepp path follower (t2d_rs_follow.hip): one action row and one record per env; agent.reset() for the masked envs (null: all)

@@ -73,7 +73,7 @@ class VecParkingEnv:
 
     def __init__(self, n_envs, max_step=int(2e4), continuous=True, auto_reset=False, seed=0, device_id=0,
                  scene_source="layout", type_proportion=0.5, info_lidar=True, copy=True, zero_copy=None, lidar_beams=360,
-                 observation="state", rs_planner=False, rs_follow=False):
+                 observation="state", rs_planner=False, rs_follow=False, occupancy=None):
         """scene_source: "generator" = the device-side ParkingLotGenerator (tactics2d_amd.generator; bay and
         parallel scenes with the reference's rejection sampler, `type_proportion` as in envs/parking.py:331-333),
         "layout" = the fixed bay layout of scenarios.parking (BASELINE config 2).
@@ -98,8 +98,14 @@ class VecParkingEnv:
         notebook's RSAgent) in front of the step: an env that holds a path, or whose last plan was found, is stepped with the
         follower's action, the others with the caller's; `actions` itself is never written.  The result gains `action` (float32
         [n, 2]: what was stepped) and `rs_follow` (the follower's record views); reset() clears the follower and ends with a scan
-        and a plan of the reset state, so the first step has a record to adopt."""
+        and a plan of the reset state, so the first step has a record to adopt.
+        occupancy: None, or the keywords of sensor.OccupancyGrid behind the pool (H, W, cell_size, origin, inflate, ...): reset()
+        and step_torch() launch the occupancy grid of every env behind the step (and the scan) on the same stream;
+        step_torch() adds `occupancy` (float64 [n, H, W]: the weights search.HybridAStar.plan_batch / Dijkstra.plan_batch read
+        in place, with `self.occupancy_grid.planner_kwargs()`) and `occupancy_mask` (u8 [n, H, W])."""
         self.observation = _check_observation(observation)
+        self.occupancy = None if occupancy is None else dict(occupancy)
+        self.occupancy_grid = None
         self.rs_planner = bool(rs_planner)
         self.rs_follow = bool(rs_follow)
         if self.rs_follow and not self.rs_planner:
@@ -191,6 +197,11 @@ class VecParkingEnv:
             self.planner.plan(self._t_lidar, st)
         fr = m.pool.frame_fetch(fresh=self.copy)
         fr = self._last = fr.copy() if self.copy_always else fr
+        if self.occupancy is not None:   # the grid of the new lots, on torch's current stream
+            from .sensor import OccupancyGrid
+            if self.occupancy_grid is None:
+                self.occupancy_grid = OccupancyGrid(m.pool, **self.occupancy)
+            self.occupancy_grid.render()
         if self.observation == "camera":
             from .sensor import BEVCamera
             # BEVCamera(perception_range=(20, 20, 20, 20)) bound to the agent  envs/parking.py:306-308
@@ -274,8 +285,11 @@ class VecParkingEnv:
             pool.lidar_scan(self._t_lidar.data_ptr(), st.cuda_stream)
             cam = self.camera.render(st.cuda_stream) if self.observation == "camera" else {}
             plan = self.planner.plan(self._t_lidar, st) if self.planner is not None else None
+            occ = self.occupancy_grid.render(st.cuda_stream) if self.occupancy_grid is not None else None
         out = dict(self._t_views)
         out["lidar"] = self._t_lidar
+        if occ is not None:
+            out["occupancy"], out["occupancy_mask"] = occ["occupancy"], occ["occupancy_mask"]
         if plan is not None:
             out["rs_plan"] = plan
         if follow is not None:

@@ -103,6 +103,10 @@ SAMPLE_FOUND, SAMPLE_MAX_ITER, SAMPLE_TRUNCATED, SAMPLE_OVERFLOW, SAMPLE_INVALID
 SAMPLE_LDS_NODES = 512
 SAMPLE_NODE_BYTES = 28
 PROFILE_POLYLINE_ROUTES = 20
+# Occupancy grid (t2d_occupancy_grid): the status of a row, the format bit of the measurement yardstick, the kernel id
+OCC_OK, OCC_INVALID = range(2)
+OCC_FORMAT_NAIVE = 1
+PROFILE_OCCUPANCY = 21
 # Reeds-Shepp path follower (t2d_rs_follow): the record's size in bytes, its event bits, the kernel id
 RS_FOLLOW_RECORD_BYTES = 48
 RS_FOLLOW_RECORD_FIELDS = {"executing": ("<i4", 0), "segment": ("<i4", 1), "events": ("<i4", 2), "steps": ("<i4", 3),

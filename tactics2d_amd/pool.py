@@ -104,6 +104,18 @@ class HostFrame:
         return HostFrame(self.base[:end].copy(), self.lay)
 
 
+class OccupancyGrids:
+    """What ParticipantPool.occupancy_grid returns: device tensors, one row per env.  weight float64 [n_env, H, W] (free_weight
+    or +inf), mask uint8 [n_env, H, W] (1 = occupied), hw int32 [n_env, 2], status int32 [n_env]; cell_size and origin are the
+    window's (planner_kwargs(): what the planners of `search` take beside the weights)."""
+
+    def __init__(self, weight, mask, hw, status, cell_size, origin):
+        self.weight, self.mask, self.hw, self.status, self.cell_size, self.origin = weight, mask, hw, status, cell_size, origin
+
+    def planner_kwargs(self):
+        return dict(cell_size=self.cell_size, origin=self.origin)
+
+
 class ParticipantPool:
     """n_env environments x max_agents participants resident on one MI355X."""
 
@@ -857,6 +869,43 @@ class ParticipantPool:
             if b[k][0]:
                 out[k] = torch.as_tensor(_DevArray(b[k][0], shape, "|u1", self), device=dev)
         return out
+
+    # ---------------------------------------------------------------- occupancy grid
+    def occupancy_grid(self, H, W, cell_size, origin, inflate=0.0, include_participants=False, exclude_slot=None, free_weight=1.0,
+                       weight=None, mask=None, stream=None, naive=False):
+        """t2d_occupancy_grid: the occupancy grid of every env's current scene in one launch, asynchronous on `stream` (None:
+        torch's current stream).  The window is shared by the batch: cell (row, col) is the closed square of side cell_size
+        centred at origin + (col, row) * cell_size, occupied iff its distance to a static ring (or a live quad of a generated
+        scene) or -- include_participants -- to an active participant's box or disc is <= inflate; exclude_slot: the participant
+        left out (None: the pool's ego index, -1: none).  weight: a contiguous float64 CUDA tensor [n_env, H, W] written in place
+        (free_weight in free cells, +inf in occupied ones: what search.plan_batch / HybridAStar.plan_batch / RRT.plan_batch read
+        in place), mask: uint8 [n_env, H, W] (1 = occupied); what is not passed is allocated.  naive=True: the measurement
+        yardstick (the same grid).  Returns OccupancyGrids: weight, mask, hw int32 [n_env, 2], status int32 [n_env] (OCC_OK /
+        OCC_INVALID: a listed participant's pose is not finite, every cell of the row is an obstacle), cell_size, origin."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        H, W = int(H), int(W)
+        if exclude_slot is None:
+            exclude_slot = self.status_config.ego_index if hasattr(self, "status_config") else 0
+        if len(origin) != 2:
+            raise ValueError(f"origin must be two numbers, got {origin}")
+        if H >= 1 and W >= 1:
+            for name, t, dt in (("weight", weight, torch.float64), ("mask", mask, torch.uint8)):
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (self.n_env, H, W)
+                                      or not t.is_contiguous() or t.device != dev):
+                    raise ValueError(f"{name} must be a contiguous {dt} [{self.n_env}, {H}, {W}] tensor on {dev}")
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev)):
+            shape = (self.n_env, max(H, 0), max(W, 0))
+            weight = torch.empty(shape, dtype=torch.float64, device=dev) if weight is None else weight
+            mask = torch.empty(shape, dtype=torch.uint8, device=dev) if mask is None else mask
+            hw = torch.empty((self.n_env, 2), dtype=torch.int32, device=dev)
+            status = torch.empty(self.n_env, dtype=torch.int32, device=dev)
+            self._ck(self._lib.t2d_occupancy_grid(self._h, H, W, float(cell_size), float(origin[0]), float(origin[1]), float(inflate),
+                                                  int(bool(include_participants)), int(exclude_slot), float(free_weight),
+                                                  weight.data_ptr(), mask.data_ptr(), hw.data_ptr(), status.data_ptr(),
+                                                  L.OCC_FORMAT_NAIVE if naive else 0, st))
+        return OccupancyGrids(weight, mask, hw, status, float(cell_size), (float(origin[0]), float(origin[1])))
 
     def parking_scenes(self, seed, type_proportion=0.5, vehicle_size=(5.3, 2.5), regenerate=False, first_env=0,
                        env_stride=None):

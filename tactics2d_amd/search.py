@@ -14,7 +14,10 @@ Hybrid A* on the device: the reference's `tactics2d.search.HybridAStar.plan` for
     out = HybridAStar.plan_batch(starts, targets, boundaries, weight_grids)     # out.path, out.path_len, out.status, ...: device tensors
     states = HybridAStar.plan(start, target, boundary, weight_grid, grid_collide)   # one query with the reference's signature
 
-The obstacles are the +inf / NaN cells of the SAME weight grids `cost_to_go` takes.  The kernel equals tests/hybrid_astar_ref.py bit
+The obstacles are the +inf / NaN cells of the SAME weight grids `cost_to_go` takes.  Such a grid comes from the scene a pool holds
+on the device -- `ParticipantPool.occupancy_grid` / `sensor.OccupancyGrid`: conservative, obstacles grown by a
+clearance, in this layout, with `planner_kwargs()` for cell_size and origin --, from `generator.GridMapGenerator`, or from the caller's
+own tensor.  The kernel equals tests/hybrid_astar_ref.py bit
 for bit; that specification equals the reference on its recorded fixture (cos / sin are this library's deterministic ones).
 
 The sampling planners on the device: the reference's `RRT.plan`, `RRTStar.plan` and `RRTConnect.plan` for n queries in ONE launch of

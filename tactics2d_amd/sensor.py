@@ -126,3 +126,65 @@ class BEVCamera:
         v = self.render()
         self.pool.sync()
         return {k: t.cpu().numpy() for k, t in v.items()}
+
+
+def parking_window(vehicle_size=(5.3, 2.5)):
+    """(x_min, x_max, y_min, y_max) of the window every lot of the device-side ParkingLotGenerator lies in, whatever its seed
+    (DESIGN.md 4.24), from the generator's own constants.  y: the back wall is at most 1.5 m deep below y = 0; the perturbed
+    vehicles behind the start range stay in a box (+ 0.5 m of perturbation) that ends at y_max + slot_len + 8 with
+    y_max <= 2 R + 2.4 (R: half the vehicle's diagonal; the side vehicles sit at most 1.6 m above their own lower extent) and
+    slot_len <= 7.  x: the back wall and that box are 30 m wide about x = 0; the outermost side vehicle's centre lies at most
+    next + max(1.6, thr + 0.8) + n_more (next + 0.8) from it (parallel lots: next = length, thr = length / 4, n_more = 2; bay
+    lots: next = width, thr = 0.85, n_more = 3) and reaches R further.  Rounded outwards to whole metres."""
+    ln, wd = float(vehicle_size[0]), float(vehicle_size[1])
+    r = 0.5 * float(np.hypot(ln, wd))
+    side = max(ln + max(1.6, 0.25 * ln + 0.8) + 2 * (ln + 0.8), wd + max(1.6, 0.85 + 0.8) + 3 * (wd + 0.8))
+    half = float(np.ceil(max(15.0 + 0.5, side + r)))
+    return -half, half, -2.0, float(np.ceil(2 * r + 17.4 + 0.5))
+
+
+class OccupancyGrid:
+    """The occupancy grid of every env of a ParticipantPool (t2d_occupancy_grid), beside BEVCamera: what the grid
+    planners of `search` read in place.
+
+        grid = OccupancyGrid(pool, 64, 64, 0.5, inflate=1.2)      # H x W cells of 0.5 m, obstacles grown by 1.2 m
+        v = grid.render(stream)                                   # {"occupancy": f64 [n_env, H, W], "occupancy_mask": u8 [n_env, H, W], ...}
+        out = HybridAStar.plan_batch(starts, targets, boundaries, v["occupancy"], **grid.planner_kwargs())
+
+    The object owns its buffers: render() launches once and returns the same tensors every time (they change with the next
+    render()).  origin: the centre of cell (0, 0); None centres the window on parking_window(vehicle_size), the window the lots of
+    the device-side ParkingLotGenerator share.  exclude_slot None: the pool's ego index; naive=True: the measurement yardstick."""
+
+    def __init__(self, pool, H, W, cell_size, origin=None, inflate=0.0, include_participants=False, exclude_slot=None,
+                 free_weight=1.0, naive=False, vehicle_size=(5.3, 2.5)):
+        import torch
+        self.pool, self.H, self.W, self.cell_size = pool, int(H), int(W), float(cell_size)
+        if origin is None:
+            x0, x1, y0, y1 = parking_window(vehicle_size)
+            origin = (0.5 * (x0 + x1) - 0.5 * (self.W - 1) * self.cell_size, 0.5 * (y0 + y1) - 0.5 * (self.H - 1) * self.cell_size)
+        self.origin = (float(origin[0]), float(origin[1]))
+        self.inflate, self.include_participants, self.exclude_slot = float(inflate), bool(include_participants), exclude_slot
+        self.free_weight, self.naive = float(free_weight), bool(naive)
+        dev = torch.device("cuda", pool.device_id)
+        self.weight = torch.empty((pool.n_env, self.H, self.W), dtype=torch.float64, device=dev)
+        self.mask = torch.empty((pool.n_env, self.H, self.W), dtype=torch.uint8, device=dev)
+        self.hw = torch.empty((pool.n_env, 2), dtype=torch.int32, device=dev)
+        self.status = torch.empty(pool.n_env, dtype=torch.int32, device=dev)
+        if self.exclude_slot is None:
+            self.exclude_slot = pool.status_config.ego_index if hasattr(pool, "status_config") else 0
+        self._device = dev
+
+    def planner_kwargs(self):
+        """cell_size and origin as HybridAStar.plan_batch / RRT.plan_batch take them: they cannot disagree with the grid"""
+        return dict(cell_size=self.cell_size, origin=self.origin)
+
+    def render(self, stream=None):
+        """One launch into the object's own tensors, asynchronous on `stream` (None: torch's current stream); returns them."""
+        import torch
+        p = self.pool
+        st = stream if stream is not None else torch.cuda.current_stream(self._device).cuda_stream
+        p._ck(p._lib.t2d_occupancy_grid(p._h, self.H, self.W, self.cell_size, self.origin[0], self.origin[1], self.inflate,
+                                        int(self.include_participants), int(self.exclude_slot), self.free_weight, self.weight.data_ptr(),
+                                        self.mask.data_ptr(), self.hw.data_ptr(), self.status.data_ptr(),
+                                        L.OCC_FORMAT_NAIVE if self.naive else 0, st))
+        return dict(occupancy=self.weight, occupancy_mask=self.mask, occupancy_hw=self.hw, occupancy_status=self.status)
