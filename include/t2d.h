@@ -53,6 +53,7 @@
  *   t2d_hybrid_astar      <- HybridAStar.plan  search/hybrid_a_star.py:58-172 with create_grid_collision_checker  tests/test_search.py:128-191
  *   t2d_sample_plan       <- RRT.plan  search/rrt.py:74-164; RRTStar.plan / _choose_parent  search/rrt_star.py:22-201;
  *                            RRTConnect.plan  search/rrt_connect.py:72-206, with the same collision checker
+ *   t2d_prm_plan          <- PRM.plan  search/prm.py:52-344, with the same collision checker
  *   t2d_set_tracks /      <- _RacingScenarioManager._locate_agent / check_status  envs/racing.py:261-301, 339-369
  *   t2d_track_progress       RacingEnv._get_rewards                envs/racing.py:121-139
  *   t2d_generate_tracks / <- RacingTrackGenerator.generate         map/generator/generate_racing_track.py (random stream: build-defined)
@@ -1326,6 +1327,54 @@ int t2d_sample_plan(int32_t device_id, int32_t n, int32_t kind, const double* we
                     double extension_step, double radius, double cell_size, double origin_x, double origin_y, int32_t max_iter,
                     int32_t max_nodes, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
                     int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream);
+
+/* Probabilistic roadmaps on the device -- search/prm.py: PRM.plan (:52-344) -- for n independent queries in ONE launch, asynchronous
+ * on hip_stream, no pool (tests/prm_ref.py).  One workgroup runs one query; fp64, one rounding per operation.
+ *   nodes        node 0 is the start, node 1 the target, node 2 + s is (x_min + (x_max - x_min) * u(2 s), y_min + (y_max - y_min) *
+ *                u(2 s + 1)) with u(k) draw k of the row's stream (seed_dev as t2d_sample_plan takes it).  N = n_samples + 2 <=
+ *                T2D_PRM_MAX_NODES.  A sample is NOT collision-checked, as in the reference: a node inside an obstacle stays, isolated.
+ *   neighbours   connection_radius == 0: of node i the min(k_nearest + 1, N) smallest dx dx + dy dy in the order (d2, index), i
+ *                itself dropped, ascending.  connection_radius > 0: every j != i with sqrt(d2) <= connection_radius in ascending j;
+ *                a node with more than max_degree of them makes the row T2D_PRM_OVERFLOW.  Only j > i becomes a candidate edge: an
+ *                edge exists because j is near i, not because i is near j (the reference's asymmetry, restated).
+ *   edges        a candidate whose segment touches no obstacle cell (the collision test of t2d_hybrid_astar) is an edge of cost
+ *                sqrt(dx dx + dy dy) of nodes[i] - nodes[j]; the list is ordered by i, within i in the neighbour order.
+ *   search       g[0] = 0, g[v] = min(g[v], fl(g[u] + w)) over both directions of every edge until nothing changes: every sweep
+ *                reads the field of the sweep before it, sweeps_dev counts them, the last one -- which changes nothing -- included.
+ *                The predecessor of v is the u with the smallest (g[u], u) among the neighbours with fl(g[u] + w) == g[v] and
+ *                g[u] < g[v] -- or, at equal g (an edge of cost 0 between coincident nodes), u given its value in an earlier
+ *                sweep than v, so that every walk ends at the start; the path is the walk back from node 1.
+ *   workspace_dev, workspace_bytes: at least t2d_prm_plan_workspace_bytes(n, n_samples, k) bytes, 16-byte aligned, k being k_nearest
+ *                or, in radius mode, max_degree.  It holds the ROADMAP, an output: with K = min(k, N - 1) and E = N * K, query e's
+ *                row starts at e * (workspace bytes / n) and holds the nodes f64 [N][2], dist f64 [N] (the cost from the start to
+ *                every node, +inf where not connected), edge_cost f64 [E], edge_ij i32 [E][2] (the first n_edges entries of each
+ *                are written), then scratch i32 [E].
+ *   path_dev     f64 [n][max_path][2] from the start to the target, NaN past the end; path_len_dev i32 [n]: the FULL length
+ *   status_dev   i32 [n]: T2D_PRM_*; n_edges_dev i32 [n]; sweeps_dev i32 [n]
+ * callback and max_iter are not modelled: the search is always finished.
+ * BUILD-DEFINED, per row, touching only that row: T2D_PRM_INVALID (nothing of the roadmap written, no path) where a coordinate of
+ * the start, the target or the boundary is not finite (above 1e150 in magnitude counts as not finite), where x_min >= x_max or
+ * y_min >= y_max, where the start or the target lies outside the closed boundary grown by 1e-9, where H or W is not positive or
+ * H * W is above max_cells -- the cases in which the reference raises.  T2D_PRM_OVERFLOW (the nodes written, no edge, no path):
+ * radius mode only.  T2D_PRM_NO_PATH: the roadmap does not connect start and target; dist is written.  T2D_PRM_TRUNCATED:
+ * path_len > max_path, the first max_path points are written.  Among exactly coincident nodes the smaller index is the nearer.
+ * T2D_ERR_INVALID, nothing launched: n < 0, max_cells < 1, max_path < 0, n_samples outside 1 .. T2D_PRM_MAX_NODES - 2, a
+ * connection_radius that is negative, NaN or infinite, k_nearest outside 1 .. T2D_PRM_MAX_K in k-nearest mode, max_degree < 1 in
+ * radius mode, cell_size not in 1e-150 .. 1e150, an origin that is not finite, a null or misaligned pointer (path_dev may be NULL
+ * when max_path is 0), a workspace smaller than t2d_prm_plan_workspace_bytes (which returns -1 for arguments out of range).     */
+#define T2D_PRM_FOUND 0
+#define T2D_PRM_NO_PATH 1
+#define T2D_PRM_TRUNCATED 2
+#define T2D_PRM_OVERFLOW 3
+#define T2D_PRM_INVALID 4
+#define T2D_PRM_MAX_NODES 1024
+#define T2D_PRM_MAX_K 16
+int64_t t2d_prm_plan_workspace_bytes(int32_t n, int32_t n_samples, int32_t k_or_degree);
+int t2d_prm_plan(int32_t device_id, int32_t n, const double* weight_dev, const int32_t* hw_dev, int32_t max_cells,
+                 const double* start_dev, const double* target_dev, const double* boundary_dev, const uint64_t* seed_dev,
+                 int32_t n_samples, int32_t k_nearest, double connection_radius, int32_t max_degree, double cell_size,
+                 double origin_x, double origin_y, int32_t max_path, void* workspace_dev, int64_t workspace_bytes, double* path_dev,
+                 int32_t* path_len_dev, int32_t* status_dev, int32_t* n_edges_dev, int32_t* sweeps_dev, void* hip_stream);
 
 /* The occupancy grid of every env's CURRENT scene, in the layout t2d_grid_dijkstra, t2d_hybrid_astar and t2d_sample_plan read in
  * place: ONE launch, asynchronous on hip_stream (enqueued behind a step on the same stream it sees that step).  The reference has no

@@ -159,6 +159,9 @@ SYMBOLS = {
     "t2d_sample_plan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "t2d_sample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64] + [_vp] * 6),
+    "t2d_prm_plan_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "t2d_prm_plan": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double,
+                               C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _vp, C.c_int64] + [_vp] * 6),
     "t2d_occupancy_grid": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                      C.c_double, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "t2d_rs_config": (C.c_int, [_vp, C.POINTER(RSParams), _vp]),

@@ -103,6 +103,11 @@ SAMPLE_FOUND, SAMPLE_MAX_ITER, SAMPLE_TRUNCATED, SAMPLE_OVERFLOW, SAMPLE_INVALID
 SAMPLE_LDS_NODES = 512
 SAMPLE_NODE_BYTES = 28
 PROFILE_POLYLINE_ROUTES = 20
+# Probabilistic roadmaps (t2d_prm_plan): the status of a row; the caps of one query: nodes (start, target and samples; x, y, two
+# planes of g and two words each in LDS), k_nearest (a sorted list in registers)
+PRM_FOUND, PRM_NO_PATH, PRM_TRUNCATED, PRM_OVERFLOW, PRM_INVALID = range(5)
+PRM_MAX_NODES = 1024
+PRM_MAX_K = 16
 # Occupancy grid (t2d_occupancy_grid): the status of a row, the format bit of the measurement yardstick, the kernel id
 OCC_OK, OCC_INVALID = range(2)
 OCC_FORMAT_NAIVE = 1

@@ -30,7 +30,16 @@ t2d_sample_plan, over the same obstacle grids and with the same
 The draws come from the build's counter stream, one stream per query keyed by its seed; the kernel equals tests/sample_plan_ref.py
 bit for bit, and that makes the reference's decisions when the reference is fed the same draws.
 
-A* (`a_star.py`, Dijkstra's cost with a heuristic) and D* (a replanner) remain out of this package.  There is no CPU fallback.
+The probabilistic roadmap on the device: the reference's `PRM.plan` for n queries in ONE launch of t2d_prm_plan, over
+the same obstacle grids and with the same collision checker and streams of draws; it returns the path AND the roadmap:
+
+    out = PRM.plan_batch(starts, targets, boundaries, weight_grids, seeds, n_samples=254)   # out.path, out.nodes, out.edge_ij, out.dist, ...
+    path, (nodes, edges) = PRM.plan(start, target, boundary, weight_grid, grid_collide, seed=7)   # the reference's signature and return
+
+The kernel equals tests/prm_ref.py bit for bit, and that makes the reference's decisions when the reference is fed the same draws.
+
+A* (`a_star.py`: serial, and on these grids `cost_to_go` already gives its cost), D* (`d_star.py`: a serial replanner) and MCTS
+(`mcts.py`: its model is Python callables) remain out of this package.  There is no CPU fallback.
 """
 import math
 
@@ -589,3 +598,197 @@ class RRTConnect:
         the search."""
         return _sample_plan(SAMPLE_RRT_CONNECT, "RRTConnect", start, target, boundary, obstacles, collide_fn, extension_step, max_iter,
                             3.0, callback, seed, device_id)
+
+
+# ---- probabilistic roadmaps ----------------------------------------------------------------------------------------------------------
+PRM_FOUND, PRM_NO_PATH, PRM_TRUNCATED, PRM_OVERFLOW, PRM_INVALID = L.PRM_FOUND, L.PRM_NO_PATH, L.PRM_TRUNCATED, L.PRM_OVERFLOW, L.PRM_INVALID
+PRM_MAX_NODES, PRM_MAX_K = L.PRM_MAX_NODES, L.PRM_MAX_K
+PRM_PLAN_MAX_DEGREE = PRM_MAX_NODES   # where PRM.plan stops doubling max_degree: no node has more neighbours than there are nodes
+
+
+class PRMPaths:
+    """What prm_plan_batch returns: device tensors, one row per query.  path float64 [n, max_path, 2] (from the start to the target,
+    NaN past the end), path_len int32 [n] (the FULL length; > max_path: PRM_TRUNCATED; 0 without a path), status int32 [n] (PRM_FOUND,
+    _NO_PATH, _TRUNCATED, _OVERFLOW, _INVALID), n_edges int32 [n], sweeps int32 [n] (relaxation rounds), and views of the roadmaps in
+    the launch's workspace: nodes float64 [n, n_nodes, 2] (node 0 the start, node 1 the target), edge_ij int32 [n, max_edges, 2] and
+    edge_cost float64 [n, max_edges] (the first n_edges[e] entries of row e are written), dist float64 [n, n_nodes] (the cost from the
+    start to every node, +inf where a node is not connected).  An INVALID row has no roadmap, an OVERFLOW row its nodes only."""
+
+    def __init__(self, path, path_len, status, n_edges, sweeps, nodes, edge_ij, edge_cost, dist):
+        self.path, self.path_len, self.status, self.n_edges, self.sweeps = path, path_len, status, n_edges, sweeps
+        self.nodes, self.edge_ij, self.edge_cost, self.dist = nodes, edge_ij, edge_cost, dist
+
+    def roadmap(self, row):
+        """(nodes, edges) of one row on the host, as PRM.plan returns them: a list of [x, y] and a list of (i, j, cost)"""
+        m = int(self.n_edges[row])
+        nodes = [] if int(self.status[row]) == PRM_INVALID else [[float(x), float(y)] for x, y in self.nodes[row].cpu().numpy()]
+        ij, cost = self.edge_ij[row, :m].cpu().numpy(), self.edge_cost[row, :m].cpu().numpy()
+        return nodes, [(int(i), int(j), float(c)) for (i, j), c in zip(ij, cost)]
+
+
+def prm_plan_batch(starts, targets, boundaries, weight_grids, seeds, hw=None, n_samples=1000, k_nearest=10, connection_radius=None,
+                   max_degree=32, cell_size=1.0, origin=(0.0, 0.0), max_path=256, device_id=0, stream=None):
+    """t2d_prm_plan: n probabilistic-roadmap queries in one launch, asynchronous on `stream`.  starts / targets [n, 2], boundaries
+    [n, 4] (x_min, x_max, y_min, y_max) or [4] for all rows, weight_grids [n, H_max, W_max] (or [H, W]) with hw, cell_size and origin,
+    and seeds (uint64 [n], an int64 / uint64 CUDA tensor, or ONE integer: row_seeds) as sample_plan_batch takes them.  Every query
+    has n_samples + 2 nodes (at most PRM_MAX_NODES).  connection_radius None: each node is joined to its k_nearest nearest (at most
+    PRM_MAX_K); a radius: to every node within it, and a node with more than max_degree of them makes its row PRM_OVERFLOW.  Returns
+    PRMPaths.  ValueError: n_samples below 1 or above PRM_MAX_NODES - 2, k_nearest outside 1 .. PRM_MAX_K, a radius that is not
+    positive and finite, max_degree below 1, a cell_size that is not positive and finite, shapes that disagree."""
+    import torch
+    if not _is_tensor(weight_grids):
+        weight_grids = np.asarray(weight_grids, np.float64)
+    shape = tuple(weight_grids.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1] * shape[2] < 1:
+        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
+    n, h_max, w_max = shape
+    stride = h_max * w_max
+    n_samples, k_nearest, max_degree, max_path = int(n_samples), int(k_nearest), int(max_degree), int(max_path)
+    if n_samples < 1:
+        raise ValueError(f"n_samples must be positive, got {n_samples}")
+    if n_samples + 2 > PRM_MAX_NODES:
+        raise ValueError(f"n_samples + 2 nodes must not exceed PRM_MAX_NODES = {PRM_MAX_NODES}, got n_samples = {n_samples}")
+    by_radius = connection_radius is not None
+    if by_radius:
+        connection_radius = float(connection_radius)
+        if not (0 < connection_radius <= 1e150):
+            raise ValueError(f"connection_radius must be positive, got {connection_radius}")
+        if max_degree < 1:
+            raise ValueError(f"max_degree must be at least 1, got {max_degree}")
+    elif not 1 <= k_nearest <= PRM_MAX_K:
+        raise ValueError(f"k_nearest must be in 1 .. {PRM_MAX_K}, got {k_nearest}")
+    cell_size = float(cell_size)
+    if not (1e-150 <= cell_size <= 1e150):
+        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
+        raise ValueError(f"origin must be two finite numbers, got {origin}")
+    if max_path < 0:
+        raise ValueError(f"max_path must not be negative, got {max_path}")
+    for what, x in (("starts", starts), ("targets", targets)):
+        if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, 2), (2,) if n == 1 else (n, 2)):
+            raise ValueError(f"{what} must have shape ({n}, 2), got {tuple(np.shape(x))}")
+    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
+        boundaries = np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
+    if not _is_tensor(seeds):
+        if np.ndim(seeds) == 0:
+            seeds = row_seeds(int(seeds), n)
+        seeds = np.ascontiguousarray(seeds).astype(np.uint64).reshape(-1)
+        if seeds.shape != (n,):
+            raise ValueError(f"seeds must be one integer or hold one per row ({n}), got {seeds.shape}")
+    elif seeds.dtype not in (torch.int64, torch.uint64) or tuple(seeds.shape) != (n,):
+        raise ValueError(f"seeds as a tensor must be int64 or uint64 [{n}]")
+    n_nodes = n_samples + 2
+    k = max_degree if by_radius else k_nearest
+    max_edges = n_nodes * min(k, n_nodes - 1)
+    lib = _ffi.lib()
+    dev, st = _stream_of(device_id, stream)
+    with torch.cuda.stream(st):
+        if _is_tensor(weight_grids):
+            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
+        else:
+            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
+        hw_t = _i32(np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else hw, dev, (n, 2))
+        s_t, t_t, b_t = _f64(starts, dev, (n, 2)), _f64(targets, dev, (n, 2)), _f64(boundaries, dev, (n, 4))
+        seed_t = seeds.to(dev).contiguous() if _is_tensor(seeds) else torch.as_tensor(seeds.view(np.int64)).to(dev)
+        need = int(lib.t2d_prm_plan_workspace_bytes(n, n_samples, k))
+        row = need // n if n else 0
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        path = torch.empty((n, max_path, 2), dtype=torch.float64, device=dev)
+        path_len, status, n_edges, sweeps = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+        if n:   # (an empty batch has no memory to point at and nothing to launch)
+            _ffi.check(lib.t2d_prm_plan(device_id, n, w.data_ptr(), hw_t.data_ptr(), stride, s_t.data_ptr(), t_t.data_ptr(), b_t.data_ptr(),
+                                        seed_t.data_ptr(), n_samples, k_nearest if not by_radius else 1,
+                                        connection_radius if by_radius else 0.0, max_degree if by_radius else 1, cell_size, float(origin[0]),
+                                        float(origin[1]), max_path, ws.data_ptr(), need, path.data_ptr() if max_path else None,
+                                        path_len.data_ptr(), status.data_ptr(), n_edges.data_ptr(), sweeps.data_ptr(), st.cuda_stream),
+                       None, lib)
+            rows = ws[:need].view(n, row)
+            part = lambda lo, hi, dt: rows[:, lo:hi].view(dt)   # (a row is a multiple of 256 bytes: every part stays aligned)
+            nodes = part(0, 16 * n_nodes, torch.float64).view(n, n_nodes, 2)
+            dist = part(16 * n_nodes, 24 * n_nodes, torch.float64)
+            edge_cost = part(24 * n_nodes, 24 * n_nodes + 8 * max_edges, torch.float64)
+            edge_ij = part(24 * n_nodes + 8 * max_edges, 24 * n_nodes + 16 * max_edges, torch.int32).view(n, max_edges, 2)
+        else:   # (an empty batch: nothing was launched, the views are empty tensors of the same shapes)
+            nodes = torch.empty((0, n_nodes, 2), dtype=torch.float64, device=dev)
+            dist = torch.empty((0, n_nodes), dtype=torch.float64, device=dev)
+            edge_cost = torch.empty((0, max_edges), dtype=torch.float64, device=dev)
+            edge_ij = torch.empty((0, max_edges, 2), dtype=torch.int32, device=dev)
+    out = PRMPaths(path, path_len, status, n_edges, sweeps, nodes, edge_ij, edge_cost, dist)
+    out._inputs = (w, hw_t, s_t, t_t, b_t, seed_t, ws)   # (kept alive with the result)
+    return out
+
+
+class PRM:
+    """PRM (search/prm.py) over a weight grid, with the grid collision checker of the reference's tests."""
+
+    plan_batch = staticmethod(prm_plan_batch)
+
+    @staticmethod
+    def plan(start, target, boundary, obstacles, collide_fn=None, n_samples=1000, k_nearest=10, connection_radius=None, max_iter=100000,
+             callback=None, seed=None, device_id=0):
+        """PRM.plan (prm.py:52-344) with the reference's argument order, defaults and ValueError messages.  `obstacles` is the weight
+        grid [H, W] (+inf or NaN: an obstacle cell, a unit square centred at (col, row)); `collide_fn` must be None or
+        `search.grid_collide`; `callback` must be None (TypeError otherwise: a Python callable cannot run in a kernel).  seed: the
+        64-bit key of the query's stream of draws; None takes ONE draw of numpy's global stream for it.  Returns the reference's
+        (path, (nodes, edges)): a list of [x, y] from the start to the target ([] without a path), a list of [x, y] and a list of
+        (i, j, cost).  A path longer than 256 points runs once more with its length; in radius mode a node with more than 32
+        neighbours doubles the room up to PRM_MAX_NODES, then RuntimeError.  max_iter: the reference's search pops at most
+        2 * n_edges + 1 entries, so a max_iter at or above that cannot bind; below it ValueError -- a binding max_iter is not
+        modelled.  Synchronous."""
+        if callback is not None:
+            raise TypeError(f"PRM.plan runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
+        if collide_fn is not None and collide_fn is not grid_collide:
+            raise TypeError("PRM.plan runs on the device, where a Python callable cannot be called: collide_fn must be None or "
+                            "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
+                            f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+        grid = np.asarray(obstacles, np.float64)
+        if grid.ndim != 2:
+            raise ValueError(f"obstacles must be a 2D weight grid, got shape {grid.shape}")
+        if len(start) < 2 or len(target) < 2 or len(boundary) != 4:
+            raise ValueError("start and target must be [x, y], boundary [x_min, x_max, y_min, y_max]")
+        boundary_arr = np.asarray(boundary)
+        x_min, x_max, y_min, y_max = boundary_arr
+        if x_min >= x_max or y_min >= y_max:
+            raise ValueError(f"Invalid boundary: {boundary_arr}. Must satisfy x_min < x_max and y_min < y_max")
+        eps = 1e-9
+        for who, point in (("start", start), ("target", target)):
+            if not (x_min - eps <= point[0] <= x_max + eps):
+                raise ValueError(f"{who} x-coordinate {point[0]} is outside boundary x-range [{x_min}, {x_max}]")
+            if not (y_min - eps <= point[1] <= y_max + eps):
+                raise ValueError(f"{who} y-coordinate {point[1]} is outside boundary y-range [{y_min}, {y_max}]")
+        if n_samples <= 0:
+            raise ValueError(f"n_samples must be positive, got {n_samples}")
+        if k_nearest <= 0:
+            raise ValueError(f"k_nearest must be positive, got {k_nearest}")
+        if connection_radius is not None and connection_radius <= 0:
+            raise ValueError(f"connection_radius must be positive, got {connection_radius}")
+        if max_iter <= 0:
+            raise ValueError(f"max_iter must be positive, got {max_iter}")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))   # (ONE draw of numpy's global stream: np.random.seed(k) repeats it)
+        seed = int(seed) & _MASK64
+        max_path, max_degree = 256, 32
+        while True:
+            out = prm_plan_batch(np.float64([list(start)[:2]]), np.float64([list(target)[:2]]), np.float64([list(boundary)]), grid[None],
+                                 np.array([seed], np.uint64), None, n_samples, k_nearest, connection_radius, max_degree, max_path=max_path,
+                                 device_id=device_id)
+            status, length = int(out.status[0]), int(out.path_len[0])
+            if status == PRM_OVERFLOW and max_degree < PRM_PLAN_MAX_DEGREE:
+                max_degree *= 2   # (the same seed: the same roadmap with more room)
+            elif status == PRM_TRUNCATED:
+                max_path = length   # (a path longer than the first buffer: once more with its length)
+            else:
+                break
+        if status == PRM_OVERFLOW:
+            raise RuntimeError(f"PRM outgrew the device's caps: a node has more than {max_degree} neighbours within {connection_radius}; "
+                               "the roadmap was not finished, which is not the same as no path")
+        if status == PRM_INVALID:
+            raise ValueError(f"start {list(start)}, target {list(target)} or boundary {list(boundary)} is not finite, or the grid is empty")
+        nodes, edges = out.roadmap(0)
+        if max_iter < 2 * len(edges) + 1:
+            raise ValueError(f"max_iter = {max_iter} is below 2 * n_edges + 1 = {2 * len(edges) + 1}, the most the reference's search can "
+                             "pop on this roadmap: a binding max_iter is not modelled")
+        path = [[float(v) for v in p] for p in out.path[0, :length].cpu().numpy()] if status == PRM_FOUND else []
+        return path, (nodes, edges)
