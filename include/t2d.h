@@ -50,6 +50,7 @@
  *   t2d_spline_curves /   <- Bezier.get_curve / BSpline.get_curve / CubicSpline.get_curve  interpolator/bezier.py, b_spline.py,
  *   t2d_spline_routes        cubic_spline.py over interpolator/cpp_interpolator/src/{bezier,b_spline,cubic_spline}.cpp
  *   t2d_grid_dijkstra     <- Dijkstra.plan / plan_graph  search/dijkstra.py:24-394 over grid_to_csr  search/graph_utils.py:10-150
+ *   t2d_grid_astar        <- AStar.plan / plan_graph  search/a_star.py:23-404 over the same graph
  *   t2d_hybrid_astar      <- HybridAStar.plan  search/hybrid_a_star.py:58-172 with create_grid_collision_checker  tests/test_search.py:128-191
  *   t2d_sample_plan       <- RRT.plan  search/rrt.py:74-164; RRTStar.plan / _choose_parent  search/rrt_star.py:22-201;
  *                            RRTConnect.plan  search/rrt_connect.py:72-206, with the same collision checker
@@ -1215,6 +1216,63 @@ int t2d_grid_dijkstra(int32_t device_id, int32_t n, const double* weight_dev, co
                       const int32_t* target_dev, int32_t max_cells, int32_t connectivity, double diagonal_cost_multiplier,
                       int32_t max_path, double* g_dev, int32_t* path_dev, int32_t* path_len_dev, int32_t* status_dev,
                       int32_t* sweeps_dev, void* hip_stream);
+
+/* Grid A* on the device -- search/a_star.py: AStar.plan_graph (:279-404; AStar.plan :23-276 is the same loop) over the graph of
+ * search/graph_utils.py: grid_to_csr, for n independent queries in ONE launch, asynchronous on hip_stream, no pool
+ * (tests/astar_ref.py).  One wave runs one query.  The rule is the reference's, decision for decision: pop the
+ * open entry with the smallest (f, cell); a popped entry whose cell is closed costs one iteration and does nothing else; close
+ * the cell, test it against the target; relax every neighbour that is not closed with fl(g[cur] + e(cur, nb)), e being
+ * t2d_grid_dijkstra's edge expression (an edge of weight exactly 0 is no edge): a STRICTLY smaller sum sets came_from, g and
+ * f = fl(g + fl(heuristic_scale * h)) and pushes (f, nb); the loop runs while the open set is not empty and i < max_iter.
+ *   weight_dev, hw_dev, source_dev, target_dev, max_cells, connectivity, diagonal_cost_multiplier, max_path: t2d_grid_dijkstra's
+ *                layout and meaning; a target is required (no field-only call)
+ *   heuristic_kind  one per launch; fp64, one rounding per operation, dx = x - hx, dy = y - hy for the cell (x, y) = (col, row):
+ *                T2D_ASTAR_H_ZERO 0; T2D_ASTAR_H_EUCLIDEAN sqrt(dx dx + dy dy) (correctly rounded); T2D_ASTAR_H_MANHATTAN
+ *                |dx| + |dy|; T2D_ASTAR_H_OCTILE hi + (diagonal_cost_multiplier - 1.0) * lo with hi / lo the larger / smaller of
+ *                |dx|, |dy|; T2D_ASTAR_H_TABLE h_dev f64 [n][max_cells], one value per cell, the caller's
+ *   htarget_dev  f64 [n][2]: the point (hx, hy) in cell units the built-in kinds measure against -- NOT the target cell: AStar.plan
+ *                measures against the unrounded target.  May be NULL for ZERO and TABLE; h_dev may be NULL unless TABLE.
+ *   heuristic_scale  f = g + heuristic_scale * h; the product is always formed (exact at 1.0): weighted A*
+ *   max_iter     the reference's; a value <= 0 pops nothing
+ *   cell_size, origin_x / origin_y: path_xy only, as in t2d_hybrid_astar
+ *   workspace_dev, workspace_bytes: at least t2d_grid_astar_workspace_bytes(n, max_cells, connectivity) bytes, 16-byte aligned,
+ *                contents irrelevant before and after: per cell the f of each push (one per neighbour), scale * h, g, came_from
+ *   path_dev     i32 [n][max_path]: the cells from source to target, -1 past the end; path_len_dev i32 [n]: the FULL length
+ *                (0 without a path); path_xy_dev f64 [n][max_path][2] or NULL: origin + (col, row) * cell_size, NaN past the end
+ *                (t2d_polyline_routes takes it as it is)
+ *   status_dev   i32 [n]: T2D_GRID_FOUND, _NO_PATH (the open set ran empty), _MAX_ITER (i reached max_iter with entries left),
+ *                _TRUNCATED (the path is longer than max_path; its first max_path cells are written), _INVALID
+ *   iterations_dev i32 [n]: the reference's i when it returns (the final pop of a found target is not counted, stale pops are);
+ *                expanded_dev i32 [n]: the closed cells
+ *   g_dev f64 / closed_dev u8 / parent_dev i32 [n][max_cells], each may be NULL: g_score, closed and came_from (-1: none) as they
+ *                stand at termination -- the state of the reference's last callback; tentative g of open cells included, +inf
+ *                where a cell was never reached.  Entries past H * W are not written.
+ * There is NO overflow status: a neighbour pushes a cell only when it closes, and closes once, so a cell never holds more than
+ * `connectivity` entries; the workspace has room for exactly that.
+ * BUILD-DEFINED, per row, touching only that row: T2D_GRID_INVALID (g +inf, nothing closed, no parent over H * W, no path, 0
+ * iterations) where H or W is not positive or H * W is above max_cells (then nothing of g / closed / parent is written), where
+ * source or target is out of range or an obstacle, where a weight is negative, where h of a cell of the grid is NaN or -inf
+ * or heuristic_scale * h is NaN (0 * inf), where htarget is not finite (built-in kinds), where heuristic_scale is negative or
+ * not finite (every row).  +inf in a table is legal: such entries order by cell.  source == target is searched like any
+ * query: the first pop finds it (path of one cell, 0 iterations, 1 closed cell); AStar.plan answers it before any launch.
+ * T2D_ERR_GEOMETRY, nothing launched: max_cells above T2D_GRID_MAX_CELLS (one fp64 key, a closed bit and a counter byte per
+ * cell in LDS: 36.5 KiB at the cap).  T2D_ERR_INVALID, nothing launched: n < 0, max_cells < 1, max_path < 0, another
+ * connectivity, a multiplier that is negative or not finite, an unknown heuristic_kind, cell_size not in 1e-150 .. 1e150, an
+ * origin that is not finite, a null or misaligned pointer (path_dev may be NULL when max_path is 0), a workspace smaller than
+ * t2d_grid_astar_workspace_bytes (which returns -1 for arguments out of range).                                                */
+#define T2D_GRID_MAX_ITER 5
+#define T2D_ASTAR_H_ZERO 0
+#define T2D_ASTAR_H_EUCLIDEAN 1
+#define T2D_ASTAR_H_MANHATTAN 2
+#define T2D_ASTAR_H_OCTILE 3
+#define T2D_ASTAR_H_TABLE 4
+int64_t t2d_grid_astar_workspace_bytes(int32_t n, int32_t max_cells, int32_t connectivity);
+int t2d_grid_astar(int32_t device_id, int32_t n, const double* weight_dev, const int32_t* hw_dev, const int32_t* source_dev,
+                   const int32_t* target_dev, int32_t max_cells, int32_t connectivity, double diagonal_cost_multiplier,
+                   int32_t heuristic_kind, const double* htarget_dev, const double* h_dev, double heuristic_scale, int32_t max_iter,
+                   int32_t max_path, double cell_size, double origin_x, double origin_y, void* workspace_dev, int64_t workspace_bytes,
+                   int32_t* path_dev, int32_t* path_len_dev, double* path_xy_dev, int32_t* status_dev, int32_t* iterations_dev,
+                   int32_t* expanded_dev, double* g_dev, uint8_t* closed_dev, int32_t* parent_dev, void* hip_stream);
 
 /* Hybrid A* on the device -- search/hybrid_a_star.py: HybridAStar.plan (:58-172) for n independent queries in ONE launch,
  * asynchronous on hip_stream, no pool (tests/hybrid_astar_ref.py).  One wave runs one query: the pops are the

@@ -153,6 +153,9 @@ SYMBOLS = {
     "t2d_planview_routes": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "t2d_polyline_routes": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "t2d_grid_dijkstra": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32] + [_vp] * 6),
+    "t2d_grid_astar_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "t2d_grid_astar": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp,
+                                 C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, C.c_int64] + [_vp] * 10),
     "t2d_hybrid_astar_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "t2d_hybrid_astar": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64] + [_vp] * 6),

@@ -89,6 +89,9 @@ PROFILE_PLANVIEW_ROUTES = 19
 # Grid shortest paths (t2d_grid_dijkstra): the status of a row, the cap on the cells of one grid (two fp64 planes in LDS)
 GRID_FOUND, GRID_NO_PATH, GRID_TRUNCATED, GRID_INVALID, GRID_FIELD_ONLY = range(5)
 GRID_MAX_CELLS = 4096
+# Grid A* (t2d_grid_astar): the status it adds to GRID_*, the heuristic kinds of a launch
+GRID_MAX_ITER = 5
+ASTAR_H_ZERO, ASTAR_H_EUCLIDEAN, ASTAR_H_MANHATTAN, ASTAR_H_OCTILE, ASTAR_H_TABLE = range(5)
 # Hybrid A* (t2d_hybrid_astar): the status of a row; the caps of one query: open entries (LDS), x_cells * y_cells of its cost grid
 # (16 headings of 2 bytes each in the workspace), steering angles
 HYBRID_FOUND, HYBRID_NO_PATH, HYBRID_MAX_ITER, HYBRID_TRUNCATED, HYBRID_OVERFLOW, HYBRID_INVALID = range(6)

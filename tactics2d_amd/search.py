@@ -38,8 +38,21 @@ the same obstacle grids and with the same collision checker and streams of draws
 
 The kernel equals tests/prm_ref.py bit for bit, and that makes the reference's decisions when the reference is fed the same draws.
 
-A* (`a_star.py`: serial, and on these grids `cost_to_go` already gives its cost), D* (`d_star.py`: a serial replanner) and MCTS
-(`mcts.py`: its model is Python callables) remain out of this package.  There is no CPU fallback.
+Grid A* on the device: the reference's `tactics2d.search.AStar` over the same graph, for n queries in ONE launch of t2d_grid_astar
+ -- the goal-directed search that stops at the target, with the reference's heap order, closed set, stale pops and
+max_iter, a heuristic per launch (zero, euclidean, manhattan, octile, or a table per cell) and its weight:
+
+    out = AStar.plan_batch(weight_grids, sources, targets, heuristic="euclidean", heuristic_scale=1.0)   # out.path, out.path_xy, out.iterations, ...
+    xy = AStar.plan(start, target, boundary, weight_grid, euclidean_heuristic, grid_resolution)   # one query with the reference's signature
+    pool.polyline_routes(out.path_xy, out.path_len)                             # the planned paths as the routes traffic follows
+
+A* is NOT Dijkstra on these grids: the Euclidean heuristic is inadmissible wherever a cell costs less than 1, so its path can
+differ from `Dijkstra.plan`'s and cost more, and its max_iter counts the stale entries its heap pops.  The kernel equals
+tests/astar_ref.py bit for bit; that specification equals the reference on its recorded fixture with tolerance 0.
+
+D* (`d_star.py`: `DStar.plan` is D* Lite run once with km = 0 and the reference has no call that replans; its answer is a shortest
+path, which `cost_to_go` gives) and MCTS (`mcts.py`: its model is Python callables) remain out of this package.  There is no CPU
+fallback.
 """
 import math
 
@@ -52,6 +65,7 @@ from .interpolator import _is_tensor, _stream_of
 SQRT2 = 1.4142135623730951   # grid_to_csr's default diagonal_cost_multiplier
 FOUND, NO_PATH, TRUNCATED, INVALID, FIELD_ONLY = L.GRID_FOUND, L.GRID_NO_PATH, L.GRID_TRUNCATED, L.GRID_INVALID, L.GRID_FIELD_ONLY
 MAX_CELLS = L.GRID_MAX_CELLS
+MAX_ITER = L.GRID_MAX_ITER   # (t2d_grid_astar only)
 
 
 class GridPaths:
@@ -209,6 +223,248 @@ def world_path(cells, width, boundary, grid_resolution):
     path[:, 0] = path[:, 0] * grid_resolution + boundary[0]
     path[:, 1] = path[:, 1] * grid_resolution + boundary[2]
     return path
+
+
+# ---- grid A* -------------------------------------------------------------------------------------------------------------------------
+def zero_heuristic(a, b):
+    """h = 0 (A* becomes Dijkstra's search with A*'s bookkeeping).  A marker for `heuristic_fn`: T2D_ASTAR_H_ZERO on the device."""
+    return 0.0
+
+
+def euclidean_heuristic(a, b):
+    """sqrt(dx * dx + dy * dy), dx = a[0] - b[0], dy = a[1] - b[1]: euclidean_heuristic of the reference's tests/test_search.py.  A
+    marker for `heuristic_fn` (T2D_ASTAR_H_EUCLIDEAN on the device) and, called, the same formula on the host."""
+    dx, dy = float(a[0]) - float(b[0]), float(a[1]) - float(b[1])
+    return math.sqrt(dx * dx + dy * dy)
+
+
+def manhattan_heuristic(a, b):
+    """|dx| + |dy|.  A marker for `heuristic_fn` (T2D_ASTAR_H_MANHATTAN) and the same formula on the host."""
+    return abs(float(a[0]) - float(b[0])) + abs(float(a[1]) - float(b[1]))
+
+
+def octile_heuristic(a, b, diagonal_cost_multiplier=SQRT2):
+    """hi + (diagonal_cost_multiplier - 1.0) * lo, hi / lo the larger / smaller of |dx|, |dy|.  A marker for `heuristic_fn`
+    (T2D_ASTAR_H_OCTILE, with the launch's multiplier) and the same formula on the host."""
+    ax, ay = abs(float(a[0]) - float(b[0])), abs(float(a[1]) - float(b[1]))
+    hi, lo = (ax, ay) if ax > ay else (ay, ax)
+    return hi + (float(diagonal_cost_multiplier) - 1.0) * lo
+
+
+ASTAR_KINDS = {"zero": L.ASTAR_H_ZERO, "euclidean": L.ASTAR_H_EUCLIDEAN, "manhattan": L.ASTAR_H_MANHATTAN, "octile": L.ASTAR_H_OCTILE,
+               "table": L.ASTAR_H_TABLE}
+_ASTAR_MARKERS = ((zero_heuristic, L.ASTAR_H_ZERO), (euclidean_heuristic, L.ASTAR_H_EUCLIDEAN), (manhattan_heuristic, L.ASTAR_H_MANHATTAN),
+                  (octile_heuristic, L.ASTAR_H_OCTILE))
+
+
+def _marker_kind(fn):
+    """ASTAR_H_* of a marker, None for any other object (by identity: a callable need not be hashable)"""
+    return next((kind for marker, kind in _ASTAR_MARKERS if fn is marker), None)
+
+
+class AStarPaths:
+    """What astar_plan_batch returns: device tensors, one row per query.  path int32 [n, max_path] (cells row * W + col from source
+    to target, -1 past the end), path_xy float64 [n, max_path, 2] (origin + (col, row) * cell_size, NaN past the end: what
+    polyline_routes takes), path_len int32 [n] (the FULL length; > max_path: TRUNCATED; 0 without a path), status int32 [n] (FOUND,
+    NO_PATH, MAX_ITER, TRUNCATED, INVALID), iterations int32 [n] (the reference's i when it returns), expanded int32 [n] (closed
+    cells), hw int32 [n, 2]; with want_state the search's state at termination, else None: g float64 [n, H_max * W_max] (tentative
+    values of open cells included, +inf where never reached), closed uint8 and parent int32 (came_from, -1: none) of the same
+    shape -- grid e is the first hw[e, 0] * hw[e, 1] entries of its flat row, the rest is not written."""
+
+    def __init__(self, path, path_xy, path_len, status, iterations, expanded, hw, g=None, closed=None, parent=None):
+        self.path, self.path_xy, self.path_len, self.status, self.iterations, self.expanded = path, path_xy, path_len, status, iterations, expanded
+        self.hw, self.g, self.closed, self.parent = hw, g, closed, parent
+
+
+def astar_plan_batch(weight_grids, sources, targets, heuristic="euclidean", heuristic_targets=None, heuristic_table=None,
+                     heuristic_scale=1.0, hw=None, connectivity=4, diagonal_cost_multiplier=SQRT2, max_iter=100000, max_path=None,
+                     cell_size=1.0, origin=(0.0, 0.0), want_state=False, device_id=0, stream=None):
+    """t2d_grid_astar: n grid A* queries in one launch, asynchronous on `stream`.  weight_grids, hw, sources, targets, connectivity,
+    diagonal_cost_multiplier, max_path: as plan_batch takes them (a target is required).  heuristic: "zero", "euclidean",
+    "manhattan", "octile", "table", one of the markers (search.euclidean_heuristic, ...) or ASTAR_H_*, one per launch.
+    heuristic_targets float64 [n, 2]: the point (hx, hy) in cell units a built-in heuristic measures the cell (x, y) = (col, row)
+    against; None: the target cell's own (col, row).  heuristic_table float64 [n, H_max, W_max] (or [n, H_max * W_max]; the rows in
+    the grids' layout): h of every cell, with heuristic="table" -- a Python callable evaluated on the host, or a cost_to_go field;
+    +inf is legal, NaN and -inf make the row INVALID.  f = g + heuristic_scale * h.  cell_size, origin: path_xy only
+    (OccupancyGrid.planner_kwargs() gives them).  want_state: also g, closed and parent.  Returns AStarPaths.  ValueError: an
+    unknown heuristic, a table without "table" or "table" without one, another connectivity, a multiplier that is negative or not
+    finite, a cell_size that is not positive and finite, shapes that disagree; GeometryError: H_max * W_max above MAX_CELLS."""
+    import torch
+    if not _is_tensor(weight_grids):
+        weight_grids = np.asarray(weight_grids, np.float64)
+    shape = tuple(weight_grids.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1] * shape[2] < 1:
+        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    mult = float(diagonal_cost_multiplier)
+    if not math.isfinite(mult) or mult < 0:
+        raise ValueError(f"diagonal_cost_multiplier must be finite and not negative, got {diagonal_cost_multiplier}")
+    kind = _marker_kind(heuristic) if callable(heuristic) else ASTAR_KINDS.get(heuristic, heuristic)
+    if isinstance(kind, bool) or kind not in ASTAR_KINDS.values():
+        raise ValueError(f"heuristic must be one of {sorted(ASTAR_KINDS)}, a marker of this module or search.ASTAR_H_*, got {heuristic!r}")
+    if (kind == L.ASTAR_H_TABLE) != (heuristic_table is not None):
+        raise ValueError('heuristic="table" and heuristic_table go together')
+    cell_size = float(cell_size)
+    if not (1e-150 <= cell_size <= 1e150):
+        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
+        raise ValueError(f"origin must be two finite numbers, got {origin}")
+    n, h_max, w_max = shape
+    stride = h_max * w_max
+    hw_host = None if _is_tensor(hw) else (np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else np.asarray(hw, np.int32).reshape(n, 2))
+    if not _is_tensor(sources):
+        sources = _cells(sources, n, hw_host)
+    if not _is_tensor(targets):
+        targets = _cells(targets, n, hw_host)
+    max_path = stride if max_path is None else int(max_path)
+    if max_path < 0:
+        raise ValueError(f"max_path must not be negative, got {max_path}")
+    max_iter = max(min(int(max_iter), 2 ** 31 - 1), 0)
+    lib = _ffi.lib()
+    dev, st = _stream_of(device_id, stream)
+    with torch.cuda.stream(st):
+        if _is_tensor(weight_grids):
+            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
+        else:
+            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
+        hw_t = _i32(hw_host if hw_host is not None else hw, dev, (n, 2))
+        src, tgt = _i32(sources, dev, (n,)), _i32(targets, dev, (n,))
+        table = _f64(heuristic_table, dev, (n, stride)) if kind == L.ASTAR_H_TABLE else None
+        if kind in (L.ASTAR_H_ZERO, L.ASTAR_H_TABLE):
+            point = None
+        elif heuristic_targets is None:   # the target cell's own (col, row)
+            width = hw_t[:, 1].clamp(min=1)
+            point = torch.stack((tgt % width, torch.div(tgt, width, rounding_mode="floor")), 1).to(torch.float64).contiguous()
+        else:
+            point = _f64(heuristic_targets, dev, (n, 2))
+        need = int(lib.t2d_grid_astar_workspace_bytes(n, min(stride, MAX_CELLS), connectivity))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        path = torch.empty((n, max_path), dtype=torch.int32, device=dev)
+        path_xy = torch.empty((n, max_path, 2), dtype=torch.float64, device=dev)
+        path_len, status, iterations, expanded = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+        g = torch.empty((n, stride), dtype=torch.float64, device=dev) if want_state else None
+        closed = torch.empty((n, stride), dtype=torch.uint8, device=dev) if want_state else None
+        parent = torch.empty((n, stride), dtype=torch.int32, device=dev) if want_state else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        if n or stride > MAX_CELLS:   # (an empty batch has no memory to point at and nothing to launch; the cap is refused by name)
+            _ffi.check(lib.t2d_grid_astar(device_id, n, w.data_ptr(), hw_t.data_ptr(), src.data_ptr(), tgt.data_ptr(), stride, connectivity,
+                                          mult, kind, ptr(point), ptr(table), float(heuristic_scale), max_iter, max_path, cell_size,
+                                          float(origin[0]), float(origin[1]), ws.data_ptr(), need, ptr(path), path_len.data_ptr(),
+                                          ptr(path_xy), status.data_ptr(), iterations.data_ptr(), expanded.data_ptr(), ptr(g), ptr(closed),
+                                          ptr(parent), st.cuda_stream), None, lib)
+    out = AStarPaths(path, path_xy, path_len, status, iterations, expanded, hw_t, g, closed, parent)
+    out._inputs = (w, src, tgt, point, table, ws)   # (kept alive with the result)
+    return out
+
+
+def _astar_one(who, grid, start_idx, target_idx, heuristic_fn, point, per_cell, max_iter, connectivity, mult, device_id):
+    """one query for AStar.plan / plan_graph -> (cells of the path or None, cost).  A marker runs its kind on the device against
+    `point`; any other callable is evaluated once per cell on the host (per_cell(cell) -> h) and launched as a table."""
+    if not callable(heuristic_fn):
+        raise TypeError(f"{who}: heuristic_fn must be callable, got {heuristic_fn!r}")
+    n = grid.size
+    kw = dict(connectivity=connectivity, diagonal_cost_multiplier=mult, max_iter=max_iter, max_path=n, want_state=True, device_id=device_id)
+    if _marker_kind(heuristic_fn) is not None:
+        out = astar_plan_batch(grid[None], np.int32([start_idx]), np.int32([target_idx]), heuristic_fn, np.float64([point]), **kw)
+    else:
+        table = np.array([float(per_cell(v)) for v in range(n)], np.float64)
+        if np.isnan(table).any() or (table == -np.inf).any():
+            raise ValueError(f"{who}: heuristic_fn returned NaN or -inf for cell {int(np.flatnonzero(np.isnan(table) | (table == -np.inf))[0])}")
+        out = astar_plan_batch(grid[None], np.int32([start_idx]), np.int32([target_idx]), "table", heuristic_table=table[None], **kw)
+    status = int(out.status[0])
+    if status == INVALID:
+        flat = grid.reshape(-1)
+        if all(math.isfinite(flat[i]) for i in (start_idx, target_idx)):   # (an obstacle at either end has no edges in the reference's graph)
+            raise ValueError(f"{who}: the weight grid holds a negative weight")
+        return None, math.inf
+    if status != FOUND:   # (NO_PATH, or MAX_ITER: the reference returns None for both)
+        return None, math.inf
+    return out.path[0, :int(out.path_len[0])].cpu().numpy(), float(out.g[0, target_idx])
+
+
+class AStar:
+    """AStar (search/a_star.py) over a weight grid."""
+
+    plan_batch = staticmethod(astar_plan_batch)
+
+    @staticmethod
+    def plan(start, target, boundary, weight_grid, heuristic_fn, grid_resolution, max_iter=100000, callback=None, connectivity=4,
+             diagonal_cost_multiplier=SQRT2, device_id=0):
+        """AStar.plan (a_star.py:23-276) with the reference's argument order and the weight grid [H, W] in place of grid_to_csr's
+        graph of it: start / target [x, y] in world coordinates, boundary [x_min, x_max, y_min, y_max].  heuristic_fn: one of the
+        markers search.euclidean_heuristic, manhattan_heuristic, octile_heuristic, zero_heuristic -- evaluated on the device against
+        the UNROUNDED rasterized target, as the reference calls it --, or any callable heuristic_fn([x, y], target_rasterized): it
+        is evaluated ONCE PER CELL on the host before the launch, so it must be a pure function of the cell (the reference calls
+        it at every relaxation).  callback must be None (TypeError otherwise: a Python callable cannot run in a kernel).  Returns
+        the reference's integer array (see world_path), None when there is no path and when max_iter stopped the search, [[x, y]]
+        of `start` when start and target fall into one cell.  The reference's ValueErrors are raised with its messages.
+        Synchronous: one launch, one download."""
+        if callback is not None:
+            raise TypeError(f"AStar.plan runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
+        x_min, x_max, y_min, y_max = boundary
+        if grid_resolution <= 0:
+            raise ValueError(f"grid_resolution must be positive, got {grid_resolution}")
+        if x_min >= x_max or y_min >= y_max:
+            raise ValueError(f"Invalid boundary: {boundary}. Must satisfy x_min < x_max and y_min < y_max")
+        eps = grid_resolution * 1e-9
+        if not (x_min - eps <= start[0] < x_max + eps and y_min - eps <= start[1] < y_max + eps):
+            raise ValueError(f"start coordinate {start} is outside boundary {boundary}")
+        if not (x_min - eps <= target[0] < x_max + eps and y_min - eps <= target[1] < y_max + eps):
+            raise ValueError(f"target coordinate {target} is outside boundary {boundary}")
+        width = int((x_max - x_min) / grid_resolution)
+        height = int((y_max - y_min) / grid_resolution)
+        grid = np.asarray(weight_grid, np.float64)
+        if grid.ndim != 2:
+            raise ValueError(f"weight_grid must be 2D array, got shape {grid.shape}")
+        N = grid.size
+        if not math.isclose(width * height, N, rel_tol=1e-9):
+            raise ValueError(f"width*height={width*height} does not equal to N={N}. "
+                             f"Graph dimensions don't match the calculated grid size.")
+        if tuple(grid.shape) != (height, width):
+            raise ValueError(f"weight_grid has shape {grid.shape}, the boundary and resolution give ({height}, {width})")
+        start_rasterized = [(start[0] - x_min) / grid_resolution, (start[1] - y_min) / grid_resolution]
+        target_rasterized = [(target[0] - x_min) / grid_resolution, (target[1] - y_min) / grid_resolution]
+        start_x = max(0, min(int(round(start_rasterized[0])), width - 1))
+        start_y = max(0, min(int(round(start_rasterized[1])), height - 1))
+        target_x = max(0, min(int(round(target_rasterized[0])), width - 1))
+        target_y = max(0, min(int(round(target_rasterized[1])), height - 1))
+        start_idx = start_y * width + start_x
+        target_idx = target_y * width + target_x
+        if not (0 <= start_idx < N):
+            raise ValueError(f"start_idx {start_idx} out of bounds [0, {N})")
+        if not (0 <= target_idx < N):
+            raise ValueError(f"target_idx {target_idx} out of bounds [0, {N})")
+        if start_idx == target_idx:
+            return np.array([[start[0], start[1]]])
+        cells, _ = _astar_one("AStar.plan", grid, start_idx, target_idx, heuristic_fn, target_rasterized,
+                              lambda v: heuristic_fn([v % width, v // width], target_rasterized), max_iter, connectivity,
+                              diagonal_cost_multiplier, device_id)
+        return None if cells is None else world_path(cells, width, boundary, grid_resolution)
+
+    @staticmethod
+    def plan_graph(start_idx, target_idx, weight_grid, heuristic_fn, max_iter=100000, connectivity=4, diagonal_cost_multiplier=SQRT2,
+                   device_id=0):
+        """AStar.plan_graph (a_star.py:279-404) over the weight grid [H, W] in place of its graph: cells row * W + col.  heuristic_fn:
+        a marker (measured against the target cell's (col, row)) or any callable heuristic_fn(cell, target_cell), evaluated once
+        per cell on the host: a pure function of the cell.  Returns (index_path, cost) -- ([start_idx], 0.0) for one cell,
+        ([], inf) when the search fails or max_iter stops it.  The reference's ValueErrors for indices out of bounds."""
+        grid = np.asarray(weight_grid, np.float64)
+        if grid.ndim != 2:
+            raise ValueError(f"weight_grid must be 2D array, got shape {grid.shape}")
+        n_nodes, width = grid.size, grid.shape[1]
+        if not (0 <= start_idx < n_nodes):
+            raise ValueError(f"start_idx {start_idx} out of bounds [0, {n_nodes})")
+        if not (0 <= target_idx < n_nodes):
+            raise ValueError(f"target_idx {target_idx} out of bounds [0, {n_nodes})")
+        if start_idx == target_idx:
+            return [start_idx], 0.0
+        cells, cost = _astar_one("AStar.plan_graph", grid, int(start_idx), int(target_idx), heuristic_fn,
+                                 [float(target_idx % width), float(target_idx // width)], lambda v: heuristic_fn(v, target_idx), max_iter,
+                                 connectivity, diagonal_cost_multiplier, device_id)
+        return ([], math.inf) if cells is None else ([int(c) for c in cells], cost)
 
 
 # ---- hybrid A* ---------------------------------------------------------------------------------------------------------------------
