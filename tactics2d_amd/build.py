@@ -19,7 +19,7 @@ SOURCES = ["t2d_api.hip", "t2d_integrate.hip", "t2d_collide.hip", "t2d_lidar.hip
            "t2d_occupancy.hip", "t2d_prm.hip", "t2d_astar.hip"]
 # test / measurement hooks (include/t2d_debug.h): compiled into libt2d_hip_debug.so only
 DEBUG_SOURCES = ["t2d_loop.hip", "t2d_math_probe.hip", "t2d_math_probe_table.hip", "t2d_geom_probe.hip"]
-HEADERS = ["t2d_math.h", "t2d_pool.h", "t2d_devbuf.h", "t2d_host.h", "t2d_step_plan.h", "t2d_integrate_dev.h", "t2d_geom_dev.h", "t2d_idm_dev.h", "t2d_scene_dev.h", "t2d_verify_dev.h", "t2d_route_dev.h", "t2d_scripted_dev.h", "t2d_route_write_dev.h", "t2d_track_dev.h", "t2d_rng.h", "t2d_rs_dev.h", "t2d_curve_dev.h", "t2d_spline_dev.h", "t2d_road_dev.h", "t2d_fresnel_tab.h", "t2d_gridsearch_dev.h", "t2d_hybrid_dev.h", "t2d_sample_dev.h", "t2d_prm_dev.h", "t2d_astar_dev.h",
+HEADERS = ["t2d_math.h", "t2d_pool.h", "t2d_devbuf.h", "t2d_host.h", "t2d_step_plan.h", "t2d_integrate_dev.h", "t2d_geom_dev.h", "t2d_idm_dev.h", "t2d_scene_dev.h", "t2d_verify_dev.h", "t2d_route_dev.h", "t2d_scripted_dev.h", "t2d_route_write_dev.h", "t2d_track_dev.h", "t2d_rng.h", "t2d_rs_dev.h", "t2d_curve_dev.h", "t2d_spline_dev.h", "t2d_road_dev.h", "t2d_fresnel_tab.h", "t2d_gridsearch_dev.h", "t2d_gridplan_dev.h", "t2d_plan_host.h", "t2d_hybrid_dev.h", "t2d_sample_dev.h", "t2d_prm_dev.h", "t2d_astar_dev.h",
            os.path.join("..", "..", "include", "t2d.h")]
 DEBUG_HEADERS = [os.path.join("..", "..", "include", "t2d_debug.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

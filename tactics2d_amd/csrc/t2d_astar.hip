@@ -5,8 +5,7 @@
 #include <string>
 
 #include "t2d_astar_dev.h"
-#include "t2d_hybrid_dev.h"
-#include "t2d_host.h"
+#include "t2d_plan_host.h"
 
 namespace t2d {
 
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(64) void grid_astar_kernel(AStarArgs a) {
         // ---- pop: the smallest (f, cell) ----
         double f = bf;
         int c = bc, unused = 0;
-        hybrid_wave_argmin(f, c, unused);
+        wave_argmin(f, c, unused);
         if (c == kAStarNoCell) {
             status = GRID_NO_PATH;
             break;
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(64) void grid_astar_kernel(AStarArgs a) {
                 sv = nan;
             }
             for (int k = 0; k < total; ++k) {
-                const double v = hybrid_bcast(sv, k);
+                const double v = wave_bcast(sv, k);
                 if (v == v && !(key <= v)) key = v;
             }
         }
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(64) void grid_astar_kernel(AStarArgs a) {
         // ---- the block minima: the pushes into their blocks, then the popped cell's block from its keys ----
         for (unsigned long long m = __ballot(pushed); m; m &= m - 1) {
             const int d = __builtin_ctzll(m);
-            const double df = hybrid_bcast(pf, d);
+            const double df = wave_bcast(pf, d);
             const int dn = __builtin_amdgcn_readlane(nb, d);
             if (lane == (dn >> 6) && (df < bf || (df == bf && dn < bc))) {
                 bf = df;
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(64) void grid_astar_kernel(AStarArgs a) {
             double kv = s_key[v];
             int kc = kv == kv ? v : kAStarNoCell;
             if (kv != kv) kv = inf;
-            hybrid_wave_argmin(kv, kc, unused);
+            wave_argmin(kv, kc, unused);
             if (lane == (c >> 6)) {
                 bf = kv;
                 bc = kc;
@@ -240,63 +239,29 @@ extern "C" int t2d_grid_astar(int32_t device_id, int32_t n, const double* weight
                               int32_t* iterations_dev, int32_t* expanded_dev, double* g_dev, uint8_t* closed_dev, int32_t* parent_dev,
                               void* hip_stream) {
     using namespace t2d;
-    const auto misaligned = [](const void* p, uintptr_t mask) { return !p || (reinterpret_cast<uintptr_t>(p) & mask); };
-    const auto odd = [](const void* p, uintptr_t mask) { return p && (reinterpret_cast<uintptr_t>(p) & mask); };
+    host::PlanEntry entry("t2d_grid_astar");
     if (n < 0 || max_cells < 1 || max_path < 0 || (connectivity != 4 && connectivity != 8))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: n >= 0, max_cells >= 1, max_path >= 0 and connectivity 4 or 8");
+        return entry.invalid("n >= 0, max_cells >= 1, max_path >= 0 and connectivity 4 or 8");
     if (!std::isfinite(diagonal_cost_multiplier) || diagonal_cost_multiplier < 0.0)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: diagonal_cost_multiplier must be finite and not negative");
-    if (heuristic_kind < T2D_ASTAR_H_ZERO || heuristic_kind > T2D_ASTAR_H_TABLE)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: heuristic_kind must be one of T2D_ASTAR_H_*");
-    if (!(cell_size >= kHybridStepMin && cell_size <= kHybridStepMax) || !(std::fabs(origin_x) <= kHybridXYLimit) ||
-        !(std::fabs(origin_y) <= kHybridXYLimit))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: cell_size must be positive (1e-150 .. 1e150), the origin finite");
+        return entry.invalid("diagonal_cost_multiplier must be finite and not negative");
+    if (heuristic_kind < T2D_ASTAR_H_ZERO || heuristic_kind > T2D_ASTAR_H_TABLE) return entry.invalid("heuristic_kind must be one of T2D_ASTAR_H_*");
+    if (int rc = entry.cell_origin(cell_size, origin_x, origin_y)) return rc;
     const bool table = heuristic_kind == T2D_ASTAR_H_TABLE, point = !table && heuristic_kind != T2D_ASTAR_H_ZERO;
-    if (misaligned(weight_dev, 7u) || misaligned(hw_dev, 3u) || misaligned(source_dev, 3u) || misaligned(target_dev, 3u) ||
-        misaligned(path_len_dev, 3u) || misaligned(status_dev, 3u) || misaligned(iterations_dev, 3u) || misaligned(expanded_dev, 3u) ||
-        (max_path > 0 && misaligned(path_dev, 3u)) || odd(path_xy_dev, 7u) || odd(g_dev, 7u) || odd(parent_dev, 3u) ||
-        (point && misaligned(htarget_dev, 7u)) || (table && misaligned(h_dev, 7u)) || misaligned(workspace_dev, 15u))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: null or misaligned device pointer (the workspace: 16 bytes)");
-    if (max_cells > T2D_GRID_MAX_CELLS)
-        return host::fail(nullptr, T2D_ERR_GEOMETRY, "t2d_grid_astar: a grid of " + std::to_string(max_cells) +
-                                                         " cells is above T2D_GRID_MAX_CELLS = " + std::to_string(T2D_GRID_MAX_CELLS) +
-                                                         " (one fp64 key per cell in LDS)");
-    const int64_t need = t2d_grid_astar_workspace_bytes(n, max_cells, connectivity);
-    if (workspace_bytes < need)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_astar: the workspace has " + std::to_string(workspace_bytes) +
-                                                        " bytes, t2d_grid_astar_workspace_bytes asks for " + std::to_string(need));
-    if (n == 0) return T2D_OK;
-    if (hipSetDevice(device_id) != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, "t2d_grid_astar: hipSetDevice failed");
-    AStarArgs a;
-    a.weight = weight_dev;
-    a.hw = hw_dev;
-    a.source = source_dev;
-    a.target = target_dev;
-    a.htarget = point ? htarget_dev : nullptr;
-    a.table = table ? h_dev : nullptr;
-    a.mult = diagonal_cost_multiplier;
-    a.scale = heuristic_scale;
-    a.cell = cell_size;
-    a.ox = origin_x;
-    a.oy = origin_y;
-    a.stride = max_cells;
-    a.conn = connectivity;
-    a.kind = heuristic_kind;
-    a.max_iter = max_iter;
-    a.max_path = max_path;
-    a.ws = static_cast<unsigned char*>(workspace_dev);
-    a.ws_row = astar_row_bytes(max_cells, connectivity);
-    a.path = path_dev;
-    a.path_len = path_len_dev;
-    a.path_xy = max_path > 0 ? path_xy_dev : nullptr;
-    a.status = status_dev;
-    a.iterations = iterations_dev;
-    a.expanded = expanded_dev;
-    a.g = g_dev;
-    a.closed = closed_dev;
-    a.parent = parent_dev;
-    hipLaunchKernelGGL(grid_astar_kernel, dim3((unsigned)n), dim3(64), (size_t)astar_lds_bytes(max_cells), (hipStream_t)hip_stream, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, std::string("t2d_grid_astar: ") + hipGetErrorString(err));
-    return T2D_OK;
+    entry.required(7u, weight_dev).required(3u, hw_dev, source_dev, target_dev, path_len_dev, status_dev, iterations_dev, expanded_dev);
+    entry.optional(7u, path_xy_dev, g_dev).optional(3u, parent_dev);
+    if (max_path > 0) entry.required(3u, path_dev);
+    if (point) entry.required(7u, htarget_dev);
+    if (table) entry.required(7u, h_dev);
+    if (int rc = entry.workspace(workspace_dev).pointers()) return rc;
+    if (int rc = entry.grid_cap(max_cells, "one fp64 key per cell in LDS")) return rc;
+    if (int rc = entry.workspace_bytes(workspace_bytes, t2d_grid_astar_workspace_bytes(n, max_cells, connectivity))) return rc;
+    const AStarArgs a{weight_dev, hw_dev, source_dev, target_dev, point ? htarget_dev : nullptr, table ? h_dev : nullptr,
+                      diagonal_cost_multiplier, heuristic_scale, cell_size, origin_x, origin_y,
+                      max_cells, connectivity, heuristic_kind, max_iter, max_path,
+                      static_cast<unsigned char*>(workspace_dev), astar_row_bytes(max_cells, connectivity),
+                      path_dev, path_len_dev, max_path > 0 ? path_xy_dev : nullptr, status_dev, iterations_dev, expanded_dev,
+                      g_dev, closed_dev, parent_dev};
+    return entry.launch(device_id, n, [&] {
+        hipLaunchKernelGGL(grid_astar_kernel, dim3((unsigned)n), dim3(64), (size_t)astar_lds_bytes(max_cells), (hipStream_t)hip_stream, a);
+    });
 }

@@ -5,7 +5,7 @@
 #include <string>
 
 #include "t2d_gridsearch_dev.h"
-#include "t2d_host.h"
+#include "t2d_plan_host.h"
 
 namespace t2d {
 
@@ -157,29 +157,22 @@ extern "C" int t2d_grid_dijkstra(int32_t device_id, int32_t n, const double* wei
                                  int32_t max_path, double* g_dev, int32_t* path_dev, int32_t* path_len_dev, int32_t* status_dev,
                                  int32_t* sweeps_dev, void* hip_stream) {
     using namespace t2d;
-    const auto misaligned = [](const void* p, uintptr_t mask) { return !p || (reinterpret_cast<uintptr_t>(p) & mask); };
+    host::PlanEntry entry("t2d_grid_dijkstra");
     if (n < 0 || max_cells < 1 || max_path < 0 || (connectivity != 4 && connectivity != 8))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_dijkstra: n >= 0, max_cells >= 1, max_path >= 0 and connectivity 4 or 8");
+        return entry.invalid("n >= 0, max_cells >= 1, max_path >= 0 and connectivity 4 or 8");
     if (!std::isfinite(diagonal_cost_multiplier) || diagonal_cost_multiplier < 0.0)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_dijkstra: diagonal_cost_multiplier must be finite and not negative");
-    if (misaligned(weight_dev, 7u) || misaligned(g_dev, 7u) || misaligned(hw_dev, 3u) || misaligned(source_dev, 3u) ||
-        misaligned(target_dev, 3u) || misaligned(path_len_dev, 3u) || misaligned(status_dev, 3u) || misaligned(sweeps_dev, 3u) ||
-        (max_path > 0 && misaligned(path_dev, 3u)))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_grid_dijkstra: null or misaligned device pointer");
-    if (max_cells > T2D_GRID_MAX_CELLS)
-        return host::fail(nullptr, T2D_ERR_GEOMETRY, "t2d_grid_dijkstra: a grid of " + std::to_string(max_cells) +
-                                                         " cells is above T2D_GRID_MAX_CELLS = " + std::to_string(T2D_GRID_MAX_CELLS) +
-                                                         " (two fp64 planes in LDS)");
-    if (n == 0) return T2D_OK;
-    if (hipSetDevice(device_id) != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, "t2d_grid_dijkstra: hipSetDevice failed");
+        return entry.invalid("diagonal_cost_multiplier must be finite and not negative");
+    entry.required(7u, weight_dev, g_dev).required(3u, hw_dev, source_dev, target_dev, path_len_dev, status_dev, sweeps_dev);
+    if (max_path > 0) entry.required(3u, path_dev);
+    if (int rc = entry.pointers()) return rc;
+    if (int rc = entry.grid_cap(max_cells, "two fp64 planes in LDS")) return rc;
     const GridArgs a{weight_dev, hw_dev, source_dev, target_dev, diagonal_cost_multiplier, max_cells, connectivity == 8, max_path,
                      g_dev, path_dev, path_len_dev, status_dev, sweeps_dev};
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (max_cells <= kGridSmallCells)
-        hipLaunchKernelGGL((grid_dijkstra_kernel<kGridSmallCells, 256>), dim3((unsigned)n), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((grid_dijkstra_kernel<kGridMaxCells, 1024>), dim3((unsigned)n), dim3(1024), 0, s, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, std::string("t2d_grid_dijkstra: ") + hipGetErrorString(err));
-    return T2D_OK;
+    return entry.launch(device_id, n, [&] {
+        hipStream_t s = (hipStream_t)hip_stream;
+        if (max_cells <= kGridSmallCells)
+            hipLaunchKernelGGL((grid_dijkstra_kernel<kGridSmallCells, 256>), dim3((unsigned)n), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((grid_dijkstra_kernel<kGridMaxCells, 1024>), dim3((unsigned)n), dim3(1024), 0, s, a);
+    });
 }

@@ -1,11 +1,10 @@
 // t2d_hybrid.hip -- the reference's hybrid A* for n independent queries in one launch (hybrid_astar_kernel).  The formulas are
 // t2d_hybrid_dev.h; what they restate is search/hybrid_a_star.py: HybridAStar.plan with the grid collision checker its tests pair
 // with it.  DESIGN.md 4.22.
-#include <cmath>
 #include <string>
 
 #include "t2d_hybrid_dev.h"
-#include "t2d_host.h"
+#include "t2d_plan_host.h"
 
 namespace t2d {
 
@@ -27,8 +26,6 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
     __shared__ double s_f[kHybridMaxOpen];
     __shared__ int s_i[kHybridMaxOpen];
     const int e = blockIdx.x, lane = threadIdx.x;
-    const double nan = __builtin_nan("");
-
     const int H = a.hw[2 * e], W = a.hw[2 * e + 1];
     const double sx = a.start[3 * e], sy = a.start[3 * e + 1], sh = a.start[3 * e + 2];
     const double tx = a.target[3 * e], ty = a.target[3 * e + 1], th = a.target[3 * e + 2];
@@ -38,12 +35,9 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
 
     int status = -1, iterations = 0, n_nodes = 0, goal = -1, x_cells = 0, y_cells = 0;
     {
-        bool bad = hybrid_bad(sx, kHybridXYLimit) || hybrid_bad(sy, kHybridXYLimit) || hybrid_bad(tx, kHybridXYLimit) ||
-                   hybrid_bad(ty, kHybridXYLimit) || hybrid_bad(x_min, kHybridXYLimit) || hybrid_bad(x_max, kHybridXYLimit) ||
-                   hybrid_bad(y_min, kHybridXYLimit) || hybrid_bad(y_max, kHybridXYLimit) || hybrid_bad(sh, kHybridAngleLimit) ||
-                   hybrid_bad(th, kHybridAngleLimit);
-        bad = bad || __ballot(hybrid_bad(my_delta, kHybridAngleLimit)) != 0ull;
-        bad = bad || x_min >= x_max || y_min >= y_max || H < 1 || W < 1 || (long long)H * (long long)W > (long long)a.stride;
+        bool bad = plan_row_bad(sx, sy, tx, ty, x_min, x_max, y_min, y_max, H, W, a.stride) || hybrid_bad_angle(sh) || hybrid_bad_angle(th);
+        bad = bad || __ballot(hybrid_bad_angle(my_delta)) != 0ull;
+        bad = bad || x_min >= x_max || y_min >= y_max;
         const double inf = __builtin_huge_val();
         const double qx = (sx - x_min) / xy_res, qy = (sy - y_min) / xy_res;
         const double cxd = __builtin_trunc((x_max - x_min) / xy_res) + 1.0, cyd = __builtin_trunc((y_max - y_min) / xy_res) + 1.0;
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
     double4* node_xyhg = reinterpret_cast<double4*>(row);
     int2* node_pd = reinterpret_cast<int2*>(row + hybrid_pd_offset(a.max_nodes));
     uint16_t* grid = reinterpret_cast<uint16_t*>(row + hybrid_grid_offset(a.max_nodes));
-    const double* weight = a.weight + (size_t)e * (size_t)a.stride;
+    const ObstacleGrid obstacles{a.weight + (size_t)e * (size_t)a.stride, H, W, a.ox, a.oy, a.cell};
 
     const auto cell_of = [&](double x, double y, double h) {
         int xi = (int)((x - x_min) / xy_res), yi = (int)((y - y_min) / xy_res);
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
                 bp = i;
             }
         }
-        hybrid_wave_argmin(bf, bi, bp);
+        wave_argmin(bf, bi, bp);
         const int idx = bi;
         ++iterations;
         --open_n;
@@ -138,26 +132,7 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
         while (todo) {
             const int s = __builtin_ctzll(todo);
             todo &= todo - 1;
-            const double px = hybrid_bcast(nx, s), py = hybrid_bcast(ny, s);
-            int c0, c1, r0, r1;
-            hybrid_range(px < x ? px : x, px > x ? px : x, a.ox, a.cell, W, c0, c1);
-            hybrid_range(py < y ? py : y, py > y ? py : y, a.oy, a.cell, H, r0, r1);
-            const int wc = c1 - c0 + 1, cnt = wc > 0 && r1 >= r0 ? wc * (r1 - r0 + 1) : 0;
-            const double half = a.cell / 2.0;
-            for (int base = 0; base < cnt; base += 64) {
-                const int j = base + lane;
-                bool hit = false;
-                if (j < cnt) {
-                    const int r = r0 + j / wc, c = c0 + j % wc;
-                    const double w = weight[r * W + c];
-                    if (w != w || w == __builtin_huge_val())
-                        hit = hybrid_slab(x, y, px, py, a.ox + (double)c * a.cell, a.oy + (double)r * a.cell, half);
-                }
-                if (__ballot(hit)) {
-                    hit_mask |= 1ull << s;
-                    break;
-                }
-            }
+            if (obstacles.wave_seg_hit(x, y, wave_bcast(nx, s), wave_bcast(ny, s), lane)) hit_mask |= 1ull << s;
         }
         alive = alive && !(hit_mask >> lane & 1ull);
         // ---- the prune against the cost grid, in the order of the primitives ----
@@ -208,11 +183,7 @@ __global__ __launch_bounds__(64) void hybrid_astar_kernel(HybridArgs a) {
             }
         }
     }
-    {
-        double* out = a.path + (size_t)e * (size_t)a.max_path * 3;
-        const int from = (len < a.max_path ? len : a.max_path) * 3;
-        for (int i = from + lane; i < a.max_path * 3; i += 64) out[i] = nan;
-    }
+    plan_path_tail<3, 64>(a.path + (size_t)e * (size_t)a.max_path * 3, len, a.max_path, lane);
     if (lane == 0) {
         a.path_len[e] = len;
         a.status[e] = status;
@@ -236,52 +207,19 @@ extern "C" int t2d_hybrid_astar(int32_t device_id, int32_t n, const double* weig
                                 int32_t* path_len_dev, int32_t* status_dev, int32_t* iterations_dev, int32_t* nodes_dev,
                                 void* hip_stream) {
     using namespace t2d;
-    const auto misaligned = [](const void* p, uintptr_t mask) { return !p || (reinterpret_cast<uintptr_t>(p) & mask); };
-    if (n < 0 || max_cells < 1 || max_path < 0 || max_nodes < 1)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: n >= 0, max_cells >= 1, max_path >= 0 and max_nodes >= 1");
-    if (n_steer < 1 || n_steer > T2D_HYBRID_MAX_STEER)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: n_steer must be 1 .. " + std::to_string(T2D_HYBRID_MAX_STEER));
-    if (!(step_size >= kHybridStepMin && step_size <= kHybridStepMax))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: step_size must be positive (1e-150 .. 1e150)");
-    if (!(cell_size >= kHybridStepMin && cell_size <= kHybridStepMax) || !(std::fabs(origin_x) <= kHybridXYLimit) ||
-        !(std::fabs(origin_y) <= kHybridXYLimit))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: cell_size must be positive (1e-150 .. 1e150), the origin finite");
-    if (misaligned(weight_dev, 7u) || misaligned(start_dev, 7u) || misaligned(target_dev, 7u) || misaligned(boundary_dev, 7u) ||
-        misaligned(delta_dev, 7u) || misaligned(hw_dev, 3u) || misaligned(path_len_dev, 3u) || misaligned(status_dev, 3u) ||
-        misaligned(iterations_dev, 3u) || misaligned(nodes_dev, 3u) || (max_path > 0 && misaligned(path_dev, 7u)) ||
-        misaligned(workspace_dev, 15u))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: null or misaligned device pointer (the workspace: 16 bytes)");
-    const int64_t need = t2d_hybrid_astar_workspace_bytes(n, max_nodes);
-    if (workspace_bytes < need)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_hybrid_astar: the workspace has " + std::to_string(workspace_bytes) +
-                                                        " bytes, t2d_hybrid_astar_workspace_bytes asks for " + std::to_string(need));
-    if (n == 0) return T2D_OK;
-    if (hipSetDevice(device_id) != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, "t2d_hybrid_astar: hipSetDevice failed");
-    HybridArgs a;
-    a.weight = weight_dev;
-    a.hw = hw_dev;
-    a.start = start_dev;
-    a.target = target_dev;
-    a.boundary = boundary_dev;
-    a.delta = delta_dev;
-    a.n_steer = n_steer;
-    a.stride = max_cells;
-    a.max_iter = max_iter;
-    a.max_nodes = max_nodes;
-    a.max_path = max_path;
-    a.step = step_size;
-    a.cell = cell_size;
-    a.ox = origin_x;
-    a.oy = origin_y;
-    a.ws = static_cast<unsigned char*>(workspace_dev);
-    a.ws_row = hybrid_row_bytes(max_nodes);
-    a.path = path_dev;
-    a.path_len = path_len_dev;
-    a.status = status_dev;
-    a.iterations = iterations_dev;
-    a.nodes = nodes_dev;
-    hipLaunchKernelGGL(hybrid_astar_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)hip_stream, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, std::string("t2d_hybrid_astar: ") + hipGetErrorString(err));
-    return T2D_OK;
+    host::PlanEntry entry("t2d_hybrid_astar");
+    if (n < 0 || max_cells < 1 || max_path < 0 || max_nodes < 1) return entry.invalid("n >= 0, max_cells >= 1, max_path >= 0 and max_nodes >= 1");
+    if (n_steer < 1 || n_steer > T2D_HYBRID_MAX_STEER) return entry.invalid("n_steer must be 1 .. " + std::to_string(T2D_HYBRID_MAX_STEER));
+    if (!(step_size >= kPlanStepMin && step_size <= kPlanStepMax)) return entry.invalid("step_size must be positive (1e-150 .. 1e150)");
+    if (int rc = entry.cell_origin(cell_size, origin_x, origin_y)) return rc;
+    entry.required(7u, weight_dev, start_dev, target_dev, boundary_dev, delta_dev);
+    entry.required(3u, hw_dev, path_len_dev, status_dev, iterations_dev, nodes_dev);
+    if (max_path > 0) entry.required(7u, path_dev);
+    if (int rc = entry.workspace(workspace_dev).pointers()) return rc;
+    if (int rc = entry.workspace_bytes(workspace_bytes, t2d_hybrid_astar_workspace_bytes(n, max_nodes))) return rc;
+    const HybridArgs a{weight_dev, hw_dev, start_dev, target_dev, boundary_dev, delta_dev,
+                       n_steer, max_cells, max_iter, max_nodes, max_path, step_size, cell_size, origin_x, origin_y,
+                       static_cast<unsigned char*>(workspace_dev), hybrid_row_bytes(max_nodes),
+                       path_dev, path_len_dev, status_dev, iterations_dev, nodes_dev};
+    return entry.launch(device_id, n, [&] { hipLaunchKernelGGL(hybrid_astar_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)hip_stream, a); });
 }

@@ -1,10 +1,9 @@
 // t2d_prm.hip -- the reference's probabilistic roadmap for n independent queries in one launch (prm_plan_kernel).  The formulas are
 // t2d_prm_dev.h; what they restate is search/prm.py: PRM.plan with the grid collision checker the reference's tests pair with it.
 // DESIGN.md 4.25.
-#include <cmath>
 #include <string>
 
-#include "t2d_host.h"
+#include "t2d_plan_host.h"
 #include "t2d_prm_dev.h"
 
 namespace t2d {
@@ -28,7 +27,7 @@ __global__ __launch_bounds__(kPrmThreads) void prm_plan_kernel(PrmArgs a) {
     __shared__ int s_cnt[kPrmMaxNodes], s_settled[kPrmMaxNodes];
     __shared__ int s_wave[kPrmThreads / 64];
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double nan = __builtin_nan(""), inf = __builtin_huge_val();
+    const double inf = __builtin_huge_val();
     const unsigned long long inf_bits = 0x7ff0000000000000ull;
 
     const int H = a.hw[2 * e], W = a.hw[2 * e + 1];
@@ -44,15 +43,13 @@ __global__ __launch_bounds__(kPrmThreads) void prm_plan_kernel(PrmArgs a) {
     double* g_cost = reinterpret_cast<double*>(row + prm_cost_offset(N));
     int* g_ij = reinterpret_cast<int*>(row + prm_ij_offset(N, a.k));
     int* g_cand = reinterpret_cast<int*>(row + prm_scratch_offset(N, a.k));
-    const double* weight = a.weight + (size_t)e * (size_t)a.stride;
+    const ObstacleGrid obstacles{a.weight + (size_t)e * (size_t)a.stride, H, W, a.ox, a.oy, a.cell};
 
     int status = -1, n_edges = 0, sweeps = 0, len = 0;
     {
-        const auto bad = [](double v) { return !(__builtin_fabs(v) <= kPrmXYLimit); };
         const auto within = [](double lo, double v, double hi) { return lo - kPrmBoundaryEps <= v && v <= hi + kPrmBoundaryEps; };
-        if (bad(sx) || bad(sy) || bad(tx) || bad(ty) || bad(x_min) || bad(x_max) || bad(y_min) || bad(y_max) || x_min >= x_max ||
-            y_min >= y_max || !within(x_min, sx, x_max) || !within(y_min, sy, y_max) || !within(x_min, tx, x_max) ||
-            !within(y_min, ty, y_max) || H < 1 || W < 1 || (long long)H * (long long)W > (long long)a.stride)
+        if (plan_row_bad(sx, sy, tx, ty, x_min, x_max, y_min, y_max, H, W, a.stride) || x_min >= x_max || y_min >= y_max ||
+            !within(x_min, sx, x_max) || !within(y_min, sy, y_max) || !within(x_min, tx, x_max) || !within(y_min, ty, y_max))
             status = PRM_INVALID;
     }
     if (status < 0) {
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(kPrmThreads) void prm_plan_kernel(PrmArgs a) {
             const int i = w / K, t = w - i * K;
             if (t < s_cnt[i]) {
                 const double2 p = s_xy[i], q = s_xy[g_cand[w]];
-                if (prm_seg_hit(p.x, p.y, q.x, q.y, weight, H, W, a.ox, a.oy, a.cell)) g_cand[w] = -1;
+                if (obstacles.lane_seg_hit(p.x, p.y, q.x, q.y)) g_cand[w] = -1;
             }
         }
         __syncthreads();
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(kPrmThreads) void prm_plan_kernel(PrmArgs a) {
                 for (int t = 0; t < s_cnt[i]; ++t) c += g_cand[i * K + t] >= 0;
             }
             int total;
-            const int before = prm_wave_excl_scan(c, total);
+            const int before = plan_wave_excl_scan(c, total);
             if (lane == 0) s_wave[wave] = total;
             __syncthreads();
             int at = n_edges + before, all = 0;
@@ -225,11 +222,7 @@ __global__ __launch_bounds__(kPrmThreads) void prm_plan_kernel(PrmArgs a) {
         len = s_wave[0];
         status = len == 0 ? PRM_NO_PATH : (len > a.max_path ? PRM_TRUNCATED : PRM_FOUND);
     }
-    {
-        double* out = a.path + (size_t)e * (size_t)a.max_path * 2;
-        const int from = (len < a.max_path ? len : a.max_path) * 2;
-        for (int i = from + tid; i < a.max_path * 2; i += kPrmThreads) out[i] = nan;
-    }
+    plan_path_tail<2, kPrmThreads>(a.path + (size_t)e * (size_t)a.max_path * 2, len, a.max_path, tid);
     if (tid == 0) {
         a.path_len[e] = len;
         a.status[e] = status;
@@ -253,57 +246,24 @@ extern "C" int t2d_prm_plan(int32_t device_id, int32_t n, const double* weight_d
                             double* path_dev, int32_t* path_len_dev, int32_t* status_dev, int32_t* n_edges_dev, int32_t* sweeps_dev,
                             void* hip_stream) {
     using namespace t2d;
-    const auto misaligned = [](const void* p, uintptr_t mask) { return !p || (reinterpret_cast<uintptr_t>(p) & mask); };
-    if (n < 0 || max_cells < 1 || max_path < 0)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: n >= 0, max_cells >= 1 and max_path >= 0");
-    if (n_samples < 1 || n_samples + 2 > T2D_PRM_MAX_NODES)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: n_samples must be in 1 .. T2D_PRM_MAX_NODES - 2");
-    if (!(connection_radius >= 0.0 && connection_radius <= kPrmXYLimit))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: connection_radius must be 0 (k-nearest mode) or positive and finite");
+    host::PlanEntry entry("t2d_prm_plan");
+    if (n < 0 || max_cells < 1 || max_path < 0) return entry.invalid("n >= 0, max_cells >= 1 and max_path >= 0");
+    if (n_samples < 1 || n_samples + 2 > T2D_PRM_MAX_NODES) return entry.invalid("n_samples must be in 1 .. T2D_PRM_MAX_NODES - 2");
+    if (!(connection_radius >= 0.0 && connection_radius <= kPlanXYLimit))
+        return entry.invalid("connection_radius must be 0 (k-nearest mode) or positive and finite");
     const bool by_radius = connection_radius > 0.0;
-    if (!by_radius && (k_nearest < 1 || k_nearest > T2D_PRM_MAX_K))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: k_nearest must be in 1 .. T2D_PRM_MAX_K");
-    if (by_radius && max_degree < 1)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: max_degree must be at least 1");
-    if (!(cell_size >= kSampleStepMin && cell_size <= kSampleStepMax) || !(std::fabs(origin_x) <= kPrmXYLimit) ||
-        !(std::fabs(origin_y) <= kPrmXYLimit))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: cell_size must be positive (1e-150 .. 1e150), the origin finite");
-    if (misaligned(weight_dev, 7u) || misaligned(start_dev, 7u) || misaligned(target_dev, 7u) || misaligned(boundary_dev, 7u) ||
-        misaligned(seed_dev, 7u) || misaligned(hw_dev, 3u) || misaligned(path_len_dev, 3u) || misaligned(status_dev, 3u) ||
-        misaligned(n_edges_dev, 3u) || misaligned(sweeps_dev, 3u) || (max_path > 0 && misaligned(path_dev, 7u)) ||
-        misaligned(workspace_dev, 15u))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: null or misaligned device pointer (the workspace: 16 bytes)");
+    if (!by_radius && (k_nearest < 1 || k_nearest > T2D_PRM_MAX_K)) return entry.invalid("k_nearest must be in 1 .. T2D_PRM_MAX_K");
+    if (by_radius && max_degree < 1) return entry.invalid("max_degree must be at least 1");
+    if (int rc = entry.cell_origin(cell_size, origin_x, origin_y)) return rc;
+    entry.required(7u, weight_dev, start_dev, target_dev, boundary_dev, seed_dev);
+    entry.required(3u, hw_dev, path_len_dev, status_dev, n_edges_dev, sweeps_dev);
+    if (max_path > 0) entry.required(7u, path_dev);
+    if (int rc = entry.workspace(workspace_dev).pointers()) return rc;
     const int k = by_radius ? max_degree : k_nearest;
-    const int64_t need = t2d_prm_plan_workspace_bytes(n, n_samples, k);
-    if (workspace_bytes < need)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_prm_plan: the workspace has " + std::to_string(workspace_bytes) +
-                                                        " bytes, t2d_prm_plan_workspace_bytes asks for " + std::to_string(need));
-    if (n == 0) return T2D_OK;
-    if (hipSetDevice(device_id) != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, "t2d_prm_plan: hipSetDevice failed");
-    PrmArgs a;
-    a.weight = weight_dev;
-    a.hw = hw_dev;
-    a.start = start_dev;
-    a.target = target_dev;
-    a.boundary = boundary_dev;
-    a.seed = seed_dev;
-    a.stride = max_cells;
-    a.n_samples = n_samples;
-    a.k = k;
-    a.max_path = max_path;
-    a.radius = by_radius ? connection_radius : 0.0;
-    a.cell = cell_size;
-    a.ox = origin_x;
-    a.oy = origin_y;
-    a.ws = static_cast<unsigned char*>(workspace_dev);
-    a.ws_row = prm_row_bytes(n_samples + 2, k);
-    a.path = path_dev;
-    a.path_len = path_len_dev;
-    a.status = status_dev;
-    a.n_edges = n_edges_dev;
-    a.sweeps = sweeps_dev;
-    hipLaunchKernelGGL(prm_plan_kernel, dim3((unsigned)n), dim3(kPrmThreads), 0, (hipStream_t)hip_stream, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, std::string("t2d_prm_plan: ") + hipGetErrorString(err));
-    return T2D_OK;
+    if (int rc = entry.workspace_bytes(workspace_bytes, t2d_prm_plan_workspace_bytes(n, n_samples, k))) return rc;
+    const PrmArgs a{weight_dev, hw_dev, start_dev, target_dev, boundary_dev, seed_dev,
+                    max_cells, n_samples, k, max_path, by_radius ? connection_radius : 0.0, cell_size, origin_x, origin_y,
+                    static_cast<unsigned char*>(workspace_dev), prm_row_bytes(n_samples + 2, k),
+                    path_dev, path_len_dev, status_dev, n_edges_dev, sweeps_dev};
+    return entry.launch(device_id, n, [&] { hipLaunchKernelGGL(prm_plan_kernel, dim3((unsigned)n), dim3(kPrmThreads), 0, (hipStream_t)hip_stream, a); });
 }

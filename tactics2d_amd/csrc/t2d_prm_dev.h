@@ -1,8 +1,10 @@
 // t2d_prm_dev.h -- the pieces of the probabilistic roadmap (search/prm.py: PRM.plan, with the grid collision checker of the
 // reference's tests/test_search.py) as device functions.  fp64 throughout, one rounding per operation; tests/prm_ref.py states the
-// same operations in Python.  The slab test and the cell range are t2d_hybrid_dev.h's, the stream is t2d_rng.h's.  DESIGN.md 4.25.
+// same operations in Python.  The collision checker and the wave's prefix sum are t2d_gridplan_dev.h's, the stream is t2d_rng.h's.
+// DESIGN.md 4.25.
 #pragma once
-#include "t2d_sample_dev.h"
+#include "t2d_gridplan_dev.h"
+#include "t2d_rng.h"
 
 namespace t2d {
 
@@ -10,7 +12,7 @@ enum { PRM_FOUND = 0, PRM_NO_PATH = 1, PRM_TRUNCATED = 2, PRM_OVERFLOW = 3, PRM_
 constexpr int kPrmMaxNodes = 1024;   // start, target and the samples of one query: x, y in 16 KiB of LDS, two planes of g in 16 KiB, two words each in 8 KiB
 constexpr int kPrmMaxK = 16;         // k_nearest: the sorted list of k + 1 (d2, index) lives in registers
 constexpr int kPrmThreads = 256;     // one query per workgroup of four waves
-constexpr double kPrmXYLimit = 1e150, kPrmBoundaryEps = 1e-9;
+constexpr double kPrmBoundaryEps = 1e-9;
 
 // The arguments of one launch (t2d_prm_plan), checked by the entry point.
 struct PrmArgs {
@@ -70,37 +72,5 @@ struct PrmNearest {
         }
     }
 };
-
-// collide_fn for ONE lane: the segment p1 -> p2 against the obstacle cells of its box (sample_box), row by row.  Which obstacle
-// answers first does not matter: the result is "any".
-T2D_DEV bool prm_seg_hit(double x1, double y1, double x2, double y2, const double* weight, int H, int W, double ox, double oy,
-                         double cell) {
-    int c0, c1, r0, r1;
-    hybrid_range(x2 < x1 ? x2 : x1, x2 > x1 ? x2 : x1, ox, cell, W, c0, c1);
-    hybrid_range(y2 < y1 ? y2 : y1, y2 > y1 ? y2 : y1, oy, cell, H, r0, r1);
-    const double half = cell / 2.0;
-    for (int r = r0; r <= r1; ++r) {
-        for (int c = c0; c <= c1; ++c) {
-            const double w = weight[r * W + c];
-            if (!(w != w || w == __builtin_huge_val())) continue;
-            if (hybrid_slab(x1, y1, x2, y2, ox + (double)c * cell, oy + (double)r * cell, half)) return true;
-        }
-    }
-    return false;
-}
-
-// Exclusive prefix sum of `cnt` over the 64 lanes of a wave (the step kernel's wave_excl_scan: row_shr 1, 2, 4, 8, row_bcast 15
-// and 31); `total` is the sum of all 64.  Must be called by all 64 lanes.
-T2D_DEV int prm_wave_excl_scan(int cnt, int& total) {
-    int v = cnt;
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    total = __builtin_amdgcn_readlane(v, 63);
-    return v - cnt;
-}
 
 }  // namespace t2d

@@ -1,10 +1,9 @@
 // t2d_sample.hip -- the reference's sampling planners for n independent queries in one launch (sample_plan_kernel): RRT, RRT* and
 // RRT-Connect.  The formulas are t2d_sample_dev.h; what they restate is search/rrt.py, search/rrt_star.py and
 // search/rrt_connect.py with the grid collision checker the reference's tests pair with them.  DESIGN.md 4.23.
-#include <cmath>
 #include <string>
 
-#include "t2d_host.h"
+#include "t2d_plan_host.h"
 #include "t2d_sample_dev.h"
 
 namespace t2d {
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
     double2* g_xy = reinterpret_cast<double2*>(row);
     double* g_cost = reinterpret_cast<double*>(row + sample_cost_offset(max_nodes));
     int* g_parent = reinterpret_cast<int*>(row + sample_parent_offset(max_nodes));
-    const double* weight = a.weight + (size_t)e * (size_t)a.stride;
+    const ObstacleGrid obstacles{a.weight + (size_t)e * (size_t)a.stride, H, W, a.ox, a.oy, a.cell};
 
     // the LDS copy of slot s, or -1: the front lds_front slots and the back kSampleLdsNodes - lds_front ones
     const int lds_front = connect ? kSampleLdsNodes / 2 : kSampleLdsNodes;
@@ -67,15 +66,7 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
         }
     };
     // the segment p1 -> p2 against the obstacle cells near it, 64 at a time; the same answer in every lane
-    const auto seg_hit = [&](double x1, double y1, double x2, double y2) {
-        const SampleBox b = sample_box(x1, y1, x2, y2, a.ox, a.oy, a.cell, H, W);
-        for (int base = 0; base < b.cnt; base += 64) {
-            const int j = base + lane;
-            const bool hit = j < b.cnt && sample_cell_hit(b, j, weight, W, x1, y1, x2, y2, a.ox, a.oy, a.cell);
-            if (__ballot(hit)) return true;
-        }
-        return false;
-    };
+    const auto seg_hit = [&](double x1, double y1, double x2, double y2) { return obstacles.wave_seg_hit(x1, y1, x2, y2, lane); };
     // the node of a tree nearest to (px, py): the first minimum of dx * dx + dy * dy
     const auto nearest = [&](bool back, int count, double px, double py) {
         double bd = inf;
@@ -88,13 +79,15 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
                 bi = i;
             }
         }
-        hybrid_wave_argmin(bd, bi, bp);
+        wave_argmin(bd, bi, bp);
         return bi;
     };
 
     int status = -1, iterations = 0, na = 0, nb = 0, end_a = -1, end_b = -1;
     {
-        const auto bad = [](double v) { return !(__builtin_fabs(v) <= kSampleXYLimit); };
+        // plan_row_bad's condition, written out: through the function this kernel compiles to another instruction stream, which
+        // measured 1 to 4 % slower on some shapes
+        const auto bad = [](double v) { return !(__builtin_fabs(v) <= kPlanXYLimit); };
         if (bad(sx) || bad(sy) || bad(tx) || bad(ty) || bad(x_min) || bad(x_max) || bad(y_min) || bad(y_max) || H < 1 || W < 1 ||
             (long long)H * (long long)W > (long long)a.stride)
             status = SAMPLE_INVALID;
@@ -159,7 +152,7 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
                         }
                     }
                 }
-                hybrid_wave_argmin(bc, bi, bp);
+                wave_argmin(bc, bi, bp);
                 if (bi == 0x7fffffff) break;
                 const double2 v = load_xy(bi);
                 if (!seg_hit(v.x, v.y, nx, ny)) {
@@ -192,7 +185,7 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
                 }
                 for (unsigned long long m = __ballot(cheaper); m; m &= m - 1) {
                     const int src = __builtin_ctzll(m);
-                    const bool hit = seg_hit(hybrid_bcast(v.x, src), hybrid_bcast(v.y, src), nx, ny);
+                    const bool hit = seg_hit(wave_bcast(v.x, src), wave_bcast(v.y, src), nx, ny);
                     if (lane == src && !hit) {
                         g_parent[i] = new_idx;
                         g_cost[i] = alt;
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(64) void sample_plan_kernel(SampleArgs a) {
         }
         if (status == SAMPLE_FOUND && len > a.max_path) status = SAMPLE_TRUNCATED;
     }
-    {
+    {   // (plan_path_tail<2, 64>, written out for the same reason)
         double* out = a.path + (size_t)e * (size_t)a.max_path * 2;
         const int from = (len < a.max_path ? len : a.max_path) * 2;
         for (int i = from + lane; i < a.max_path * 2; i += 64) out[i] = nan;
@@ -286,56 +279,22 @@ extern "C" int t2d_sample_plan(int32_t device_id, int32_t n, int32_t kind, const
                                int64_t workspace_bytes, double* path_dev, int32_t* path_len_dev, int32_t* status_dev,
                                int32_t* iterations_dev, int32_t* nodes_dev, void* hip_stream) {
     using namespace t2d;
-    const auto misaligned = [](const void* p, uintptr_t mask) { return !p || (reinterpret_cast<uintptr_t>(p) & mask); };
+    host::PlanEntry entry("t2d_sample_plan");
     if (kind != T2D_SAMPLE_RRT && kind != T2D_SAMPLE_RRT_STAR && kind != T2D_SAMPLE_RRT_CONNECT)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: kind must be T2D_SAMPLE_RRT, _RRT_STAR or _RRT_CONNECT");
+        return entry.invalid("kind must be T2D_SAMPLE_RRT, _RRT_STAR or _RRT_CONNECT");
     if (n < 0 || max_cells < 1 || max_path < 0 || max_nodes < 1 || max_iter < 0)
-        return host::fail(nullptr, T2D_ERR_INVALID,
-                          "t2d_sample_plan: n >= 0, max_cells >= 1, max_path >= 0, max_nodes >= 1 and max_iter >= 0");
-    if (!(extension_step >= kSampleStepMin && extension_step <= kSampleStepMax))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: extension_step must be positive (1e-150 .. 1e150)");
-    if (!(radius >= 0.0))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: radius must not be negative or NaN");
-    if (!(cell_size >= kSampleStepMin && cell_size <= kSampleStepMax) || !(std::fabs(origin_x) <= kSampleXYLimit) ||
-        !(std::fabs(origin_y) <= kSampleXYLimit))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: cell_size must be positive (1e-150 .. 1e150), the origin finite");
-    if (misaligned(weight_dev, 7u) || misaligned(start_dev, 7u) || misaligned(target_dev, 7u) || misaligned(boundary_dev, 7u) ||
-        misaligned(seed_dev, 7u) || misaligned(hw_dev, 3u) || misaligned(path_len_dev, 3u) || misaligned(status_dev, 3u) ||
-        misaligned(iterations_dev, 3u) || misaligned(nodes_dev, 3u) || (max_path > 0 && misaligned(path_dev, 7u)) ||
-        misaligned(workspace_dev, 15u))
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: null or misaligned device pointer (the workspace: 16 bytes)");
-    const int64_t need = t2d_sample_plan_workspace_bytes(n, max_nodes);
-    if (workspace_bytes < need)
-        return host::fail(nullptr, T2D_ERR_INVALID, "t2d_sample_plan: the workspace has " + std::to_string(workspace_bytes) +
-                                                        " bytes, t2d_sample_plan_workspace_bytes asks for " + std::to_string(need));
-    if (n == 0) return T2D_OK;
-    if (hipSetDevice(device_id) != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, "t2d_sample_plan: hipSetDevice failed");
-    SampleArgs a;
-    a.weight = weight_dev;
-    a.hw = hw_dev;
-    a.start = start_dev;
-    a.target = target_dev;
-    a.boundary = boundary_dev;
-    a.seed = seed_dev;
-    a.kind = kind;
-    a.stride = max_cells;
-    a.max_iter = max_iter;
-    a.max_nodes = max_nodes;
-    a.max_path = max_path;
-    a.step = extension_step;
-    a.radius = radius;
-    a.cell = cell_size;
-    a.ox = origin_x;
-    a.oy = origin_y;
-    a.ws = static_cast<unsigned char*>(workspace_dev);
-    a.ws_row = sample_row_bytes(max_nodes);
-    a.path = path_dev;
-    a.path_len = path_len_dev;
-    a.status = status_dev;
-    a.iterations = iterations_dev;
-    a.nodes = nodes_dev;
-    hipLaunchKernelGGL(sample_plan_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)hip_stream, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return host::fail(nullptr, T2D_ERR_HIP, std::string("t2d_sample_plan: ") + hipGetErrorString(err));
-    return T2D_OK;
+        return entry.invalid("n >= 0, max_cells >= 1, max_path >= 0, max_nodes >= 1 and max_iter >= 0");
+    if (!(extension_step >= kPlanStepMin && extension_step <= kPlanStepMax)) return entry.invalid("extension_step must be positive (1e-150 .. 1e150)");
+    if (!(radius >= 0.0)) return entry.invalid("radius must not be negative or NaN");
+    if (int rc = entry.cell_origin(cell_size, origin_x, origin_y)) return rc;
+    entry.required(7u, weight_dev, start_dev, target_dev, boundary_dev, seed_dev);
+    entry.required(3u, hw_dev, path_len_dev, status_dev, iterations_dev, nodes_dev);
+    if (max_path > 0) entry.required(7u, path_dev);
+    if (int rc = entry.workspace(workspace_dev).pointers()) return rc;
+    if (int rc = entry.workspace_bytes(workspace_bytes, t2d_sample_plan_workspace_bytes(n, max_nodes))) return rc;
+    const SampleArgs a{weight_dev, hw_dev, start_dev, target_dev, boundary_dev, seed_dev,
+                       kind, max_cells, max_iter, max_nodes, max_path, extension_step, radius, cell_size, origin_x, origin_y,
+                       static_cast<unsigned char*>(workspace_dev), sample_row_bytes(max_nodes),
+                       path_dev, path_len_dev, status_dev, iterations_dev, nodes_dev};
+    return entry.launch(device_id, n, [&] { hipLaunchKernelGGL(sample_plan_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)hip_stream, a); });
 }

@@ -89,6 +89,100 @@ def _i32(x, dev, shape):
     return t.reshape(shape).contiguous()
 
 
+def _f64(x, dev, shape):
+    import torch
+    t = x.to(dev, torch.float64) if _is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, np.float64)).to(dev)
+    return t.reshape(shape).contiguous()
+
+
+# ---- what every batch function takes in the same way ---------------------------------------------------------------------------------
+def _grids(weight_grids):
+    """weight_grids [n, H_max, W_max] or [H, W], numpy or a CUDA tensor -> (n, h_max, w_max, stride, upload); upload(dev), inside
+    the stream context, gives float64 [n, stride] on the device (a contiguous float64 tensor is read in place)"""
+    if not _is_tensor(weight_grids):
+        weight_grids = np.asarray(weight_grids, np.float64)
+    shape = tuple(weight_grids.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1] * shape[2] < 1:
+        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
+    n, h_max, w_max = shape
+    return n, h_max, w_max, h_max * w_max, lambda dev: _f64(weight_grids, dev, (n, h_max * w_max))
+
+
+def _hw_host(hw, n, h_max, w_max):
+    """the host copy of hw, int32 [n, 2] (None: every grid fills its row) -- or None for a device-resident hw, which _hw_dev takes
+    as it is"""
+    if _is_tensor(hw):
+        return None
+    return np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else np.asarray(hw, np.int32).reshape(n, 2)
+
+
+def _hw_dev(hw, hw_host, dev, n):
+    return _i32(hw if hw_host is None else hw_host, dev, (n, 2))
+
+
+def _cell_origin(cell_size, origin):
+    """-> (cell_size, origin_x, origin_y) as floats"""
+    cell_size = float(cell_size)
+    if not (1e-150 <= cell_size <= 1e150):
+        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
+        raise ValueError(f"origin must be two finite numbers, got {origin}")
+    return cell_size, float(origin[0]), float(origin[1])
+
+
+def _count(name, value, least=0):
+    """int(value), not below `least`"""
+    value = int(value)
+    if value < least:
+        raise ValueError(f"{name} must not be negative, got {value}" if least == 0 else f"{name} must be at least {least}, got {value}")
+    return value
+
+
+def _clamped_iter(max_iter):
+    return max(min(int(max_iter), 2 ** 31 - 1), 0)
+
+
+def _points(what, x, n, cols):
+    """starts / targets: [n, cols], or [cols] for one row"""
+    if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, cols), (cols,) if n == 1 else (n, cols)):
+        raise ValueError(f"{what} must have shape ({n}, {cols}), got {tuple(np.shape(x))}")
+    return x
+
+
+def _boundaries(boundaries, n):
+    """[n, 4], or [4] for all rows"""
+    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
+        return np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
+    return boundaries
+
+
+def _workspace(need, n, dev):
+    """-> (ws, part): the launch's workspace of `need` bytes (allocated on the current stream: reused only behind this launch) and
+    part(lo, dtype, *shape): the view [n, *shape] of the bytes from lo of every query's row (a row is a multiple of 256 bytes: every
+    part stays aligned); an empty batch has empty parts of the same shapes"""
+    import torch
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    rows = ws[:need].view(n, need // n) if n else None
+
+    def part(lo, dtype, *shape):
+        if rows is None:
+            return torch.empty((0,) + shape, dtype=dtype, device=dev)
+        return rows[:, lo:lo + math.prod(shape) * dtype.itemsize].view(dtype).view((n,) + shape)
+    return ws, part
+
+
+def _device_only(who, callback=None, collide_fn=None):
+    """the refusals of the one-query calls: a Python callable cannot run in a kernel"""
+    if callback is not None:
+        raise TypeError(f"{who} runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
+    if collide_fn is not None and collide_fn is not grid_collide:
+        raise TypeError(f"{who} runs on the device, where a Python callable cannot be called: collide_fn must be None or "
+                        "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
+                        f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+
+
 def _cells(cells, n, hw_host):
     """[n] linear indices from [n] indices or [n, 2] (row, col) pairs (numpy; pairs need the host copy of hw)"""
     c = np.asarray(cells)
@@ -109,38 +203,18 @@ def plan_batch(weight_grids, sources, targets=None, hw=None, connectivity=4, dia
     columns of `path` (default: H_max * W_max with targets, 0 without).  Returns GridPaths.  ValueError: another connectivity, a
     multiplier that is negative or not finite, shapes that disagree; GeometryError: H_max * W_max above MAX_CELLS."""
     import torch
-    if not _is_tensor(weight_grids):
-        weight_grids = np.asarray(weight_grids, np.float64)
-    shape = tuple(weight_grids.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3:
-        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W), got {tuple(weight_grids.shape)}")
-    if connectivity not in (4, 8):
-        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
-    mult = float(diagonal_cost_multiplier)
-    if not math.isfinite(mult) or mult < 0:
-        raise ValueError(f"diagonal_cost_multiplier must be finite and not negative, got {diagonal_cost_multiplier}")
-    n, h_max, w_max = shape
-    stride = h_max * w_max
-    if stride < 1:
-        raise ValueError(f"weight_grids must have at least one cell, got shape {shape}")
-    hw_host = None if _is_tensor(hw) else (np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else np.asarray(hw, np.int32).reshape(n, 2))
+    n, h_max, w_max, stride, upload = _grids(weight_grids)
+    mult = _edge_rule(connectivity, diagonal_cost_multiplier)
+    hw_host = _hw_host(hw, n, h_max, w_max)
     if not _is_tensor(sources):
         sources = _cells(sources, n, hw_host)
     if targets is not None and not _is_tensor(targets):
         targets = _cells(targets, n, hw_host)
-    max_path = (stride if targets is not None else 0) if max_path is None else int(max_path)
-    if max_path < 0:
-        raise ValueError(f"max_path must not be negative, got {max_path}")
+    max_path = _count("max_path", (stride if targets is not None else 0) if max_path is None else max_path)
     lib = _ffi.lib()
     dev, st = _stream_of(device_id, stream)
     with torch.cuda.stream(st):
-        if _is_tensor(weight_grids):
-            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
-        else:
-            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
-        hw_t = _i32(hw_host if hw_host is not None else hw, dev, (n, 2))
+        w, hw_t = upload(dev), _hw_dev(hw, hw_host, dev, n)
         src = _i32(sources, dev, (n,))
         tgt = torch.full((n,), -1, dtype=torch.int32, device=dev) if targets is None else _i32(targets, dev, (n,))
         field = torch.empty((n, stride), dtype=torch.float64, device=dev)
@@ -160,6 +234,56 @@ def cost_to_go(weight_grids, sources, hw=None, connectivity=4, diagonal_cost_mul
     return plan_batch(weight_grids, sources, None, hw, connectivity, diagonal_cost_multiplier, 0, device_id, stream).field
 
 
+def _edge_rule(connectivity, diagonal_cost_multiplier):
+    """-> the multiplier as a float"""
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    mult = float(diagonal_cost_multiplier)
+    if not math.isfinite(mult) or mult < 0:
+        raise ValueError(f"diagonal_cost_multiplier must be finite and not negative, got {diagonal_cost_multiplier}")
+    return mult
+
+
+def _grid_query(start, target, boundary, weight_grid, grid_resolution):
+    """The head Dijkstra.plan (dijkstra.py:24-266) and AStar.plan (a_star.py:23-276) share: the reference's checks of boundary and
+    resolution with its messages, start and target rasterised to cells and clamped -> (width, height, grid float64 [H, W],
+    start_rasterized, target_rasterized, start_idx, target_idx)"""
+    x_min, x_max, y_min, y_max = boundary
+    if grid_resolution <= 0:
+        raise ValueError(f"grid_resolution must be positive, got {grid_resolution}")
+    if x_min >= x_max or y_min >= y_max:
+        raise ValueError(f"Invalid boundary: {boundary}. Must satisfy x_min < x_max and y_min < y_max")
+    eps = grid_resolution * 1e-9
+    if not (x_min - eps <= start[0] < x_max + eps and y_min - eps <= start[1] < y_max + eps):
+        raise ValueError(f"start coordinate {start} is outside boundary {boundary}")
+    if not (x_min - eps <= target[0] < x_max + eps and y_min - eps <= target[1] < y_max + eps):
+        raise ValueError(f"target coordinate {target} is outside boundary {boundary}")
+    width = int((x_max - x_min) / grid_resolution)
+    height = int((y_max - y_min) / grid_resolution)
+    grid = np.asarray(weight_grid, np.float64)
+    if grid.ndim != 2:
+        raise ValueError(f"weight_grid must be 2D array, got shape {grid.shape}")
+    N = grid.size
+    if not math.isclose(width * height, N, rel_tol=1e-9):
+        raise ValueError(f"width*height={width*height} does not equal to N={N}. "
+                         f"Graph dimensions don't match the calculated grid size.")
+    if tuple(grid.shape) != (height, width):
+        raise ValueError(f"weight_grid has shape {grid.shape}, the boundary and resolution give ({height}, {width})")
+    start_rasterized = [(start[0] - x_min) / grid_resolution, (start[1] - y_min) / grid_resolution]
+    target_rasterized = [(target[0] - x_min) / grid_resolution, (target[1] - y_min) / grid_resolution]
+    start_x = max(0, min(int(round(start_rasterized[0])), width - 1))
+    start_y = max(0, min(int(round(start_rasterized[1])), height - 1))
+    target_x = max(0, min(int(round(target_rasterized[0])), width - 1))
+    target_y = max(0, min(int(round(target_rasterized[1])), height - 1))
+    start_idx = start_y * width + start_x
+    target_idx = target_y * width + target_x
+    if not (0 <= start_idx < N):
+        raise ValueError(f"start_idx {start_idx} out of bounds [0, {N})")
+    if not (0 <= target_idx < N):
+        raise ValueError(f"target_idx {target_idx} out of bounds [0, {N})")
+    return width, height, grid, start_rasterized, target_rasterized, start_idx, target_idx
+
+
 class Dijkstra:
     """Dijkstra (search/dijkstra.py) over a weight grid."""
 
@@ -172,41 +296,8 @@ class Dijkstra:
         x * grid_resolution + x_min, y * grid_resolution + y_min WRITTEN INTO THE INTEGER ARRAY of cell coordinates (so truncated
         towards zero, as there), None when there is no path, [[x, y]] of `start` when start and target fall into one cell.  The
         reference's ValueErrors are raised with its messages; max_iter is not modelled.  Synchronous: one launch, one download."""
-        x_min, x_max, y_min, y_max = boundary
-        if grid_resolution <= 0:
-            raise ValueError(f"grid_resolution must be positive, got {grid_resolution}")
-        if x_min >= x_max or y_min >= y_max:
-            raise ValueError(f"Invalid boundary: {boundary}. Must satisfy x_min < x_max and y_min < y_max")
-        eps = grid_resolution * 1e-9
-        if not (x_min - eps <= start[0] < x_max + eps and y_min - eps <= start[1] < y_max + eps):
-            raise ValueError(f"start coordinate {start} is outside boundary {boundary}")
-        if not (x_min - eps <= target[0] < x_max + eps and y_min - eps <= target[1] < y_max + eps):
-            raise ValueError(f"target coordinate {target} is outside boundary {boundary}")
-        width = int((x_max - x_min) / grid_resolution)
-        height = int((y_max - y_min) / grid_resolution)
-        grid = np.asarray(weight_grid, np.float64)
-        if grid.ndim != 2:
-            raise ValueError(f"weight_grid must be 2D array, got shape {grid.shape}")
+        width, _, grid, _, _, start_idx, target_idx = _grid_query(start, target, boundary, weight_grid, grid_resolution)
         N = grid.size
-        if not math.isclose(width * height, N, rel_tol=1e-9):
-            raise ValueError(f"width*height={width*height} does not equal to N={N}. "
-                             f"Graph dimensions don't match the calculated grid size.")
-        if tuple(grid.shape) != (height, width):
-            raise ValueError(f"weight_grid has shape {grid.shape}, the boundary and resolution give ({height}, {width})")
-        start_x = int(round((start[0] - x_min) / grid_resolution))
-        start_y = int(round((start[1] - y_min) / grid_resolution))
-        target_x = int(round((target[0] - x_min) / grid_resolution))
-        target_y = int(round((target[1] - y_min) / grid_resolution))
-        start_x = max(0, min(start_x, width - 1))
-        start_y = max(0, min(start_y, height - 1))
-        target_x = max(0, min(target_x, width - 1))
-        target_y = max(0, min(target_y, height - 1))
-        start_idx = start_y * width + start_x
-        target_idx = target_y * width + target_x
-        if not (0 <= start_idx < N):
-            raise ValueError(f"start_idx {start_idx} out of bounds [0, {N})")
-        if not (0 <= target_idx < N):
-            raise ValueError(f"target_idx {target_idx} out of bounds [0, {N})")
         if start_idx == target_idx:
             return np.array([[start[0], start[1]]])
         out = plan_batch(grid[None], np.int32([start_idx]), np.int32([target_idx]), None, connectivity, diagonal_cost_multiplier, N,
@@ -290,47 +381,25 @@ def astar_plan_batch(weight_grids, sources, targets, heuristic="euclidean", heur
     unknown heuristic, a table without "table" or "table" without one, another connectivity, a multiplier that is negative or not
     finite, a cell_size that is not positive and finite, shapes that disagree; GeometryError: H_max * W_max above MAX_CELLS."""
     import torch
-    if not _is_tensor(weight_grids):
-        weight_grids = np.asarray(weight_grids, np.float64)
-    shape = tuple(weight_grids.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[1] * shape[2] < 1:
-        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
-    if connectivity not in (4, 8):
-        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
-    mult = float(diagonal_cost_multiplier)
-    if not math.isfinite(mult) or mult < 0:
-        raise ValueError(f"diagonal_cost_multiplier must be finite and not negative, got {diagonal_cost_multiplier}")
+    n, h_max, w_max, stride, upload = _grids(weight_grids)
+    mult = _edge_rule(connectivity, diagonal_cost_multiplier)
     kind = _marker_kind(heuristic) if callable(heuristic) else ASTAR_KINDS.get(heuristic, heuristic)
     if isinstance(kind, bool) or kind not in ASTAR_KINDS.values():
         raise ValueError(f"heuristic must be one of {sorted(ASTAR_KINDS)}, a marker of this module or search.ASTAR_H_*, got {heuristic!r}")
     if (kind == L.ASTAR_H_TABLE) != (heuristic_table is not None):
         raise ValueError('heuristic="table" and heuristic_table go together')
-    cell_size = float(cell_size)
-    if not (1e-150 <= cell_size <= 1e150):
-        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
-    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
-        raise ValueError(f"origin must be two finite numbers, got {origin}")
-    n, h_max, w_max = shape
-    stride = h_max * w_max
-    hw_host = None if _is_tensor(hw) else (np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else np.asarray(hw, np.int32).reshape(n, 2))
+    cell_size, origin_x, origin_y = _cell_origin(cell_size, origin)
+    hw_host = _hw_host(hw, n, h_max, w_max)
     if not _is_tensor(sources):
         sources = _cells(sources, n, hw_host)
     if not _is_tensor(targets):
         targets = _cells(targets, n, hw_host)
-    max_path = stride if max_path is None else int(max_path)
-    if max_path < 0:
-        raise ValueError(f"max_path must not be negative, got {max_path}")
-    max_iter = max(min(int(max_iter), 2 ** 31 - 1), 0)
+    max_path = _count("max_path", stride if max_path is None else max_path)
+    max_iter = _clamped_iter(max_iter)
     lib = _ffi.lib()
     dev, st = _stream_of(device_id, stream)
     with torch.cuda.stream(st):
-        if _is_tensor(weight_grids):
-            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
-        else:
-            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
-        hw_t = _i32(hw_host if hw_host is not None else hw, dev, (n, 2))
+        w, hw_t = upload(dev), _hw_dev(hw, hw_host, dev, n)
         src, tgt = _i32(sources, dev, (n,)), _i32(targets, dev, (n,))
         table = _f64(heuristic_table, dev, (n, stride)) if kind == L.ASTAR_H_TABLE else None
         if kind in (L.ASTAR_H_ZERO, L.ASTAR_H_TABLE):
@@ -341,7 +410,7 @@ def astar_plan_batch(weight_grids, sources, targets, heuristic="euclidean", heur
         else:
             point = _f64(heuristic_targets, dev, (n, 2))
         need = int(lib.t2d_grid_astar_workspace_bytes(n, min(stride, MAX_CELLS), connectivity))
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        ws, _ = _workspace(need, n, dev)
         path = torch.empty((n, max_path), dtype=torch.int32, device=dev)
         path_xy = torch.empty((n, max_path, 2), dtype=torch.float64, device=dev)
         path_len, status, iterations, expanded = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
@@ -352,7 +421,7 @@ def astar_plan_batch(weight_grids, sources, targets, heuristic="euclidean", heur
         if n or stride > MAX_CELLS:   # (an empty batch has no memory to point at and nothing to launch; the cap is refused by name)
             _ffi.check(lib.t2d_grid_astar(device_id, n, w.data_ptr(), hw_t.data_ptr(), src.data_ptr(), tgt.data_ptr(), stride, connectivity,
                                           mult, kind, ptr(point), ptr(table), float(heuristic_scale), max_iter, max_path, cell_size,
-                                          float(origin[0]), float(origin[1]), ws.data_ptr(), need, ptr(path), path_len.data_ptr(),
+                                          origin_x, origin_y, ws.data_ptr(), need, ptr(path), path_len.data_ptr(),
                                           ptr(path_xy), status.data_ptr(), iterations.data_ptr(), expanded.data_ptr(), ptr(g), ptr(closed),
                                           ptr(parent), st.cuda_stream), None, lib)
     out = AStarPaths(path, path_xy, path_len, status, iterations, expanded, hw_t, g, closed, parent)
@@ -402,41 +471,8 @@ class AStar:
         the reference's integer array (see world_path), None when there is no path and when max_iter stopped the search, [[x, y]]
         of `start` when start and target fall into one cell.  The reference's ValueErrors are raised with its messages.
         Synchronous: one launch, one download."""
-        if callback is not None:
-            raise TypeError(f"AStar.plan runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
-        x_min, x_max, y_min, y_max = boundary
-        if grid_resolution <= 0:
-            raise ValueError(f"grid_resolution must be positive, got {grid_resolution}")
-        if x_min >= x_max or y_min >= y_max:
-            raise ValueError(f"Invalid boundary: {boundary}. Must satisfy x_min < x_max and y_min < y_max")
-        eps = grid_resolution * 1e-9
-        if not (x_min - eps <= start[0] < x_max + eps and y_min - eps <= start[1] < y_max + eps):
-            raise ValueError(f"start coordinate {start} is outside boundary {boundary}")
-        if not (x_min - eps <= target[0] < x_max + eps and y_min - eps <= target[1] < y_max + eps):
-            raise ValueError(f"target coordinate {target} is outside boundary {boundary}")
-        width = int((x_max - x_min) / grid_resolution)
-        height = int((y_max - y_min) / grid_resolution)
-        grid = np.asarray(weight_grid, np.float64)
-        if grid.ndim != 2:
-            raise ValueError(f"weight_grid must be 2D array, got shape {grid.shape}")
-        N = grid.size
-        if not math.isclose(width * height, N, rel_tol=1e-9):
-            raise ValueError(f"width*height={width*height} does not equal to N={N}. "
-                             f"Graph dimensions don't match the calculated grid size.")
-        if tuple(grid.shape) != (height, width):
-            raise ValueError(f"weight_grid has shape {grid.shape}, the boundary and resolution give ({height}, {width})")
-        start_rasterized = [(start[0] - x_min) / grid_resolution, (start[1] - y_min) / grid_resolution]
-        target_rasterized = [(target[0] - x_min) / grid_resolution, (target[1] - y_min) / grid_resolution]
-        start_x = max(0, min(int(round(start_rasterized[0])), width - 1))
-        start_y = max(0, min(int(round(start_rasterized[1])), height - 1))
-        target_x = max(0, min(int(round(target_rasterized[0])), width - 1))
-        target_y = max(0, min(int(round(target_rasterized[1])), height - 1))
-        start_idx = start_y * width + start_x
-        target_idx = target_y * width + target_x
-        if not (0 <= start_idx < N):
-            raise ValueError(f"start_idx {start_idx} out of bounds [0, {N})")
-        if not (0 <= target_idx < N):
-            raise ValueError(f"target_idx {target_idx} out of bounds [0, {N})")
+        _device_only("AStar.plan", callback)
+        width, _, grid, _, target_rasterized, start_idx, target_idx = _grid_query(start, target, boundary, weight_grid, grid_resolution)
         if start_idx == target_idx:
             return np.array([[start[0], start[1]]])
         cells, _ = _astar_one("AStar.plan", grid, start_idx, target_idx, heuristic_fn, target_rasterized,
@@ -512,12 +548,6 @@ class HybridPaths:
         self.path, self.path_len, self.status, self.iterations, self.nodes = path, path_len, status, iterations, nodes
 
 
-def _f64(x, dev, shape):
-    import torch
-    t = x.to(dev, torch.float64) if _is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, np.float64)).to(dev)
-    return t.reshape(shape).contiguous()
-
-
 def steer_deltas(steering_angles, wheelbase, step_size):
     """delta_heading of each motion primitive (hybrid_a_star.py:121-122), on the host with libm's tan as the reference has it"""
     return [math.tan(float(s)) / wheelbase * step_size for s in steering_angles]
@@ -533,53 +563,32 @@ def hybrid_plan_batch(starts, targets, boundaries, weight_grids, hw=None, step_s
     Returns HybridPaths.  ValueError: no or more than 16 steering angles, a step_size or cell_size that is not positive and
     finite, a wheelbase of 0, shapes that disagree."""
     import torch
-    if not _is_tensor(weight_grids):
-        weight_grids = np.asarray(weight_grids, np.float64)
-    shape = tuple(weight_grids.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[1] * shape[2] < 1:
-        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
-    n, h_max, w_max = shape
-    stride = h_max * w_max
-    step_size, cell_size, wheelbase = float(step_size), float(cell_size), float(wheelbase)
+    n, h_max, w_max, stride, upload = _grids(weight_grids)
+    step_size, wheelbase = float(step_size), float(wheelbase)
     if not (1e-150 <= step_size <= 1e150):
         raise ValueError(f"step_size must be positive and finite, got {step_size}")
-    if not (1e-150 <= cell_size <= 1e150):
-        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    cell_size, origin_x, origin_y = _cell_origin(cell_size, origin)
     if wheelbase == 0 or wheelbase != wheelbase:
         raise ValueError(f"wheelbase must not be 0, got {wheelbase}")
     steering_angles = list(steering_angles)
     if not 1 <= len(steering_angles) <= L.HYBRID_MAX_STEER:
         raise ValueError(f"1 .. {L.HYBRID_MAX_STEER} steering angles, got {len(steering_angles)}")
-    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
-        raise ValueError(f"origin must be two finite numbers, got {origin}")
-    max_path, max_nodes, max_iter = int(max_path), int(max_nodes), int(max_iter)
-    if max_path < 0 or max_nodes < 1:
-        raise ValueError(f"max_path must not be negative and max_nodes at least 1, got {max_path} and {max_nodes}")
-    max_iter = max(min(max_iter, 2 ** 31 - 1), 0)
+    max_path, max_nodes, max_iter = _count("max_path", max_path), _count("max_nodes", max_nodes, 1), _clamped_iter(max_iter)
     deltas = steer_deltas(steering_angles, wheelbase, step_size)
-    for what, x, cols in (("starts", starts, 3), ("targets", targets, 3)):
-        if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, cols), (cols,) if n == 1 else (n, cols)):
-            raise ValueError(f"{what} must have shape ({n}, {cols}), got {tuple(np.shape(x))}")
-    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
-        boundaries = np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
+    starts, targets, boundaries = _points("starts", starts, n, 3), _points("targets", targets, n, 3), _boundaries(boundaries, n)
+    hw_host = _hw_host(hw, n, h_max, w_max)
     lib = _ffi.lib()
     dev, st = _stream_of(device_id, stream)
     with torch.cuda.stream(st):
-        if _is_tensor(weight_grids):
-            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
-        else:
-            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
-        hw_t = _i32(np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else hw, dev, (n, 2))
+        w, hw_t = upload(dev), _hw_dev(hw, hw_host, dev, n)
         s_t, t_t, b_t = _f64(starts, dev, (n, 3)), _f64(targets, dev, (n, 3)), _f64(boundaries, dev, (n, 4))
         d_t = _f64(np.float64(deltas), dev, (len(deltas),))
         need = int(lib.t2d_hybrid_astar_workspace_bytes(n, max_nodes))
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        ws, _ = _workspace(need, n, dev)
         path = torch.empty((n, max_path, 3), dtype=torch.float64, device=dev)
         path_len, status, iterations, nodes = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
         _ffi.check(lib.t2d_hybrid_astar(device_id, n, w.data_ptr(), hw_t.data_ptr(), stride, s_t.data_ptr(), t_t.data_ptr(), b_t.data_ptr(),
-                                        d_t.data_ptr(), len(deltas), step_size, cell_size, float(origin[0]), float(origin[1]), max_iter,
+                                        d_t.data_ptr(), len(deltas), step_size, cell_size, origin_x, origin_y, max_iter,
                                         max_nodes, max_path, ws.data_ptr(), need, path.data_ptr() if max_path else None,
                                         path_len.data_ptr(), status.data_ptr(), iterations.data_ptr(), nodes.data_ptr(), st.cuda_stream),
                    None, lib)
@@ -602,10 +611,7 @@ class HybridAStar:
         TypeError.  `velocity` is unused, as in the reference.  Returns the reference's list of [x, y, heading] from start to
         target, [] when there is no path and when max_iter stopped the search.  RuntimeError when the search outgrew the device's
         caps (HYBRID_OVERFLOW): that is not "no path".  ValueError for a row the device calls INVALID.  Synchronous."""
-        if collide_fn is not None and collide_fn is not grid_collide:
-            raise TypeError("HybridAStar.plan runs on the device, where a Python callable cannot be called: collide_fn must be None or "
-                            "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
-                            f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+        _device_only("HybridAStar.plan", collide_fn=collide_fn)
         grid = np.asarray(obstacles, np.float64)
         if grid.ndim != 2:
             raise ValueError(f"obstacles must be a 2D weight grid, got shape {grid.shape}")
@@ -654,6 +660,21 @@ def row_seeds(seed, n):
     return np.array([stream_mix((seed + (i + 1) * _GAMMA) & _MASK64) for i in range(n)], np.uint64)
 
 
+def _seeds(seeds, n):
+    """seeds as sample_plan_batch takes them -> upload(dev): the n 64-bit keys on the device"""
+    import torch
+    if _is_tensor(seeds):
+        if seeds.dtype not in (torch.int64, torch.uint64) or tuple(seeds.shape) != (n,):
+            raise ValueError(f"seeds as a tensor must be int64 or uint64 [{n}]")
+        return lambda dev: seeds.to(dev).contiguous()
+    if np.ndim(seeds) == 0:
+        seeds = row_seeds(int(seeds), n)
+    seeds = np.ascontiguousarray(seeds).astype(np.uint64).reshape(-1)
+    if seeds.shape != (n,):
+        raise ValueError(f"seeds must be one integer or hold one per row ({n}), got {seeds.shape}")
+    return lambda dev: torch.as_tensor(seeds.view(np.int64)).to(dev)
+
+
 class SamplePaths:
     """What sample_plan_batch returns: device tensors, one row per query.  path float64 [n, max_path, 2] (NaN past the end),
     path_len int32 [n] (the FULL length; > max_path: cut), status int32 [n] (SAMPLE_FOUND, _MAX_ITER, _TRUNCATED, _OVERFLOW,
@@ -688,67 +709,35 @@ def sample_plan_batch(kind, starts, targets, boundaries, weight_grids, seeds, hw
     kind = SAMPLE_KINDS.get(kind, kind)
     if kind not in SAMPLE_KINDS.values() or isinstance(kind, bool):
         raise ValueError(f"kind must be one of {sorted(SAMPLE_KINDS)} or search.SAMPLE_*, got {kind!r}")
-    if not _is_tensor(weight_grids):
-        weight_grids = np.asarray(weight_grids, np.float64)
-    shape = tuple(weight_grids.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[1] * shape[2] < 1:
-        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
-    n, h_max, w_max = shape
-    stride = h_max * w_max
-    extension_step, cell_size, radius = float(extension_step), float(cell_size), float(radius)
+    n, h_max, w_max, stride, upload = _grids(weight_grids)
+    extension_step, radius = float(extension_step), float(radius)
     if not (1e-150 <= extension_step <= 1e150):
         raise ValueError(f"extension_step must be positive and finite, got {extension_step}")
-    if not (1e-150 <= cell_size <= 1e150):
-        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
+    cell_size, origin_x, origin_y = _cell_origin(cell_size, origin)
     if not radius >= 0:
         raise ValueError(f"radius must not be negative or NaN, got {radius}")
-    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
-        raise ValueError(f"origin must be two finite numbers, got {origin}")
-    max_path, max_nodes, max_iter = int(max_path), int(max_nodes), int(max_iter)
-    if max_path < 0 or max_nodes < 1:
-        raise ValueError(f"max_path must not be negative and max_nodes at least 1, got {max_path} and {max_nodes}")
-    max_iter = max(min(max_iter, 2 ** 31 - 1), 0)
-    for what, x in (("starts", starts), ("targets", targets)):
-        if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, 2), (2,) if n == 1 else (n, 2)):
-            raise ValueError(f"{what} must have shape ({n}, 2), got {tuple(np.shape(x))}")
-    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
-        boundaries = np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
-    if not _is_tensor(seeds):
-        if np.ndim(seeds) == 0:
-            seeds = row_seeds(int(seeds), n)
-        seeds = np.ascontiguousarray(seeds).astype(np.uint64).reshape(-1)
-        if seeds.shape != (n,):
-            raise ValueError(f"seeds must be one integer or hold one per row ({n}), got {seeds.shape}")
-    elif seeds.dtype not in (torch.int64, torch.uint64) or tuple(seeds.shape) != (n,):
-        raise ValueError(f"seeds as a tensor must be int64 or uint64 [{n}]")
+    max_path, max_nodes, max_iter = _count("max_path", max_path), _count("max_nodes", max_nodes, 1), _clamped_iter(max_iter)
+    starts, targets, boundaries = _points("starts", starts, n, 2), _points("targets", targets, n, 2), _boundaries(boundaries, n)
+    upload_seeds = _seeds(seeds, n)
+    hw_host = _hw_host(hw, n, h_max, w_max)
     lib = _ffi.lib()
     dev, st = _stream_of(device_id, stream)
     with torch.cuda.stream(st):
-        if _is_tensor(weight_grids):
-            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
-        else:
-            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
-        hw_t = _i32(np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else hw, dev, (n, 2))
+        w, hw_t, seed_t = upload(dev), _hw_dev(hw, hw_host, dev, n), upload_seeds(dev)
         s_t, t_t, b_t = _f64(starts, dev, (n, 2)), _f64(targets, dev, (n, 2)), _f64(boundaries, dev, (n, 4))
-        seed_t = seeds.to(dev).contiguous() if _is_tensor(seeds) else torch.as_tensor(seeds.view(np.int64)).to(dev)
         need = int(lib.t2d_sample_plan_workspace_bytes(n, max_nodes))
-        row = need // n if n else 0
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        ws, part = _workspace(need, n, dev)
         path = torch.empty((n, max_path, 2), dtype=torch.float64, device=dev)
         path_len, status, iterations = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
         nodes = torch.empty((n, 2), dtype=torch.int32, device=dev)
         _ffi.check(lib.t2d_sample_plan(device_id, n, kind, w.data_ptr(), hw_t.data_ptr(), stride, s_t.data_ptr(), t_t.data_ptr(),
-                                       b_t.data_ptr(), seed_t.data_ptr(), extension_step, radius, cell_size, float(origin[0]),
-                                       float(origin[1]), max_iter, max_nodes, max_path, ws.data_ptr(), need,
+                                       b_t.data_ptr(), seed_t.data_ptr(), extension_step, radius, cell_size, origin_x,
+                                       origin_y, max_iter, max_nodes, max_path, ws.data_ptr(), need,
                                        path.data_ptr() if max_path else None, path_len.data_ptr(), status.data_ptr(),
                                        iterations.data_ptr(), nodes.data_ptr(), st.cuda_stream), None, lib)
-        rows = ws[:need].view(n, row) if n else ws[:0].view(0, 0)
-        part = lambda lo, hi, dt: rows[:, lo:hi].view(dt)   # (a row is a multiple of 256 bytes: every part stays aligned)
-        xy = part(0, 16 * max_nodes, torch.float64).view(n, max_nodes, 2)
-        cost = part(16 * max_nodes, 24 * max_nodes, torch.float64) if kind == SAMPLE_RRT_STAR else None
-        parent = part(24 * max_nodes, 28 * max_nodes, torch.int32)
+        xy = part(0, torch.float64, max_nodes, 2)
+        cost = part(16 * max_nodes, torch.float64, max_nodes) if kind == SAMPLE_RRT_STAR else None
+        parent = part(24 * max_nodes, torch.int32, max_nodes)
     out = SamplePaths(kind, path, path_len, status, iterations, nodes, xy, parent, cost)
     out._inputs = (w, hw_t, s_t, t_t, b_t, seed_t, ws)   # (kept alive with the result)
     return out
@@ -756,12 +745,7 @@ def sample_plan_batch(kind, starts, targets, boundaries, weight_grids, seeds, hw
 
 def _sample_plan(kind, who, start, target, boundary, obstacles, collide_fn, extension_step, max_iter, radius, callback, seed, device_id):
     """RRT.plan / RRTStar.plan / RRTConnect.plan: one query, synchronous, in the reference's lists"""
-    if callback is not None:
-        raise TypeError(f"{who}.plan runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
-    if collide_fn is not None and collide_fn is not grid_collide:
-        raise TypeError(f"{who}.plan runs on the device, where a Python callable cannot be called: collide_fn must be None or "
-                        "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
-                        f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+    _device_only(f"{who}.plan", callback, collide_fn)
     grid = np.asarray(obstacles, np.float64)
     if grid.ndim != 2:
         raise ValueError(f"obstacles must be a 2D weight grid, got shape {grid.shape}")
@@ -892,16 +876,8 @@ def prm_plan_batch(starts, targets, boundaries, weight_grids, seeds, hw=None, n_
     PRMPaths.  ValueError: n_samples below 1 or above PRM_MAX_NODES - 2, k_nearest outside 1 .. PRM_MAX_K, a radius that is not
     positive and finite, max_degree below 1, a cell_size that is not positive and finite, shapes that disagree."""
     import torch
-    if not _is_tensor(weight_grids):
-        weight_grids = np.asarray(weight_grids, np.float64)
-    shape = tuple(weight_grids.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[1] * shape[2] < 1:
-        raise ValueError(f"weight_grids must have shape (n, H, W) or (H, W) with at least one cell, got {tuple(weight_grids.shape)}")
-    n, h_max, w_max = shape
-    stride = h_max * w_max
-    n_samples, k_nearest, max_degree, max_path = int(n_samples), int(k_nearest), int(max_degree), int(max_path)
+    n, h_max, w_max, stride, upload = _grids(weight_grids)
+    n_samples, k_nearest, max_degree = int(n_samples), int(k_nearest), int(max_degree)
     if n_samples < 1:
         raise ValueError(f"n_samples must be positive, got {n_samples}")
     if n_samples + 2 > PRM_MAX_NODES:
@@ -915,62 +891,33 @@ def prm_plan_batch(starts, targets, boundaries, weight_grids, seeds, hw=None, n_
             raise ValueError(f"max_degree must be at least 1, got {max_degree}")
     elif not 1 <= k_nearest <= PRM_MAX_K:
         raise ValueError(f"k_nearest must be in 1 .. {PRM_MAX_K}, got {k_nearest}")
-    cell_size = float(cell_size)
-    if not (1e-150 <= cell_size <= 1e150):
-        raise ValueError(f"cell_size must be positive and finite, got {cell_size}")
-    if len(origin) != 2 or not all(math.isfinite(float(v)) for v in origin):
-        raise ValueError(f"origin must be two finite numbers, got {origin}")
-    if max_path < 0:
-        raise ValueError(f"max_path must not be negative, got {max_path}")
-    for what, x in (("starts", starts), ("targets", targets)):
-        if tuple(x.shape if _is_tensor(x) else np.shape(x)) not in ((n, 2), (2,) if n == 1 else (n, 2)):
-            raise ValueError(f"{what} must have shape ({n}, 2), got {tuple(np.shape(x))}")
-    if not _is_tensor(boundaries) and np.ndim(boundaries) == 1:
-        boundaries = np.tile(np.asarray(boundaries, np.float64).reshape(1, 4), (n, 1))
-    if not _is_tensor(seeds):
-        if np.ndim(seeds) == 0:
-            seeds = row_seeds(int(seeds), n)
-        seeds = np.ascontiguousarray(seeds).astype(np.uint64).reshape(-1)
-        if seeds.shape != (n,):
-            raise ValueError(f"seeds must be one integer or hold one per row ({n}), got {seeds.shape}")
-    elif seeds.dtype not in (torch.int64, torch.uint64) or tuple(seeds.shape) != (n,):
-        raise ValueError(f"seeds as a tensor must be int64 or uint64 [{n}]")
+    cell_size, origin_x, origin_y = _cell_origin(cell_size, origin)
+    max_path = _count("max_path", max_path)
+    starts, targets, boundaries = _points("starts", starts, n, 2), _points("targets", targets, n, 2), _boundaries(boundaries, n)
+    upload_seeds = _seeds(seeds, n)
+    hw_host = _hw_host(hw, n, h_max, w_max)
     n_nodes = n_samples + 2
     k = max_degree if by_radius else k_nearest
     max_edges = n_nodes * min(k, n_nodes - 1)
     lib = _ffi.lib()
     dev, st = _stream_of(device_id, stream)
     with torch.cuda.stream(st):
-        if _is_tensor(weight_grids):
-            w = weight_grids.to(dev, torch.float64).reshape(n, stride).contiguous()
-        else:
-            w = torch.as_tensor(np.ascontiguousarray(weight_grids, np.float64).reshape(n, stride)).to(dev)
-        hw_t = _i32(np.tile(np.int32([h_max, w_max]), (n, 1)) if hw is None else hw, dev, (n, 2))
+        w, hw_t, seed_t = upload(dev), _hw_dev(hw, hw_host, dev, n), upload_seeds(dev)
         s_t, t_t, b_t = _f64(starts, dev, (n, 2)), _f64(targets, dev, (n, 2)), _f64(boundaries, dev, (n, 4))
-        seed_t = seeds.to(dev).contiguous() if _is_tensor(seeds) else torch.as_tensor(seeds.view(np.int64)).to(dev)
         need = int(lib.t2d_prm_plan_workspace_bytes(n, n_samples, k))
-        row = need // n if n else 0
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (allocated on st: reused only behind this launch)
+        ws, part = _workspace(need, n, dev)
         path = torch.empty((n, max_path, 2), dtype=torch.float64, device=dev)
         path_len, status, n_edges, sweeps = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
         if n:   # (an empty batch has no memory to point at and nothing to launch)
             _ffi.check(lib.t2d_prm_plan(device_id, n, w.data_ptr(), hw_t.data_ptr(), stride, s_t.data_ptr(), t_t.data_ptr(), b_t.data_ptr(),
                                         seed_t.data_ptr(), n_samples, k_nearest if not by_radius else 1,
-                                        connection_radius if by_radius else 0.0, max_degree if by_radius else 1, cell_size, float(origin[0]),
-                                        float(origin[1]), max_path, ws.data_ptr(), need, path.data_ptr() if max_path else None,
+                                        connection_radius if by_radius else 0.0, max_degree if by_radius else 1, cell_size, origin_x,
+                                        origin_y, max_path, ws.data_ptr(), need, path.data_ptr() if max_path else None,
                                         path_len.data_ptr(), status.data_ptr(), n_edges.data_ptr(), sweeps.data_ptr(), st.cuda_stream),
                        None, lib)
-            rows = ws[:need].view(n, row)
-            part = lambda lo, hi, dt: rows[:, lo:hi].view(dt)   # (a row is a multiple of 256 bytes: every part stays aligned)
-            nodes = part(0, 16 * n_nodes, torch.float64).view(n, n_nodes, 2)
-            dist = part(16 * n_nodes, 24 * n_nodes, torch.float64)
-            edge_cost = part(24 * n_nodes, 24 * n_nodes + 8 * max_edges, torch.float64)
-            edge_ij = part(24 * n_nodes + 8 * max_edges, 24 * n_nodes + 16 * max_edges, torch.int32).view(n, max_edges, 2)
-        else:   # (an empty batch: nothing was launched, the views are empty tensors of the same shapes)
-            nodes = torch.empty((0, n_nodes, 2), dtype=torch.float64, device=dev)
-            dist = torch.empty((0, n_nodes), dtype=torch.float64, device=dev)
-            edge_cost = torch.empty((0, max_edges), dtype=torch.float64, device=dev)
-            edge_ij = torch.empty((0, max_edges, 2), dtype=torch.int32, device=dev)
+        nodes, dist = part(0, torch.float64, n_nodes, 2), part(16 * n_nodes, torch.float64, n_nodes)
+        edge_cost = part(24 * n_nodes, torch.float64, max_edges)
+        edge_ij = part(24 * n_nodes + 8 * max_edges, torch.int32, max_edges, 2)
     out = PRMPaths(path, path_len, status, n_edges, sweeps, nodes, edge_ij, edge_cost, dist)
     out._inputs = (w, hw_t, s_t, t_t, b_t, seed_t, ws)   # (kept alive with the result)
     return out
@@ -993,12 +940,7 @@ class PRM:
         neighbours doubles the room up to PRM_MAX_NODES, then RuntimeError.  max_iter: the reference's search pops at most
         2 * n_edges + 1 entries, so a max_iter at or above that cannot bind; below it ValueError -- a binding max_iter is not
         modelled.  Synchronous."""
-        if callback is not None:
-            raise TypeError(f"PRM.plan runs on the device, where a Python callable cannot be called: callback must be None, got {callback!r}")
-        if collide_fn is not None and collide_fn is not grid_collide:
-            raise TypeError("PRM.plan runs on the device, where a Python callable cannot be called: collide_fn must be None or "
-                            "tactics2d_amd.search.grid_collide (the grid collision checker of the reference's tests, which the kernel "
-                            f"implements over the weight grid passed as `obstacles`), got {collide_fn!r}")
+        _device_only("PRM.plan", callback, collide_fn)
         grid = np.asarray(obstacles, np.float64)
         if grid.ndim != 2:
             raise ValueError(f"obstacles must be a 2D weight grid, got shape {grid.shape}")
